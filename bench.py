@@ -6,16 +6,21 @@ the smoother launch (mfs, Pfs -> mss, Pss), inputs already resident in HBM.  Def
 discrete EKF + EKS of the demos' chirp model (demos/ekfs_mle.py), d = 4, T = 10 000, B = 1000 Monte-Carlo trials per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload kf|ekf|sgp|cd_sgp|cd_ekf|harmonic] [--batch B] [--T T]
-                    [--force-dist] [--no-other-configs] [--no-cpu-baseline]
+                    [--force-dist] [--dump-outputs DIR] [--full [--no-other-configs] [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last step if `--dump-outputs DIR` is given
+(DIR/<name>.npy, float64; a fixed sample of trials and time steps when the whole would exceed DUMP_LIMIT_BYTES) and prints
+the line.  Everything else described below -- the strong figure, the regime counters, the other configurations and the
+host-CPU baseline -- runs only with `--full`.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts N ranks itself (torch.distributed.run as a child
 process, one rank per GPU over RCCL; the parent never touches the GPU); under an external torchrun it checks that
 WORLD_SIZE == N.  Trials shard across ranks with no data-path collective; one all_gather of the per-trial final NLL
 happens after the timed region and is reported as gather_ms.  Scaling: C2 (`ekf`) is weak by default (B = 1000 per
-rank) and also reports the strong figure (B = 1000 in total) under "strong"; C3 / C5 (`sgp`, `harmonic`) are strong
+rank) and with `--full` also reports the strong figure (B = 1000 in total) under "strong"; C3 / C5 (`sgp`, `harmonic`) are strong
 by default ("batch=1000 sharded 8 GPUs", BASELINE.json); `--scaling weak|strong` overrides.  Rank 0 prints ONE JSON line.
 
-After the timed loop of the default workload (C2) the same process runs a few passes of the OTHER BASELINE configurations
+With `--full`, after the timed loop of the default workload (C2) the same process runs a few passes of the OTHER BASELINE configurations
 (C1 kf + rts, C3 sgp, C4 cd_sgp at 512 x 50 000 per GPU, C5 harmonic) and attaches their kernel times, throughput and
 roofline fractions under "other_configs" -- `value` stays C2's.  `--force-dist` takes the RCCL path (init_process_group
 ('nccl'), barrier, all_reduce, all_gather on device tensors) even with one rank.  The host-CPU baseline (the oracle's C port
@@ -245,6 +250,38 @@ def cpu_baseline(wl, target_seconds=10.0):
 
 LINE_LIMIT = 4096          # bytes of the ONE contract line on stdout (round 5's 24.7 KB line was not parsed by the driver)
 DETAILS_NAME = 'bench_details.json'
+# --dump-outputs: what a caller of the timed path receives, one .npy per array
+OUTPUT_NAMES = (('filter_means', 'filter_covs', 'filter_nll'), ('smoother_means', 'smoother_covs'))
+DUMP_LIMIT_BYTES = 32 << 20        # all files together; larger outputs are sampled
+DUMP_SEED = 20241016
+DUMP_MAX_TRIALS = 64
+
+
+def output_sample(f, s):
+    """The last step's filter outputs f = (mfs, Pfs, nll) and smoother outputs s = (mss, Pss), device tensors with leading axes
+    (B, T), as host float64 arrays named by OUTPUT_NAMES.  Whole when they fit in DUMP_LIMIT_BYTES; otherwise the same fixed sample
+    of every array: DUMP_MAX_TRIALS trials and as many time steps as the limit allows, drawn (sorted, without replacement) from
+    numpy default_rng(DUMP_SEED) -- the same indices for the same B and T, whichever build runs."""
+    import torch
+    arrays = {n: a for names, outs in zip(OUTPUT_NAMES, (f, s)) for n, a in zip(names, outs) if a is not None}
+    B, T = (int(x) for x in arrays['filter_means'].shape[:2])
+    per_trial_step = 8 * sum(int(np.prod(a.shape[2:])) for a in arrays.values())
+    if B * T * per_trial_step > DUMP_LIMIT_BYTES:
+        rng = np.random.default_rng(DUMP_SEED)
+        nb = min(B, DUMP_MAX_TRIALS)
+        nt = max(1, min(T, DUMP_LIMIT_BYTES // (nb * per_trial_step)))
+        trials = np.sort(rng.choice(B, nb, replace=False))
+        steps = np.sort(rng.choice(T, nt, replace=False))
+        dev = arrays['filter_means'].device
+        ti, si = torch.from_numpy(trials).to(dev), torch.from_numpy(steps).to(dev)
+        arrays = {n: a.index_select(0, ti).index_select(1, si) for n, a in arrays.items()}
+    return {n: a.cpu().numpy() for n, a in arrays.items()}
+
+
+def dump_outputs(folder, outputs):
+    os.makedirs(folder, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(folder, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def _finite(x):
@@ -396,9 +433,14 @@ def parse_args(argv=None):
     ap.add_argument('--batch', type=int, default=None,
                     help='trials: per GPU under weak scaling, in total under strong scaling (default: BASELINE config)')
     ap.add_argument('--T', type=int, default=None)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: the strong figure (N > 1), the regime counters, the other '
+                         'BASELINE configurations and the host-CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step (rank 0) as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the host-CPU baseline')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help='skip the passes of the other BASELINE configurations that follow the timed loop of the default workload')
+                    help='with --full: skip the passes of the other BASELINE configurations that follow the timed loop of the default workload')
     ap.add_argument('--other-steps', type=int, default=3, help='timed passes of each other configuration')
     ap.add_argument('--no-spread', action='store_true', help='skip other_configs.C2_spread (45 record sets of the headline shape)')
     ap.add_argument('--force-dist', action='store_true',
@@ -493,6 +535,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # Start the ranks as a child process BEFORE anything here imports torch or touches the GPU; never exec.
         import subprocess
@@ -547,9 +591,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(kind, mode, batch, T, steps, warmup, kw):
+    def measure(kind, mode, batch, T, steps, warmup, kw, count_regimes=True, keep_outputs=False):
         """`warmup` untimed and `steps` timed passes of workload `kind` under `mode` scaling -> measurements (wall time and
-        kernel times are the maximum over ranks)."""
+        kernel times are the maximum over ranks); with `keep_outputs` also this rank's output_sample() of the last timed pass."""
         if mode == 'strong':                          # contiguous shard of the total batch (SURVEY.md 8e)
             lo, hi = shard_bounds(batch, rank, world)
             B, B_total = hi - lo, batch
@@ -597,8 +641,9 @@ def main():
         sync()
         elapsed = time.perf_counter() - t0
         _engine.kernel_events = None
+        outputs = output_sample(f, s) if (keep_outputs and B > 0) else None
         regimes = None
-        if wl['kind'] == 'ekf' and B > 0:
+        if count_regimes and wl['kind'] == 'ekf' and B > 0:
             # which regimes of its speculative step the filter ran the 64-step chunks of THESE records in: one more, untimed,
             # launch with the context's counters switched on (include/chirpgp_hip.h: cgp_debug_set / cgp_debug_counters)
             _engine.debug_set(_engine.DBG_COUNT_REGIMES, 1)
@@ -632,7 +677,7 @@ def main():
         del f, s, ys_dev
         torch.cuda.empty_cache()
         return dict(wl=wl, kind=wl['kind'], T=T, steps=steps, B=B, B_total=B_total, elapsed=elapsed, gather_ms=gather_ms,
-                    filt_ms=mine[1], smooth_ms=mine[2], filt_ms_max=filt_max, smooth_ms_max=smooth_max, regimes=regimes)
+                    filt_ms=mine[1], smooth_ms=mine[2], filt_ms_max=filt_max, smooth_ms_max=smooth_max, regimes=regimes, outputs=outputs)
 
     def measure_time_split(steps):
         """The time-split filters with burn-in (cgp_filter_time_split) at the shard sizes BASELINE's 8-GPU configurations leave on one
@@ -799,15 +844,18 @@ def main():
     T = args.T or T_default
     kw = dict(flags=args.flags) if args.flags else {}
 
-    m = measure(args.workload, scaling, batch, T, args.steps, args.warmup, kw)
+    m = measure(args.workload, scaling, batch, T, args.steps, args.warmup, kw, count_regimes=args.full,
+                keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if m['outputs'] is not None:
+        dump_outputs(args.dump_outputs, m.pop('outputs'))
     # C2's north star also asks for the strong figure (1000 trials in total): measured right after, reported beside
-    other = measure(args.workload, 'strong', batch, T, args.steps, args.warmup, kw) if (world > 1 and scaling == 'weak' and args.workload == 'ekf') else None
+    other = measure(args.workload, 'strong', batch, T, args.steps, args.warmup, kw) if (args.full and world > 1 and scaling == 'weak' and args.workload == 'ekf') else None
     # The other BASELINE configurations under the same clock: a few passes each after the headline loop, their own default
     # sizes and scaling (C3 / C5: 1000 trials sharded; C4: 512 x 50 000 per GPU; C1: one record per rank).
     others = {}
     crlb = tsplit = spread = None
     default_shape = args.workload == 'ekf' and args.batch is None and args.T is None and not args.flags
-    if default_shape and not args.no_other_configs:
+    if args.full and default_shape and not args.no_other_configs:
         for tag, kind in OTHER_CONFIGS:
             _, Bo, To, mode_o, _ = WORKLOADS[kind if kind != 'ekf_low' else 'ekf']
             others[tag] = measure(kind, mode_o, Bo, To, args.other_steps, 1, {})
@@ -886,7 +934,7 @@ def main():
             if tsplit:
                 oc["time_split_filters"] = tsplit
             result["other_configs"] = oc
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:                                        # the GPU figures above are printed whatever happens to the host-side build / run
                 result["cpu_baseline"] = cpu_baseline(wl)
             except Exception as exc:                    # noqa: BLE001 -- gcc missing, OpenMP failing, ...: report it, keep the line

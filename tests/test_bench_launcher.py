@@ -122,3 +122,38 @@ def test_contract_line_is_compact_strict_json():
     # the details file is strict JSON too
     import tempfile
     assert json.loads(json.dumps(bench._finite(full), allow_nan=False))['steps'] == full['steps']
+
+
+def test_dumped_outputs_are_a_fixed_bounded_sample():
+    """--dump-outputs at the headline shape (1000 x 10^4, d = 4: 3.3 GB of outputs): every array sampled at the same sorted trials and
+    steps, the same in every run, float64, within the limit; a small output is written whole."""
+    import numpy as np
+    import torch
+    import bench
+
+    def outputs(B, T, d):
+        cell = torch.arange(B * T, dtype=torch.float64).reshape(B, T)            # value = trial * T + step
+        return ((cell[:, :, None].expand(B, T, d), cell[:, :, None, None].expand(B, T, d, d), cell),
+                (cell[:, :, None].expand(B, T, d), cell[:, :, None, None].expand(B, T, d, d)))
+    B, T = 1000, 10000
+    o = bench.output_sample(*outputs(B, T, 4))
+    assert set(o) == set(bench.OUTPUT_NAMES[0] + bench.OUTPUT_NAMES[1])
+    assert all(a.dtype == np.float64 for a in o.values()) and sum(a.nbytes for a in o.values()) <= bench.DUMP_LIMIT_BYTES <= 64 << 20
+    nll = o['filter_nll']
+    trials, steps = nll[:, 0] // T, nll[0, :] % T
+    assert len(trials) == bench.DUMP_MAX_TRIALS and len(steps) > 1000
+    assert np.all(np.diff(trials) > 0) and np.all(np.diff(steps) > 0) and np.array_equal(nll, trials[:, None] * T + steps[None, :])
+    for name in ('filter_means', 'filter_covs', 'smoother_covs'):
+        assert np.array_equal(o[name].reshape(nll.shape + (-1,)).min(-1), nll)
+    again = bench.output_sample(*outputs(B, T, 4))
+    assert all(np.array_equal(again[k], o[k]) for k in o)
+    small = bench.output_sample(*outputs(8, 300, 4))
+    assert small['smoother_covs'].shape == (8, 300, 4, 4) and np.array_equal(small['filter_nll'], np.arange(2400.).reshape(8, 300))
+
+
+def test_plain_run_flags():
+    import bench
+    a = bench.parse_args(['--steps', '7', '--warmup', '2'])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(['--full', '--dump-outputs', 'out'])
+    assert a.full and a.dump_outputs == 'out'

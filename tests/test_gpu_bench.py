@@ -36,7 +36,7 @@ def _no_constants(tok):
 
 
 def test_two_rank_rehearsal_prints_one_line_for_both_ranks():
-    r = _run('--gpus', '2', '--rehearse', '--batch', '8', '--T', '300', '--steps', '2', '--warmup', '1', '--no-cpu-baseline')
+    r = _run('--gpus', '2', '--rehearse', '--batch', '8', '--T', '300', '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline')
     assert r['n_gpus'] == 2 and r['ranks_seen'] == 2 and r['scaling'] == 'weak'
     assert r['config']['global_batch'] == 16 and r['config']['batch_per_gpu'] == 8
     assert r['gather_ms'] is not None and r['value'] > 0
@@ -50,7 +50,7 @@ def test_strong_default_for_the_sigma_point_configs():
 
 
 def test_single_gpu_line_carries_roofline_and_cpu_baseline():
-    r = _run('--batch', '64', '--T', '500', '--steps', '2', '--warmup', '1')
+    r = _run('--batch', '64', '--T', '500', '--steps', '2', '--warmup', '1', '--full')
     assert r['n_gpus'] == 1 and r['roofline']['bound'] == 'hbm' and r['roofline']['frac'] > 0
     assert 'traffic_source' in r['roofline'] and r['roofline']['algorithmic_frac'] > 0
     cb = r['cpu_baseline']
@@ -59,6 +59,30 @@ def test_single_gpu_line_carries_roofline_and_cpu_baseline():
     assert cb['one_core']['cores'] == 1 and 0 < cb['one_core']['value'] <= cb['value'] * 1.5
     assert '-march=native' in cb['build'] and '-DFIXED_D=4' in cb['build']
     assert 'other_configs' not in r                       # a non-default shape runs the named workload only
+
+
+def test_plain_run_and_its_dumped_outputs(tmp_path):
+    """A plain run measures the headline alone; --dump-outputs writes what its last timed step computed on the bench's seeded inputs:
+    the C port's filter and smoother on the same records, and the same arrays again from a second run with other step counts."""
+    import numpy as np
+    import bench
+    from oracle import port
+    from tests import cases as cs
+    a, b = tmp_path / 'a', tmp_path / 'b'
+    r = _run('--batch', '8', '--T', '300', '--steps', '3', '--warmup', '1', '--dump-outputs', str(a))
+    assert r['steps'] == 3 and r['ms_per_step'] > 0 and r['value'] > 0
+    assert r['regimes'] is None and not {'cpu_baseline', 'other_configs', 'strong'} & set(r)
+    _run('--batch', '8', '--T', '300', '--steps', '2', '--warmup', '0', '--dump-outputs', str(b))
+    wl = bench.make_workload(8, 300, seed=0, kind='ekf')
+    wf = port.filter(port.F_EKF, wl['disc'], None, wl['H'], wl['Xi'], wl['m0'], wl['P0'], wl['dt'], wl['ys'])
+    ws = port.smoother(port.S_EKS, wl['disc'], None, wl['dt'], wf[0], wf[1])
+    names = bench.OUTPUT_NAMES[0] + bench.OUTPUT_NAMES[1]
+    assert sorted(os.listdir(a)) == sorted(n + '.npy' for n in names)
+    for name, want in zip(names, wf + ws):
+        got = np.load(a / (name + '.npy'))
+        assert got.dtype == np.float64 and got.shape == want.shape, (name, got.shape)
+        assert cs.max_rel_err(got, want) <= 1e-5, name
+        np.testing.assert_allclose(np.load(b / (name + '.npy')), got, rtol=1e-12, atol=0)
 
 
 def test_world_one_rccl_path():
@@ -74,7 +98,7 @@ def test_world_one_rccl_path():
 def test_default_line_carries_the_other_baseline_configs():
     """The driver's command (default workload and sizes, fewer steps): C1, C3, C4, C5 ride on the same JSON line, each with its
     kernel times, throughput and both roofline fractions (executed and algorithmic) for the float64-bound ones."""
-    r = _run('--steps', '3', '--warmup', '1', '--other-steps', '1', '--no-cpu-baseline')
+    r = _run('--steps', '3', '--warmup', '1', '--full', '--other-steps', '1', '--no-cpu-baseline')
     assert r['config']['batch_per_gpu'] == 1000 and r['config']['T'] == 10000
     # counter traffic is quoted only from a profile of the very library that ran (sha256 recorded in profiles/r05_ekf_pmc.json); any other
     # library gets null and the reason -- never a stale figure
@@ -145,7 +169,7 @@ def test_three_rank_rehearsal_of_the_scaling_command():
     other_configs and the gathers, rank 0 alone times the host CPU once, and the whole run stays far inside the driver's 600 s."""
     import time
     t0 = time.time()
-    r = _run('--gpus', '3', '--rehearse', '--steps', '2', '--warmup', '1', '--other-steps', '1')
+    r = _run('--gpus', '3', '--rehearse', '--steps', '2', '--warmup', '1', '--full', '--other-steps', '1')
     took = time.time() - t0
     assert r['n_gpus'] == 3 and r['ranks_seen'] == 3 and r['collectives'].startswith('gloo')
     assert r['scaling'] == 'weak' and r['config']['batch_per_gpu'] == 1000 and r['config']['global_batch'] == 3000
@@ -165,7 +189,7 @@ def test_two_rank_rehearsal_of_the_default_line():
     """The driver's N > 1 command in rehearsal (two ranks on the one GPU, gloo collectives): the default shapes, so the ranks go
     through `other_configs` (C3 / C5 sharded 500 + 500, C4 and C1 per rank), the strong C2 figure, the final gathers, and rank 0
     times the host CPU AFTER the process group is gone -- the control flow a multi-GPU node will run, which no other test reaches."""
-    r = _run('--gpus', '2', '--rehearse', '--steps', '2', '--warmup', '1', '--other-steps', '1')
+    r = _run('--gpus', '2', '--rehearse', '--steps', '2', '--warmup', '1', '--full', '--other-steps', '1')
     assert r['n_gpus'] == 2 and r['ranks_seen'] == 2 and r['collectives'].startswith('gloo')
     assert r['config']['batch_per_gpu'] == 1000 and r['config']['global_batch'] == 2000 and r['strong']['batch_per_gpu'] == 500
     oc = r['other_configs']
