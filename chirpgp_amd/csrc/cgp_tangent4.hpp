@@ -45,6 +45,7 @@ struct TangentIO {
     }
 };
 
+#ifndef CGP_TANGENT4_IO_ONLY      // cgp_inst_tangent4_sgp.hip takes TangentIO and not a second copy of this kernel
 __global__ void __launch_bounds__(64) ekf4_tangent_kernel(TangentIO io, ModelArgs ma) {
     const int64_t gidx = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const int64_t total = io.B * io.n_dir;
@@ -173,5 +174,6 @@ inline hipError_t launch_ekf4_tangent(const TangentIO& io, const ModelArgs& ma, 
     hipLaunchKernelGGL(ekf4_tangent_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, stream, io, ma);
     return hipGetLastError();
 }
+#endif  // CGP_TANGENT4_IO_ONLY
 
 }  // namespace cgp

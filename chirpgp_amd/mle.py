@@ -55,7 +55,7 @@ def batched_nll(method, build, thetas, ys, Xi, dt, sgps=None, record_index=None,
     return nll.cpu().numpy() if type(nll).__module__.startswith('torch') else np.asarray(nll)
 
 
-# ---- exact gradients: forward tangents through the scan (include/chirpgp_hip.h: cgp_ekf_nll_grad) ------------------------------
+# ---- exact gradients: forward tangents through the scan (include/chirpgp_hip.h: cgp_ekf_nll_grad, cgp_sgp_nll_grad) ------------
 def _m32_c(ell, sigma, dt):
     """models.py:61-73 for complex arguments (the complex step below)."""
     gamma = np.sqrt(3.) / ell
@@ -112,9 +112,19 @@ def tangent_directions(build, thetas, dt, Xi, h=1e-30):
     return out
 
 
-def has_exact_gradient(method, build, Xi):
-    """The in-kernel tangent gradient exists for the discrete EKF on the d = 4 chirp and La Scala models with a scalar Xi."""
-    return method == 'ekf' and _constants_of(build) is not None and np.ndim(Xi) == 0
+def _sigma_dim(sgps):
+    xi = getattr(sgps, 'xi', None)
+    return None if xi is None or np.ndim(xi) != 2 else int(np.shape(xi)[1])
+
+
+def has_exact_gradient(method, build, Xi, sgps=None):
+    """The in-kernel tangent gradient exists on the d = 4 chirp and La Scala models with a scalar Xi for the discrete EKF
+    (cgp_ekf_nll_grad) and for the sigma-point filter with a d = 4 sigma-point set ``sgps`` (cgp_sgp_nll_grad)."""
+    if _constants_of(build) is None or np.ndim(Xi) != 0:
+        return False
+    if method == 'ekf':
+        return True
+    return method == 'sgp_filter' and _sigma_dim(sgps) == 4
 
 
 # Which form is the default (``exact=None``).  Measured on MI355X at T = 3141 (tools/grad_bench.py, profiles/r06_grad_bench.txt): the tangent
@@ -126,13 +136,21 @@ EXACT_FROM_RECORDS = 1500
 
 
 def _exact_by_default(method, build, Xi, n_records, build_kw):
-    return has_exact_gradient(method, build, Xi) and not build_kw and n_records >= EXACT_FROM_RECORDS
+    return method == 'ekf' and has_exact_gradient(method, build, Xi) and not build_kw and n_records >= EXACT_FROM_RECORDS
 
 
-def value_and_grad(build, thetas, ys, Xi, dt, record_index=None):
-    """EKF objective and its EXACT gradient (forward tangents through the scan, cgp_ekf_nll_grad) at every row of thetas (G, P):
-    ONE launch of G P lanes; ys (T,) or (R, T) shared out evenly over the rows as in batched_nll.  -> (nll (G,), grad (G, P))."""
+def _exact_unsupported():
+    return ValueError('exact=True: the tangent kernels are built for the discrete EKF and the sigma-point filter (with a d = 4 sigma-point '
+                      'set, sgps=) on build_chirp_model / build_lascala_model with a scalar Xi')
+
+
+def value_and_grad(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf', sgps=None):
+    """Objective and its EXACT gradient (forward tangents through the scan) at every row of thetas (G, P), in ONE launch: the EKF's
+    (method='ekf', cgp_ekf_nll_grad: G P lanes) or the sigma-point filter's (method='sgp_filter' with a d = 4 SigmaPoints ``sgps``,
+    cgp_sgp_nll_grad: G wavefronts).  ys (T,) or (R, T) shared out evenly over the rows as in batched_nll.  -> (nll (G,), grad (G, P))."""
     from chirpgp_amd import _engine as E
+    if not has_exact_gradient(method, build, Xi, sgps):
+        raise _exact_unsupported()
     thetas = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
     G = thetas.shape[0]
     n_rec = 1 if np.ndim(ys) == 1 else int(np.shape(ys)[0])
@@ -143,25 +161,29 @@ def value_and_grad(build, thetas, ys, Xi, dt, record_index=None):
     with np.errstate(all='ignore'):
         drift, disp, disc, m0, P0, H = build(M.g(thetas))
     dirs = tangent_directions(build, thetas, dt, Xi)
-    nll, grad = E.run_ekf_nll_grad(disc, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=G // n_rec, record_index=record_index)
+    if method == 'sgp_filter':
+        nll, grad = E.run_sgp_nll_grad(disc, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=G // n_rec, record_index=record_index)
+    else:
+        nll, grad = E.run_ekf_nll_grad(disc, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=G // n_rec, record_index=record_index)
     return nll.cpu().numpy(), grad.cpu().numpy()
 
 
 def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=None, **build_kw):
     """-> fun(theta) returning (nll, gradient): value and central differences from one batched launch of 2 P + 1 filter passes, or --
-    ``exact=True``, the discrete EKF on the chirp / La Scala models -- value and EXACT gradient from one launch of the tangent kernel
-    (cgp_ekf_nll_grad: 4e-14 of the gradient's scale against 100-digit arithmetic where the differences carry 2e-7; slower for a single
-    record, see EXACT_FROM_RECORDS)."""
+    ``exact=True``, the discrete EKF or the sigma-point filter (with a d = 4 ``sgps``) on the chirp / La Scala models -- value and EXACT
+    gradient from one launch of a tangent kernel (cgp_ekf_nll_grad: 4e-14 of the gradient's scale against 100-digit arithmetic where the
+    differences carry 2e-7; slower for a single record, see EXACT_FROM_RECORDS; cgp_sgp_nll_grad).  exact=None takes the tangent kernel
+    for the EKF from EXACT_FROM_RECORDS records only and never for the sigma-point filter."""
     if exact is None:
         exact = _exact_by_default(method, build, Xi, 1, build_kw)
     if exact:
-        if not has_exact_gradient(method, build, Xi) or build_kw:
-            raise ValueError('exact=True: the tangent kernel is built for the discrete EKF on build_chirp_model / build_lascala_model with a scalar Xi')
+        if not has_exact_gradient(method, build, Xi, sgps) or build_kw:
+            raise _exact_unsupported()
         from chirpgp_amd import _engine as E
         ys_dev = E.dev(ys)
 
         def fun_exact(theta):
-            f, g_ = value_and_grad(build, np.asarray(theta, dtype=np.float64)[None, :], ys_dev, Xi, dt)
+            f, g_ = value_and_grad(build, np.asarray(theta, dtype=np.float64)[None, :], ys_dev, Xi, dt, method=method, sgps=sgps)
             if not np.isfinite(f[0]):                   # diverged filter: the reference writes NaN results and moves on
                 return np.inf, np.zeros(np.size(theta))
             return float(f[0]), np.where(np.isfinite(g_[0]), g_[0], 0.0)
@@ -196,15 +218,15 @@ def fit(method, build, init_params, ys, Xi, dt, sgps=None, maxiter=200, exact=No
 
 def _value_and_grad_many(method, build, thetas, yss, Xi, dt, sgps, rel_step, build_kw, record_index=None, exact=None):
     """NLL and gradient of R records (the rows ``record_index`` of yss; all of them by default) at R parameter vectors: exact (the tangent
-    kernel, R P lanes) for the discrete EKF on the chirp / La Scala models, else central differences -- ONE launch of R (2 P + 1)
-    trials, each record read in place by its 2 P + 1 probes."""
+    kernel, R P lanes) for the discrete EKF on the chirp / La Scala models (and, with exact=True, the sigma-point filter's, R wavefronts),
+    else central differences -- ONE launch of R (2 P + 1) trials, each record read in place by its 2 P + 1 probes."""
     R, P = thetas.shape
     if exact is None:
         exact = _exact_by_default(method, build, Xi, R, build_kw)
     if exact:
-        if not has_exact_gradient(method, build, Xi) or build_kw:
-            raise ValueError('exact=True: the tangent kernel is built for the discrete EKF on build_chirp_model / build_lascala_model with a scalar Xi')
-        f, grad = value_and_grad(build, thetas, yss, Xi, dt, record_index=record_index)
+        if not has_exact_gradient(method, build, Xi, sgps) or build_kw:
+            raise _exact_unsupported()
+        f, grad = value_and_grad(build, thetas, yss, Xi, dt, record_index=record_index, method=method, sgps=sgps)
         f = f.copy()
         f[~np.isfinite(f)] = np.inf
         return f, np.where(np.isfinite(grad), grad, 0.0)

@@ -96,15 +96,16 @@ def run_records(method, yss, Xi, dt, sgps=None, num_harmonics=0, maxiter=200, in
     return dict(opt_params=params, fun=info['fun'], nll0=nll0, mss=mss, Pss=Pss, est_freq=est, nit=info['nit'], launches=info['launches'])
 
 
-def run_record(method, ys, Xi, dt, sgps=None, num_harmonics=0, maxiter=200, init=None, family=None, keep_rows=True):
+def run_record(method, ys, Xi, dt, sgps=None, num_harmonics=0, maxiter=200, init=None, family=None, keep_rows=True, exact=False):
     """MLE -> filter -> smoother -> E[g(V)] on one measurement record.
     method: 'ekfs' | 'ghfs' | 'cd_ekfs' | 'cd_ghfs' | 'kpt';  family: 'chirp' | 'harmonic' | 'lascala' | 'kpt'
     (default: 'kpt' for method 'kpt', else 'harmonic' when num_harmonics > 0, else 'chirp').
+    exact=True: the fit's gradient from a tangent kernel (chirpgp_amd.mle.make_objective) instead of the default route.
     Returns a dict with opt_params, the scipy result, nll0 (objective at the start), the smoothing results and est_freq."""
     build, init, build_kw = _family_setup(method, family, num_harmonics, dt, init)
     filt = FILTER_OF[method]
     nll0 = float(mle.batched_nll(filt, build, np.log(np.expm1(np.asarray(init, dtype=np.float64))), ys, Xi, dt, sgps, **build_kw)[0])
-    opt_params, res = mle.fit(filt, build, init, ys, Xi, dt, sgps=sgps, maxiter=maxiter, **build_kw)
+    opt_params, res = mle.fit(filt, build, init, ys, Xi, dt, sgps=sgps, maxiter=maxiter, exact=True if exact else None, **build_kw)
     mss, Pss, est = _filter_and_smooth(method, build, build_kw, opt_params, sgps, Xi, dt, ys, keep_rows)
     return dict(opt_params=opt_params, res=res, nll0=nll0, mss=mss, Pss=Pss, est_freq=est)
 
@@ -124,18 +125,19 @@ def records_of_run(seed, T, dt, Xi, signal_harmonics, mags=None):
 
 
 def demo(method, sgps=None, num_harmonics=0, T=3141, seed=555, Xi=0.1, dt=0.001, maxiter=200, save_dir=None, mags=None, quiet=False,
-         family=None, signal_harmonics=None, result_name=None, mc=None):
+         family=None, signal_harmonics=None, result_name=None, mc=None, exact=False):
     """One run per magnitude law, as the reference's demo scripts do; returns [(name, rmse, nll0, nll_opt), ...].
     ``signal_harmonics``: harmonics of the SIGNAL (default: those of the model); ``result_name``: file stem of the saved
     results (the reference's jobs: 'kpt_mle', 'lascala_ekfs_mle', ...; default: the method name), numbered ``mc`` (default: the
-    position of the magnitude law, as the demos have a single run)."""
+    position of the magnitude law, as the demos have a single run); ``exact``: fit with the exact gradient (run_record)."""
     sig_h = num_harmonics if signal_harmonics is None else signal_harmonics
     ts = np.linspace(dt, dt * T, T)
     true_freq_func, _ = meow_freq(offset=8.)
     out = []
     for k, name, ys in records_of_run(seed, T, dt, Xi, sig_h, mags):
         t0 = time.time()
-        r = run_record(method, ys, Xi, dt, sgps=sgps, num_harmonics=num_harmonics, maxiter=maxiter, family=family, keep_rows=bool(save_dir))
+        r = run_record(method, ys, Xi, dt, sgps=sgps, num_harmonics=num_harmonics, maxiter=maxiter, family=family, keep_rows=bool(save_dir),
+                       exact=exact)
         err = float(rmse(true_freq_func(ts), r['est_freq'])) if r['res'].success or np.isfinite(r['res'].fun) else float('nan')
         if save_dir:       # tetralith/jobs/ekfs_mle.py:75-81: NaN results for a diverged run
             results.save_result(save_dir, result_name or method, name, k if mc is None else mc, r['mss'], r['Pss'], err)

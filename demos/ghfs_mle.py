@@ -1,7 +1,10 @@
 """Counterpart of the reference's demos/ghfs_mle.py (BASELINE config C3's driver): Gauss-Hermite (order 3, 81 points)
 sigma-point filter and smoother on the chirp model, parameters by MLE through the filter.
 
-    python demos/ghfs_mle.py [--T 3141] [--seed 555] [--save DIR]
+    python demos/ghfs_mle.py [--T 3141] [--seed 555] [--save DIR] [--exact]
+
+--exact: the objective's gradient from the sigma-point tangent kernel (cgp_sgp_nll_grad: forward tangents through the scan, what
+jax.value_and_grad gives the reference) instead of 13-probe central differences.
 """
 import argparse
 
@@ -13,5 +16,6 @@ if __name__ == '__main__':
     ap.add_argument('--T', type=int, default=3141)
     ap.add_argument('--seed', type=int, default=555)
     ap.add_argument('--save', default=None, help='directory for <method>_<mag>_<mc>.npz result files')
+    ap.add_argument('--exact', action='store_true', help='exact gradients (tangent kernel)')
     a = ap.parse_args()
-    demo('ghfs', sgps=SigmaPoints.gauss_hermite(d=4, order=3), T=a.T, seed=a.seed, save_dir=a.save)
+    demo('ghfs', sgps=SigmaPoints.gauss_hermite(d=4, order=3), T=a.T, seed=a.seed, save_dir=a.save, exact=a.exact)

@@ -19,6 +19,7 @@
  *   cgp_smoother_select                                                the smoothers above + the marginal step behind them in every driver
  *                                                                      (demos/ekfs_mle.py:69-77: mss[:, k], Pss[:, k, k], gaussian_expectation), fused
  *   cgp_ekf_nll_grad                                                   value_and_grad of ekf(...)[-1][-1] through the scan, demos/ekfs_mle.py:43-51
+ *   cgp_sgp_nll_grad                                                   value_and_grad of sgp_filter(...)[-1][-1] through the scan, demos/ghfs_mle.py:53-56
  *   cgp_model_from_source, cgp_filter_custom, cgp_smoother_custom      ekf / eks / cd_ekf / cd_eks on ANY model (the reference traces any callable:
  *                                                                      filters_smoothers.py:255, 342, 382, 425; test/test_ekfs.py:11-62), compiled at run time
  *   cgp_gaussian_expectation                                           gaussian_expectation quadratures.py:234-274
@@ -227,6 +228,17 @@ int cgp_filter_time_split(cgp_ctx* ctx, int method, const cgp_model* model, cons
  * (trial, direction). */
 #define CGP_DIR_DOUBLES 24
 int cgp_ekf_nll_grad(cgp_ctx* ctx, const cgp_model* model, const cgp_init* init, double dt,
+                     const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
+                     const double* dirs, int32_t n_dir, double* nll, double* grad, uint32_t flags, void* stream);
+
+/* The same for the sigma-point filter (sgp_filter, filters_smoothers.py:446-490): its final negative log-likelihood and exact gradient
+ * by forward tangents through the scan -- the Cholesky factor's tangent, every sigma point's tangent through the model, the tangents of
+ * the predicted moments' sums and of the update (demos/ghfs_mle.py:53-56, tetralith/jobs/lascala_ghfs_mle.py).  The same models (d = 4
+ * chirp / La Scala LCD), directions, records and outputs as cgp_ekf_nll_grad, with ANY d = 4 sigma-point set: the kernel takes the
+ * literal sum over the points (group_start and the CGP_SIGMA_* flags are not needed and not used).  One wavefront per trial; B < 2^31.
+ * CGP_E_UNSUPPORTED for another model or a set of another dimension; a Cholesky that breaks down writes NaN to nll and grad, as
+ * sgp_filter writes NaN; T = 0 writes nll = 0 and grad = 0. */
+int cgp_sgp_nll_grad(cgp_ctx* ctx, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init, double dt,
                      const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
                      const double* dirs, int32_t n_dir, double* nll, double* grad, uint32_t flags, void* stream);
 
