@@ -169,7 +169,7 @@ __global__ void __launch_bounds__(64) ekf4_tangent_kernel(TangentIO io, ModelArg
 }
 
 inline hipError_t launch_ekf4_tangent(const TangentIO& io, const ModelArgs& ma, hipStream_t stream) {
-    if (io.B <= 0 || io.T <= 0 || io.n_dir <= 0) return hipSuccess;
+    if (io.B <= 0 || io.n_dir <= 0) return hipSuccess;                    // (T == 0 launches: the kernel skips its loop and writes nll = 0, grad = 0)
     const int64_t total = io.B * io.n_dir;
     hipLaunchKernelGGL(ekf4_tangent_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, stream, io, ma);
     return hipGetLastError();

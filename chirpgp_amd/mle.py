@@ -56,25 +56,63 @@ def batched_nll(method, build, thetas, ys, Xi, dt, sgps=None, record_index=None,
 
 
 # ---- exact gradients: forward tangents through the scan (include/chirpgp_hip.h: cgp_ekf_nll_grad, cgp_sgp_nll_grad) ------------
+def _horner(x, coeffs):
+    """sum_k coeffs[k] x^k (complex-safe)."""
+    acc = coeffs[-1] + 0. * x
+    for c in coeffs[-2::-1]:
+        acc = acc * x + c
+    return acc
+
+
+_FACT = np.cumprod(np.r_[1., np.arange(1., 40.)])                       # k!
+_SERIES_TERMS = 26                                                      # x <= 1: x^26 / 26! = 2.5e-27
+_PHI = [(-1.) ** k / _FACT[k + 1] for k in range(_SERIES_TERMS)]         # (1 - exp(-x)) / x = sum (-x)^k / (k + 1)!
+_PSI = [1. / _FACT[k + 3] for k in range(_SERIES_TERMS)]                 # (exp(x) - 1 - x - x^2 / 2) / x^3 = sum x^k / (k + 3)!
+_F00 = [(-1.) ** k * (-1. - k) / _FACT[k + 2] for k in range(_SERIES_TERMS)]   # ((1 + x) exp(-x) - 1) / x^2 = sum (-1)^k (-1 - k) / (k + 2)! x^k
+
+
+def _below(x, at, series, closed):
+    """series where Re x < at, closed elsewhere (both complex-safe; the unused side may be NaN)."""
+    return np.where(np.real(x) < at, series, closed)
+
+
+def _decay_ratio(x):
+    """(1 - exp(-x)) / x without the cancellation of its numerator -- nor of its DERIVATIVE's (x exp(-x) - (1 - exp(-x))) / x^2, which the
+    complex step through expm1(-x) / x still carries at eps / x: the alternating series below x = 0.5 (x = 0 included), -expm1(-x) / x above."""
+    safe = np.where(np.real(x) < 0.5, 1., x)
+    return _below(x, 0.5, _horner(x, _PHI), -np.expm1(-safe) / safe)
+
+
 def _m32_c(ell, sigma, dt):
-    """models.py:61-73 for complex arguments (the complex step below)."""
+    """models.py:61-73 for complex arguments (the complex step below), in forms whose real AND imaginary parts carry no cancellation.
+    With x = 2 eta, eta = sqrt(3) dt / ell:
+        Sigma[0] = sigma^2 (1 - exp(-x) (1 + x + x^2 / 2))                   = sigma^2 exp(-x) x^3 psi(x)
+        Sigma[2] = gamma^2 sigma^2 (1 - exp(-x) (1 - x + x^2 / 2))           = gamma^2 sigma^2 exp(-x) (2 x + x^3 psi(x))
+        F[0]     = (1 + eta) exp(-eta)                                       = 1 + eta^2 sum (-1)^k (-1 - k) / (k + 2)! eta^k
+    psi(x) = sum x^k / (k + 3)! (positive terms): the series below x = 1 (eta = 0.5 for F[0]), the reference's closed form above, where its
+    cancellation costs a factor of 12 at most.  (The primal -- csrc/cgp_models.hpp, models.py -- keeps the reference's formulas: the directions
+    are the derivatives of the function those approximate to their own rounding.)"""
     gamma = np.sqrt(3.) / ell
     eta = dt * gamma
-    beta = sigma ** 2 * np.exp(-2 * eta)
+    x = 2 * eta
+    e2 = np.exp(-x)
+    beta = sigma ** 2 * e2
     e = np.exp(-eta)
-    F = np.array([(1 + eta) * e, dt * e, -dt * gamma ** 2 * e, (1 - eta) * e])
+    F = np.array([_below(eta, 0.5, 1. + eta * eta * _horner(eta, _F00), (1 + eta) * e), dt * e, -dt * gamma ** 2 * e, (1 - eta) * e])
     off = 2 * dt ** 2 * gamma ** 3 * beta
-    S = np.array([sigma ** 2 - beta * (2 * eta + 2 * eta ** 2 + 1), off, gamma ** 2 * (sigma ** 2 + beta * (2 * eta - 2 * eta ** 2 - 1))])
-    return F, S
+    tail = x ** 3 * _horner(x, _PSI)                                     # exp(x) - 1 - x - x^2 / 2
+    S0 = _below(x, 1., beta * tail, sigma ** 2 - beta * (2 * eta + 2 * eta ** 2 + 1))
+    S2 = gamma ** 2 * _below(x, 1., beta * (2 * x + tail), sigma ** 2 + beta * (2 * eta - 2 * eta ** 2 - 1))
+    return F, np.array([S0, off, S2])
 
 
 def _chirp_constants(p, dt, Xi):
     """The 24 model constants a tangent direction differentiates (include/chirpgp_hip.h: CGP_DIR_DOUBLES), as functions of the chirp
     builder's parameters lam, b, delta, ell, sigma, m0_v (models.py:437-459, 264-311, 56-58) -- complex-safe, vectorised over a
-    trailing axis: p (6, G) -> (24, G)."""
+    trailing axis: p (6, G) -> (24, G).  q = b^2 (1 - exp(-2 lam dt)) / (2 lam) = b^2 dt phi(2 lam dt) with phi = _decay_ratio: one smooth
+    function whose lam = 0 value is the reference's other branch, b^2 dt."""
     lam, b, delta, ell, sigma, m0_v = p
-    safe = np.where(lam == 0., 1., lam)
-    q = np.where(lam == 0., b ** 2 * dt, b ** 2 / (2 * safe) * (1 - np.exp(-2 * safe * dt)))
+    q = b ** 2 * dt * _decay_ratio(2 * lam * dt)
     F, S = _m32_c(ell, sigma, dt)
     zero = 0. * lam
     P0 = [delta, zero, delta, zero, zero, sigma ** 2, zero, zero, zero, (np.sqrt(3.) / ell) ** 2 * sigma ** 2]
@@ -97,13 +135,22 @@ def _constants_of(build):
 def tangent_directions(build, thetas, dt, Xi, h=1e-30):
     """d (model constants) / d theta_k for every row of thetas (G, P) -> (G, P, 24): complex-step derivatives of the builder's constants
     with respect to the positive parameters (exact to rounding), times d g(theta) / d theta = sigmoid(theta) (the reference's
-    parametrisation, demos/ekfs_mle.py:39-47).  (lam = 0 exactly takes the branch's own derivative, as jax.lax.cond would.)"""
+    parametrisation, demos/ekfs_mle.py:39-47).
+
+    The constants are differentiated in cancellation-free forms (_decay_ratio, _m32_c), not in the reference's: the complex step is exact
+    for the formula it is given, its rounding included, and `1 - exp(-2 lam dt)` over `lam` or `sigma^2 - beta (2 eta + 2 eta^2 + 1)` lose
+    every digit of their derivative for lam << 1 or a large ell (the lam-entry of d q was off by a factor of 27 at lam = 1e-6).  The primal
+    -- the kernels' cgp_models.hpp, models.py, the checker's port -- keeps the reference's formulas for parity with it, so the gradient returned is
+    the derivative of the function that primal approximates to its own rounding, not of the rounded formula.  Every entry is within 1e-12
+    of the derivative taken in 100-digit arithmetic over lam 0 .. 10, b 1e-4 .. 10, ell 1e-2 .. 100, sigma 1e-2 .. 10
+    (tests/test_gradient_directions.py).  At lam = 0 exactly (theta_lam -> -inf) d q / d lam is the limit -b^2 dt^2 and the entry is 0 with
+    sigmoid(theta_lam)."""
     consts = _constants_of(build)
     thetas = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
     G, P = thetas.shape
     out = np.empty((G, P, 24))
     with np.errstate(all='ignore'):
-        params = M.g(thetas).T                                   # (P, G)
+        params = np.logaddexp(0., thetas).T                      # (P, G): g(theta) to rounding (M.g's naive form is off by 1e-16 / g)
         dg = 1.0 / (1.0 + np.exp(-thetas))
         for k in range(P):
             pc = params.astype(np.complex128)
@@ -171,8 +218,8 @@ def value_and_grad(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf'
 def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=None, **build_kw):
     """-> fun(theta) returning (nll, gradient): value and central differences from one batched launch of 2 P + 1 filter passes, or --
     ``exact=True``, the discrete EKF or the sigma-point filter (with a d = 4 ``sgps``) on the chirp / La Scala models -- value and EXACT
-    gradient from one launch of a tangent kernel (cgp_ekf_nll_grad: 4e-14 of the gradient's scale against 100-digit arithmetic where the
-    differences carry 2e-7; slower for a single record, see EXACT_FROM_RECORDS; cgp_sgp_nll_grad).  exact=None takes the tangent kernel
+    gradient from one launch of a tangent kernel (cgp_ekf_nll_grad: within 8e-13 of the gradient's scale against 100-digit arithmetic where
+    the differences carry 2e-7; slower for a single record, see EXACT_FROM_RECORDS; cgp_sgp_nll_grad).  exact=None takes the tangent kernel
     for the EKF from EXACT_FROM_RECORDS records only and never for the sigma-point filter."""
     if exact is None:
         exact = _exact_by_default(method, build, Xi, 1, build_kw)
