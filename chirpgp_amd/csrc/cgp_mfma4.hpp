@@ -16,9 +16,14 @@
 //     S = H . PH + Xi       mfma(A = H[r],          B = PH[r], C = Xi)       lands in every lane
 //
 // Five matrix instructions replace the 85 DPP moves and FMAs of the cooperative kernel's covariance algebra
-// (cgp_coop4.hpp), three more carry the mean (ekf4_mfma_finish); what stays on the vector ALU is the scalar chain
-// softplus -> rotation and the rank-one update.  This is not a GEMM-shaped workload being forced onto MFMA: the products ARE 4 x 4 x 4, and the instruction
-// is used for its latency (one issue slot, 4 passes) on a T-serial chain.
+// (cgp_coop4.hpp); in this general form three more carry the mean (ekf4_mfma_finish_j, E1 == 0); what stays on the vector
+// ALU is the scalar chain softplus -> rotation and the rank-one update.  This is not a GEMM-shaped workload being forced onto
+// MFMA: the products ARE 4 x 4 x 4, and the instruction is used for its latency (one issue slot, 4 passes) on a T-serial chain.
+//
+// The form every chirp / La Scala model runs (H = e_1, E1 != 0) takes THREE matrix instructions a step -- Q, Pp and H Pp by
+// column: H picks entries of Q and Pp instead of contracting with them, and the mean lives by column only, its prediction
+// f = J0 u being a quad swap, a multiply and an FMA per lane because J0 = blockdiag(rho Rot(theta), M32) is 2 x 2
+// block-diagonal (see ekf4_mfma_finish_j and Ekf4Anchor).
 //
 // Speculation.  The step is one dependent chain, and a branch anywhere in it costs far more than its own cycles: it
 // cuts the step into basic blocks that cannot be interleaved (tools/ekf_variants.py: 167 cycles of a 1070-cycle step
@@ -48,13 +53,30 @@ struct Ekf4MfmaConst {
     double kc, ks, kj, kk;                     // J[q][r] = kc c + ks s + kk + kj dth f[q ^ 1]  (kj = -1 at (0, 2), +1 at (1, 2))
     double SigHq, c0;                          // H = e_1 form of the update: Sigma[1][q], Sigma[1][1] + Xi
     double kcr, ksr, kja;                      // kc rho, ks rho, kj ang: the damping and the angle scale ride in the per-lane coefficients
-    double angm;                               // ang in the lanes of the rotation block, 0 elsewhere (see Ekf4Anchor)
+    double angm;                               // fold(): ang in the lanes of the rotation block, 0 elsewhere; fold_e1(): +ang, -ang, 0, 0 by column (see Ekf4Anchor)
+    // H = e_1 form (fold_e1): the lane's COLUMN pair (A2, B2) = (pa cos + pA0, pb sin + pB0) and its two uses (Ekf4Anchor)
+    double pa, pb, pA0, pB0, m1, m2;
     CGP_DEV void fold() { kcr = kc * rho; ksr = ks * rho; kja = kj * ang; angm = (kc != 0.0 || ks != 0.0) ? ang : 0.0; }
+    // lane (r, q) of the H = e_1 form: the pair is (rho cos, -+ rho sin) in columns 0 / 1, (M0, M1) / (M3, M2) in columns 2 / 3; the angle
+    // scale is +ang in column 0, -ang in column 1 (the pair of column 1 turns BACKWARDS: its sine term has the opposite sign) and 0 beyond
+    // (of what fold() sets, this path reads kja alone: kcr and ksr, like kc, ks and kk, belong to the general form)
+    CGP_DEV void fold_e1(int r, int q) {
+        fold();
+        angm = q == 0 ? ang : (q == 1 ? -ang : 0.0);
+        pa = q < 2 ? rho : 0.0;
+        pb = q == 0 ? -rho : (q == 1 ? rho : 0.0);
+        pA0 = q == 2 ? M0 : (q == 3 ? M3 : 0.0);
+        pB0 = q == 2 ? M1 : (q == 3 ? M2 : 0.0);
+        m1 = r == q ? 1.0 : 0.0;
+        m2 = r == (q ^ 1) ? 1.0 : 0.0;
+    }
 };
 // The mean is distributed like the covariance: ur = u[r] (row layout) and uq = u[q] (column layout) at lane (r, q); the
-// frequency state u[2] every lane needs is one quad broadcast of uq.
+// frequency state u[2] every lane needs is one quad broadcast of uq.  The H = e_1 form carries uq ALONE (ur is neither read
+// nor written there): every consumer of the mean -- the u[2] broadcast, the quad swap for the Jacobian column, H . f = f[1],
+// the stores, the junction state of a time-split launch -- reads the column form.
 struct Ekf4State {
-    double P, ur, uq;
+    double P, ur, uq;                                                          // (ur: read and updated by the general form only; 0 in the H = e_1 form)
     CGP_DEV double u2() const { return dpp_f64<kQuadBcast2>(uq); }
     CGP_DEV double u2_replicated() const { return row_bcast_f64<2>(uq); }      // one trial per wavefront: the four blocks are replicas
 };
@@ -76,7 +98,15 @@ struct Ekf4State {
 //     S = Pp[1][1] + Xi                                 E1 == 2 (one trial per wavefront): entry 1 of (H Pp) by column, one row broadcast;
 //                                                        E1 == 1 (one trial per MFMA block, the x4 kernel): mfma(A = a, B = P a, C = Sigma_11 + Xi)
 //     H f = f[1]                                        one quad broadcast of f by column
-// -- FIVE matrix instructions a step (f by row, f by column, Q, Pp, H Pp) where the general form has eight.  What this kernel
+//     f[q] = A2 u[q] + B2 u[q ^ 1]                      J0 is 2 x 2 block-diagonal: with the lane's COLUMN pair (A2, B2) = (rho cos, -+ rho sin)
+//                                                        in columns 0 / 1, (M0, M1) / (M3, M2) in columns 2 / 3 (Ekf4Anchor) the predicted mean by
+//                                                        column is one quad swap of uq, a multiply and an FMA -- f by row, which only fed the
+//                                                        matrix cores' own contraction, and ur with it are gone
+//     J0[q][r] = m1 A2 + m2 B2                           the matrix operand from the same pair: m1 = [r == q], m2 = [r == q ^ 1]
+// -- THREE matrix instructions a step (Q, Pp, H Pp) where the general form has eight; until the mean left the matrix cores there
+// were five (f = mfma(J0, ur) by row and mfma(ur, J0) by column: the same product twice, because the cores contract over a ROW-form
+// vector).  Two matrix instructions and the ur update out, two FMA pairs and a 64-bit quad swap in: -40 + 15 + 8 issue cycles a step
+// at the costs below, and f no longer waits for a matrix instruction at the head of the step's tail.  What this kernel
 // is bound by was measured in round 3's last microbenchmarks: INSTRUCTION ISSUE first, its dependent chain second.  A wavefront
 // that has its SIMD to itself issues nothing in the shadow of its own v_mfma_f64_4x4x4 (tools/ubench/mfma_valu_overlap.hip:
 // M matrix + N vector instructions take 20 M + 5 N cycles, not the maximum of the two); a v_fma_f64 / v_mul_f64 / v_add_f64
@@ -89,8 +119,18 @@ struct Ekf4State {
 // linear filter, whose step is the tail alone, takes that form and gains 4 % (kf4_mfma_trial).
 template <int E1 = 0>
 // kjd = (kj ang) x the softplus derivative: this lane's factor of the Jacobian column d f / d u2
-CGP_DEV void ekf4_mfma_finish_j(const Ekf4MfmaConst& K, double y, double J0T, double kjd, Ekf4State& x, double& S, double& innov) {
-    const double f_r = mfma4(J0T, x.ur, 0.0), f_q = mfma4(x.ur, J0T, 0.0);
+CGP_DEV void ekf4_mfma_finish_j(const Ekf4MfmaConst& K, double y, double A, double B2, double kjd, Ekf4State& x, double& S, double& innov) {
+    // E1 != 0: (A, B2) is the lane's column pair -- f by column on the vector ALU, the matrix operand J0[q][r] picked from the pair;
+    // E1 == 0: A is J0[q][r] itself (B2 unused) and f goes through the matrix cores in both layouts
+    double J0T, f_r, f_q;
+    if constexpr (E1 != 0) {
+        f_q = fma(A, x.uq, B2 * dpp_f64<kQuadSwap1>(x.uq));
+        J0T = fma(K.m1, A, K.m2 * B2);
+        f_r = 0.0;
+    } else {
+        J0T = A;
+        f_r = mfma4(J0T, x.ur, 0.0); f_q = mfma4(x.ur, J0T, 0.0);
+    }
     const double RJT = fma(kjd, dpp_f64<kQuadSwap1>(f_q), J0T);
     double Pp, PHr, PHq;
     if constexpr (E1 != 0) {
@@ -126,13 +166,17 @@ CGP_DEV void ekf4_mfma_finish_j(const Ekf4MfmaConst& K, double y, double J0T, do
     // spare the move that forms Pp H by row.  The compiler does not form it; as inline assembly it measured 2.48 against 2.40 ms.)
     x.P = fma(-(PHr * rS), PHq, Pp);                            // Pf = Pp - K (Pp H)^T
     const double g = rS * innov;
-    x.ur = fma(PHr, g, f_r);                                    // mf = mp + K innov, in both layouts
+    if constexpr (E1 == 0) x.ur = fma(PHr, g, f_r);             // mf = mp + K innov, in both layouts (H = e_1: by column only)
     x.uq = fma(PHq, g, f_q);
 }
 template <int E1 = 0>
 CGP_DEV void ekf4_mfma_finish(const Ekf4MfmaConst& K, double y, double c1, double s1, double dsp, Ekf4State& x, double& S, double& innov) {
-    const double J0T = fma(K.kcr, c1, fma(K.ksr, s1, K.kk));           // rho (kc cos + ks sin) + kk: rho rides in kcr, ksr
-    ekf4_mfma_finish_j<E1>(K, y, J0T, K.kja * dsp, x, S, innov);
+    if constexpr (E1 != 0) {
+        ekf4_mfma_finish_j<E1>(K, y, fma(K.pa, c1, K.pA0), fma(K.pb, s1, K.pB0), K.kja * dsp, x, S, innov);
+    } else {
+        const double J0T = fma(K.kcr, c1, fma(K.ksr, s1, K.kk));       // rho (kc cos + ks sin) + kk: rho rides in kcr, ksr
+        ekf4_mfma_finish_j<E1>(K, y, J0T, 0.0, K.kja * dsp, x, S, innov);
+    }
 }
 
 // The WIDE step (round 5): full-accuracy softplus and sincos WITHOUT regime branches, valid for any |u2| < 700 and |theta| < 1e5
@@ -176,20 +220,35 @@ CGP_DEV void ekf4_mfma_step_checked(const Ekf4MfmaConst& K, double y, Ekf4State&
 // lanes outside the rotation block (A = kk or 0, B = 0) the increment d is ZERO, hence sd = 0, cd = 1 and A' = A: the angle
 // scale rides in per-lane coefficients (K.angm and the polynomial of SpecRegs::init(K.angm)) that vanish there, at no cost.
 // (The verdict on |d| is taken over the wavefront, so the lanes of the rotation block speak for it.)
+//
+// H = e_1 form (set<E1 != 0>, Ekf4MfmaConst::fold_e1): the rotated pair depends on the lane's COLUMN q alone,
+//     q = 0: (rho cos, -rho sin)    q = 1: (rho cos, +rho sin)    q = 2: (M0, M1)    q = 3: (M3, M2),
+// so that f[q] = A u[q] + B u[q ^ 1] and J0[q][r] = m1 A + m2 B both come from it.  The pairs of columns 0 and 1 turn in OPPOSITE
+// directions (A' = cd A -+ sd B), which is free: the angle scale K.angm is +ang in column 0, -ang in column 1 (0 beyond, as before),
+// and with it th = +-theta, the increment d, tau and sn change sign per lane.  Everything that forms theta or d from th uses the
+// lane's K.angm (set, the `lin` terms of every regime, the coefficients of SpecRegs / SpecRegsHigh / SpecRegsMid); the verdict on
+// |d| compares magnitudes and keeps both signs apart already (d / di).
 struct Ekf4Anchor {
     double th, A, B;
+    template <int E1 = 0>
     CGP_DEV void set(const Ekf4MfmaConst& K, double sp, double c1, double s1) {      // sp = softplus(u2): theta = ang sp
         th = K.angm * sp;
-        A = fma(K.kcr, c1, fma(K.ksr, s1, K.kk));
-        B = fma(K.ksr, c1, -(K.kcr * s1));
+        if constexpr (E1 != 0) {
+            A = fma(K.pa, c1, K.pA0);
+            B = fma(K.pb, s1, K.pB0);
+        } else {
+            A = fma(K.kcr, c1, fma(K.ksr, s1, K.kk));
+            B = fma(K.ksr, c1, -(K.kcr * s1));
+        }
     }
 };
 
+template <int E1 = 0>
 CGP_DEV void ekf4_anchor(const Ekf4MfmaConst& K, double u2, Ekf4Anchor& a) {
     double sp, dsp, s1, c1;
     softplus_pair_uniform(u2, sp, dsp);
     fast_sincos_uniform(K.ang * sp, s1, c1);
-    a.set(K, sp, c1, s1);
+    a.template set<E1>(K, sp, c1, s1);
 }
 
 // Round 3 made the step five vector instructions shorter:
@@ -291,7 +350,7 @@ CGP_DEV void ekf4_mfma_step_spec1(const Ekf4MfmaConst& K, const SpecRegs& R, con
     verdict.d = verdict.d > hd ? verdict.d : hd;
     verdict.di = verdict.di > (int)hd ? verdict.di : (int)hd;
     a.th += d; a.A = A; a.B = B;
-    ekf4_mfma_finish_j<E1>(K, y, A, jfac, x, S, innov);
+    ekf4_mfma_finish_j<E1>(K, y, A, B, jfac, x, S, innov);
 }
 
 // Tried with it and dropped (all measured on the bench configuration, same box, A/B): a third, FLAT regime for chunks that start
@@ -338,11 +397,12 @@ CGP_DEV void ekf4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
     K.ks = (q == 0 && r == 1) ? -1.0 : ((q == 1 && r == 0) ? 1.0 : 0.0);
     K.kj = (r == 2 && q == 0) ? -1.0 : ((r == 2 && q == 1) ? 1.0 : 0.0);
     K.kk = (q == 2) ? (r == 2 ? K.M0 : (r == 3 ? K.M1 : 0.0)) : ((q == 3) ? (r == 2 ? K.M2 : (r == 3 ? K.M3 : 0.0)) : 0.0);
-    K.fold();
+    if constexpr (E1) K.fold_e1(r, q);
+    else K.fold();
 
     const double* __restrict__ m0p = io.m0 + trial * io.m0_stride;
     Ekf4State x;
-    x.ur = m0p[r]; x.uq = m0p[q];
+    x.ur = E1 ? 0.0 : m0p[r]; x.uq = m0p[q];                             // (H = e_1: the mean by column only)
     x.P = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, r, q);
 
     const int64_t T = io.T;
@@ -418,7 +478,7 @@ CGP_DEV void ekf4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
         // (not for a chunk that goes straight to the wide step: the anchor is a dependent chain of ~ 70 operations)
         const bool spec_allowed = spec_off == 0;
         if (!spec_allowed) anchor0 = anchor_live;
-        else if (anchor_age < 0 || anchor_age >= 4) { ekf4_anchor(K, x.u2(), anchor0); anchor_age = 0; }
+        else if (anchor_age < 0 || anchor_age >= 4) { ekf4_anchor<E1 ? 2 : 0>(K, x.u2(), anchor0); anchor_age = 0; }
         else anchor0 = anchor_live;
         // One speculative pass over the chunk in regime REG: kRegCommon, kRegHigh (the short polynomials of u2 >= 5: SpecRegsHigh),
         // kRegLow, kRegAny.
@@ -739,11 +799,12 @@ CGP_DEV void ekf4_mfma_step_checked_lane(const Ekf4MfmaConst& K, double y, Ekf4S
     fast_sincos(K.ang * sp, s1, c1);
     ekf4_mfma_finish<E1>(K, y, c1, s1, dsp, x, S, innov);
 }
+template <int E1 = 0>
 CGP_DEV void ekf4_anchor_lane(const Ekf4MfmaConst& K, double u2, Ekf4Anchor& a) {
     double sp, dsp, s1, c1;
     softplus_pair_wide(u2, sp, dsp);
     fast_sincos(K.ang * sp, s1, c1);
-    a.set(K, sp, c1, s1);
+    a.template set<E1>(K, sp, c1, s1);
 }
 
 // DENSE = false: constants pinned, 297 registers, one wave per SIMD (the dispatcher then has to spread the waves over all
@@ -775,11 +836,12 @@ CGP_DEV void ekf4_mfma_x4_trials(const FilterIO& io, const ModelArgs& ma) {
     K.ks = (q == 0 && r == 1) ? -1.0 : ((q == 1 && r == 0) ? 1.0 : 0.0);
     K.kj = (r == 2 && q == 0) ? -1.0 : ((r == 2 && q == 1) ? 1.0 : 0.0);
     K.kk = (q == 2) ? (r == 2 ? K.M0 : (r == 3 ? K.M1 : 0.0)) : ((q == 3) ? (r == 2 ? K.M2 : (r == 3 ? K.M3 : 0.0)) : 0.0);
-    K.fold();
+    if constexpr (E1) K.fold_e1(r, q);
+    else K.fold();
 
     const double* __restrict__ m0p = io.m0 + trial * io.m0_stride;
     Ekf4State x;
-    x.ur = m0p[r]; x.uq = m0p[q];
+    x.ur = E1 ? 0.0 : m0p[r]; x.uq = m0p[q];
     x.P = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, r, q);
 
     const int64_t T = io.T;
@@ -811,7 +873,7 @@ CGP_DEV void ekf4_mfma_x4_trials(const FilterIO& io, const ModelArgs& ma) {
         unsigned long long uncommon = 0;                         // the verdicts of the four trials, pooled: a wave mask
         if (checked_left == 0) {
             Ekf4Anchor anchor;
-            ekf4_anchor_lane(K, x.u2(), anchor);
+            ekf4_anchor_lane<E1 ? 1 : 0>(K, x.u2(), anchor);
             Ekf4Verdict verdict;
             auto one = [&](int slot) {
                 double S, innov;

@@ -253,13 +253,28 @@ def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=No
     return fun
 
 
+# L-BFGS-B's stopping rule where the gradient is differenced from the filter's NLL (see fit; tests/test_mle_stopping_rule.py)
+DIFFERENCE_STOP = dict(ftol=1e-13, gtol=1e-7)
+
+
 def fit(method, build, init_params, ys, Xi, dt, sgps=None, maxiter=200, exact=None, **build_kw):
     """L-BFGS-B from ``init_params`` (positive model parameters, e.g. [0.1, 0.1, 0.1, 1, 1, 7]).
-    Returns (opt_params, scipy OptimizeResult)."""
+    Returns (opt_params, scipy OptimizeResult).
+
+    With the difference form of the gradient the stopping rule is tighter than SciPy's default (ftol 2.2e-9, gtol 1e-5).  These
+    likelihoods end in a shallow valley, and under the default rule the point at which the search stops is decided by the last bits of
+    the filter's NLL, which the differences amplify: on a T = 3141 chirp record, perturbing the NLL by 2e-14 of its value (a few units in
+    the last place, what any re-ordering of the filter's arithmetic does) moved the parameters at which it stopped by up to 2.2e-3 of
+    their value, seven runs, although every NLL agreed to 1e-7.  With ftol 1e-13 and gtol 1e-7 the same seven runs end within 1.7e-4 of
+    the optimum, for 60 - 85 objective launches where the default took 45 - 55.  (The tangent kernels' searches, exact=True, keep
+    SciPy's rule.)"""
     from scipy.optimize import minimize
+    if exact is None:
+        exact = _exact_by_default(method, build, Xi, 1, build_kw)
     fun = make_objective(method, build, ys, Xi, dt, sgps, exact=exact, **build_kw)
+    stop = {} if exact else DIFFERENCE_STOP
     res = minimize(fun, M.g_inv(np.asarray(init_params, dtype=np.float64)), jac=True, method='L-BFGS-B',
-                   options=dict(maxiter=maxiter))
+                   options=dict(maxiter=maxiter, **stop))
     return M.g(res.x), res
 
 

@@ -84,18 +84,32 @@ def step_ops(k, part='all'):
         op('ur@', 'valu', 'fma(kjd_@, 1e-9, ur#)', 'kjd_@ ur#')
         op('P@', 'valu', 'P# + 0.0', 'P#')
         return O
-    if part == 'tail':      # the head's results replaced by cheap stand-ins that still depend on the previous step
+    if part in ('tail', 'tail_col'):      # the head's results replaced by cheap stand-ins that still depend on the previous step
         del O[:]
         op('y@', 'rdl', 'readlane_f64(ychunk, slot + %d)' % (k - 1), '')
-        op('J_@', 'valu', 'fma(uq#, 1e-9, K.kk)', 'uq#')
+        if part == 'tail':
+            op('J_@', 'valu', 'fma(uq#, 1e-9, K.kk)', 'uq#')
+        else:               # (the column form's head hands over a pair: one stand-in more than the row form's tail carries)
+            op('A2_@', 'valu', 'fma(uq#, 1e-9, K.pA0)', 'uq#')
+            op('B2_@', 'valu', 'fma(uq#, -1e-9, K.pB0)', 'uq#')
         op('kjd_@', 'valu', 'K.kja * 0.5', '')
         op('th@', 'valu', 'th# + 0.0', 'th#')
         op('c@', 'valu', 'c# + 0.0', 'c#')
         op('s@', 'valu', 's# + 0.0', 's#')
         op('accU@', 'int', 'accU# + 0u', 'accU#', 'unsigned')
         op('accD@', 'valu', 'accD# + 0.0', 'accD#')
-    op('fr_@', 'mfma', 'mfma4(J_@, ur#, 0.0)', 'J_@ ur#')
-    op('fq_@', 'mfma', 'mfma4(ur#, J_@, 0.0)', 'J_@ ur#')
+    col = part == 'tail_col'
+    if col:
+        # the mean by column only (cgp_mfma4.hpp, Ekf4Anchor): f[q] = A2 u[q] + B2 u[q ^ 1] on the vector ALU and the matrix operand
+        # J0[q][r] = m1 A2 + m2 B2 from the lane's column pair -- no f by row, no ur, three matrix instructions a step
+        op('usw_@', 'dpp', 'dpp_f64<kQuadSwap1>(uq#)', 'uq#')
+        op('bs_@', 'valu', 'B2_@ * usw_@', 'B2_@ usw_@')
+        op('fq_@', 'valu', 'fma(A2_@, uq#, bs_@)', 'A2_@ uq# bs_@')
+        op('jm_@', 'valu', 'K.m2 * B2_@', 'B2_@')
+        op('J_@', 'valu', 'fma(K.m1, A2_@, jm_@)', 'A2_@ jm_@')
+    else:
+        op('fr_@', 'mfma', 'mfma4(J_@, ur#, 0.0)', 'J_@ ur#')
+        op('fq_@', 'mfma', 'mfma4(ur#, J_@, 0.0)', 'J_@ ur#')
     op('fsw_@', 'dpp', 'dpp_f64<kQuadSwap1>(fq_@)', 'fq_@')
     op('RJ_@', 'valu', 'fma(kjd_@, fsw_@, J_@)', 'kjd_@ fsw_@ J_@')
     op('Q_@', 'mfma', 'mfma4(P#, RJ_@, 0.0)', 'P# RJ_@')
@@ -113,7 +127,8 @@ def step_ops(k, part='all'):
     op('g_@', 'valu', 'rS_@ * in_@', 'rS_@ in_@')
     op('Kn_@', 'valu', 'PHr_@ * -rS_@', 'PHr_@ rS_@')
     op('P@', 'valu', 'fma(Kn_@, PHq_@, Pp_@)', 'Kn_@ PHq_@ Pp_@')
-    op('ur@', 'valu', 'fma(PHr_@, g_@, fr_@)', 'PHr_@ g_@ fr_@')
+    if not col:
+        op('ur@', 'valu', 'fma(PHr_@, g_@, fr_@)', 'PHr_@ g_@ fr_@')
     op('uq@', 'valu', 'fma(PHq_@, g_@, fq_@)', 'PHq_@ g_@ fq_@')
     op('', 'lds', 'park[(slot + %d) * kParkStride] = make_double2(S_@, in_@)' % (k - 1), 'S_@ in_@', None)
     op('', 'st', 'Pfs.store_s(P@, p_off, (unsigned)(t0 + slot + %d) * 128u)' % (k - 1), 'P@', None)
@@ -185,7 +200,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=4)
     ap.add_argument('--emit', default=None)
-    ap.add_argument('--part', default='all', choices=['all', 'head', 'tail'])
+    ap.add_argument('--part', default='all', choices=['all', 'head', 'tail', 'tail_col'])
     ap.add_argument('--no-stores', action='store_true')
     ap.add_argument('--source-order', action='store_true', help='emit the operations as written (baseline of the model)')
     a = ap.parse_args()

@@ -5,7 +5,7 @@ set -e
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 cd "$ROOT"
 mkdir -p tools/ubench/ekf4_parts_gen
-for p in all head tail; do
+for p in all head tail tail_col; do
     for o in "" --source-order; do
         python tools/sched/ekf4_sched.py --part $p --no-stores $o --emit tools/ubench/ekf4_parts_gen/$p${o:+_src}.inc
     done
