@@ -189,36 +189,45 @@ static bool sigma_mfma_taken(uint32_t flags, int64_t T, const ModelArgs& ma) {
 __global__ void __launch_bounds__(64) filter_split_fixup_kernel(FilterIO io, int d, double* __restrict__ junction_err) {
     const int64_t b = blockIdx.x;
     const int lane = threadIdx.x;
-    const int n = d + d * d;
+    const SegLayout L = seg_layout(d);
     const double* __restrict__ rec = io.seg_state + b * io.segs * io.seg_stride;
     double worst = 0.0;
     for (int s = 1; s < io.segs; s++) {
-        const double* start = rec + s * io.seg_stride;                   // (m, P) after the burn-in of segment s
-        const double* end = rec + (s - 1) * io.seg_stride + n;           // (m, P) after the last step of segment s - 1
-        double dm = 0.0, rm = 0.0, dp = 0.0, rp = 0.0;
-        bool nan = false;
-        for (int i = 0; i < n; i++) {
-            const double a = start[i], r = end[i], e = fabs(a - r);
-            nan = nan || !(e == e);
-            if (i < d) { dm = fmax(dm, e); rm = fmax(rm, fabs(r)); } else { dp = fmax(dp, e); rp = fmax(rp, fabs(r)); }
-        }
-        double err = fmax(rm > 0.0 ? dm / rm : dm, rp > 0.0 ? dp / rp : dp);
-        if (nan) err = __builtin_inf();                                  // a NaN on either side of a junction: the split run is not the sequential one
-        worst = fmax(worst, err);
+        const double* start = rec + s * io.seg_stride + L.junction;      // (m, P) after the burn-in of segment s
+        const double* end = rec + (s - 1) * io.seg_stride + L.end;       // (m, P) after the last step of segment s - 1
+        // (a NaN on either side of a junction: the split run is not the sequential one)
+        worst = fmax(worst, junction_mismatch(start, start + d, end, end + d, d));
     }
     if (lane == 0) junction_err[b] = worst;
     if (!io.nll) return;
-    const int tot = 2 * n;
     if (io.flags & CGP_NLL_FINAL_ONLY) {
-        if (lane == 0) { double sum = 0.0; for (int s = 0; s < io.segs; s++) sum += rec[s * io.seg_stride + tot]; io.nll[b] = sum; }
+        if (lane == 0) { double sum = 0.0; for (int s = 0; s < io.segs; s++) sum += rec[s * io.seg_stride + L.nll]; io.nll[b] = sum; }
         return;
     }
     double offset = 0.0;
     for (int s = 1; s < io.segs; s++) {
-        offset += rec[(s - 1) * io.seg_stride + tot];
+        offset += rec[(s - 1) * io.seg_stride + L.nll];
         const int64_t t0 = (int64_t)s * io.seg_len, t1 = (t0 + io.seg_len < io.T) ? t0 + io.seg_len : io.T;
         for (int64_t t = t0 + lane; t < t1; t += 64) io.nll[b * io.T + t] += offset;
     }
+}
+
+// Fix-up pass of a time-split smoother launch (one wavefront per trial): junction_err[b] = the largest mismatch, over the junctions of trial b,
+// between the state a segment's burn-in arrived at and the row the segment before it (later in time) wrote there.  A heuristic like the filters'
+// (include/chirpgp_hip.h).
+__global__ void __launch_bounds__(64) smoother_split_fixup_kernel(SmootherIO io, double* __restrict__ junction_err) {
+    const int64_t trial = blockIdx.x;
+    if (threadIdx.x != 0) return;
+    const int64_t T = io.T;
+    double worst = 0.0;
+    for (int s = 1; s < io.bsegs; s++) {
+        const int64_t j_own = (int64_t)s * io.chunks_per_bseg;
+        if (j_own >= (T - 1 + 63) / 64) break;
+        const int64_t row = T - 1 - 64 * j_own;                          // the row both sides hold: segment s - 1 wrote it, segment s arrived at it
+        const double* __restrict__ jn = io.junction + (trial * io.bsegs + s) * SmootherIO::kJunctionDoubles;
+        worst = fmax(worst, junction_mismatch(jn, jn + 4, io.mss + (trial * T + row) * 4, io.Pss + (trial * T + row) * 16, 4));
+    }
+    junction_err[trial] = worst;
 }
 
 }  // namespace cgp
@@ -383,7 +392,7 @@ static int filter_impl(cgp_ctx* ctx, int method, const cgp_model* model, const c
         int64_t seg_len = ((T + segments - 1) / segments + 63) / 64 * 64;
         const int64_t segs = (T + seg_len - 1) / seg_len;                  // without the empty ones
         io.segs = (int)segs; io.seg_len = seg_len; io.burn_in = (burn_in + 63) / 64 * 64;
-        io.seg_stride = 2 * (model->d + model->d * model->d) + 1;
+        io.seg_stride = seg_layout(model->d).stride;
         if (segs > 1) {
             // (a set too large for the LDS stage runs one lane per trial whatever the flags say -- choose_wave -- and those kernels
             // know no segments: refuse instead of reading records nobody wrote)
@@ -602,7 +611,7 @@ static int smoother_impl(cgp_ctx* ctx, int method, const cgp_model* model, const
             const int64_t segs = (chunks + cps - 1) / cps;
             if (segs > 1) {
                 io.bsegs = (int)segs; io.chunks_per_bseg = (int)cps; io.burn_chunks = (int)((burn_in + 63) / 64);
-                io.junction = (double*)ctx_workspace(ctx, st, sizeof(double) * 20 * (size_t)B * (size_t)segs);
+                io.junction = (double*)ctx_workspace(ctx, st, sizeof(double) * SmootherIO::kJunctionDoubles * (size_t)B * (size_t)segs);
                 if (!io.junction) return fail(ctx, CGP_E_HIP, "no workspace for the junction states (allocation failed, or the buffer would grow inside a graph capture: cgp_reserve_workspace first)");
             }
         }
@@ -622,8 +631,10 @@ static int smoother_impl(cgp_ctx* ctx, int method, const cgp_model* model, const
     default: rc = CGP_E_ARG;
     }
     if (rc == CGP_OK && junction_err) {
-        if (io.bsegs > 1) rc = dispatch_smoother_split_fixup(io, junction_err, st);
-        else if (hipMemsetAsync(junction_err, 0, sizeof(double) * (size_t)B, st) != hipSuccess) rc = CGP_E_HIP;      // nothing was split: no junction, no mismatch
+        if (io.bsegs > 1) {
+            hipLaunchKernelGGL(smoother_split_fixup_kernel, dim3((unsigned)B), dim3(64), 0, st, io, junction_err);
+            rc = hip_rc(hipGetLastError());
+        } else if (hipMemsetAsync(junction_err, 0, sizeof(double) * (size_t)B, st) != hipSuccess) rc = CGP_E_HIP;      // nothing was split: no junction, no mismatch
     }
     if (rc == CGP_OK && want_sel && !sel_native) {
         SmoothSel sel;

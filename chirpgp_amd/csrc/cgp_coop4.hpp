@@ -146,6 +146,128 @@ CGP_DEV double nll_flush_wave(double S_l, double innov_l, int lane, int nsteps, 
 CGP_DEV double coop4_load_sym_entry(const double* __restrict__ p, int li, int lj) {
     return (li >= lj) ? p[li * 4 + lj] : p[lj * 4 + li];
 }
+// The lane's entry Sigma[i][j] of the transition covariance of the chirp / La Scala LCD model (models.py:302-308)
+template <class DM> CGP_DEV double lane_sigma_entry(const DM& model, int i, int j) {
+    static_assert(DM::D == 4, "q I on the chirp block, the Matern block behind it");
+    // (the model's fields are read BEFORE the choice: a choice between their addresses would keep the caller's model in scratch memory)
+    const double q = model.q, s0 = model.MS[0], s1 = model.MS[1], s2 = model.MS[2];
+    double Sig = 0.0;
+    if (i == j) Sig = (i < 2) ? q : (i == 2 ? s0 : s2);
+    else if (i + j == 5) Sig = s1;
+    return Sig;
+}
+// Whether a trial's measurement vector is the unit vector e_1, as in every chirp / La Scala builder of the reference (models.py:118)
+CGP_DEV bool h_is_e1(const double* __restrict__ Hp) { return Hp[0] == 0.0 && Hp[1] == 1.0 && Hp[2] == 0.0 && Hp[3] == 0.0; }
+
+// ---- the d = 4 matrix-core kernels (cgp_mfma4*.hpp; lane = 16 r + 4 b + q holds P[r][q], the four blocks b are replicas): what goes on
+// around their steps.  The store calls stay in the kernels: they differ on purpose.
+// Outputs of a filter.  Rows leave through buffer windows: the per-lane byte offset is a CONSTANT (block 0 stores the 16 entries of Pf,
+// lanes 0..3 the column-form mean; every other lane carries an out-of-range offset and is dropped by the hardware).  A time-split segment's
+// burn-in chunks (whole chunks: t_out is a multiple of 64) store through the EMPTY window -- a scalar choice of the buffer descriptor per
+// chunk, the lane offsets stay loop-invariant (as per-chunk offsets they cost two vector adds a step).
+struct Tile4FilterOut {
+    OobWindow wP, wm, wnull;
+    unsigned offP, offm;
+    double* __restrict__ nll;
+    bool nll_final, want_nll;
+    CGP_DEV void init(const FilterIO& io, int64_t trial, int lane) {
+        const int64_t T = io.T;
+        wP.init(io.Pfs ? io.Pfs + trial * T * 16 : nullptr, T * 128);
+        wm.init(io.mfs ? io.mfs + trial * T * 4 : nullptr, T * 32);
+        wnull.init(nullptr, 0);
+        offP = (((lane >> 2) & 3) == 0) ? 8u * (4 * (lane >> 4) + (lane & 3)) : kOobOffset;
+        offm = (lane < 4) ? 8u * lane : kOobOffset;
+        nll_final = (io.flags & CGP_NLL_FINAL_ONLY) != 0;
+        nll = (io.nll && !nll_final) ? io.nll + trial * T : nullptr;
+        want_nll = io.nll != nullptr;
+    }
+    CGP_DEV OobWindow P_window(bool burn) const { return burn ? wnull : wP; }
+    CGP_DEV OobWindow m_window(bool burn) const { return burn ? wnull : wm; }
+    // the NLL of a chunk whose steps parked (S, innovation) in park[slot]; returns the new running total
+    CGP_DEV double flush_nll(const double2* park, int lane, int nsteps, double cum, int64_t t0) const {
+        wave_lds_fence();
+        const double2 si = park[lane < nsteps ? lane : 0];
+        return nll_flush_wave(si.x, si.y, lane, nsteps, cum, nll ? nll + t0 : nullptr);
+    }
+    CGP_DEV void store_nll_total(const FilterIO& io, int64_t trial, int lane, double cum) const {
+        if (lane == 0 && io.nll && nll_final) io.nll[trial] = cum;
+    }
+};
+
+// RK4 on a lane's (m, P) (quadratures.py:34-54), same operation order as cgp_steps.hpp:rk4_m_cov; rhs(m, P, km, kP) evaluates the moment ODE.
+constexpr double kSixth = 1.0 / 6.0;       // RK4's "/ 6" (quadratures.py:53) as a multiplication: within an ulp of the division, a dozen instructions less per use
+template <class Rhs> CGP_DEV void rk4_lane(double dt, double& m, double& P, Rhs rhs) {
+    double tm = m, am = 0.0, km, tP = P, aP = 0.0, kP;
+#pragma unroll 1
+    for (int stage = 0; stage < 4; stage++) {
+        rhs(tm, tP, km, kP);
+        const double wgt = (stage == 0 || stage == 3) ? 1.0 : 2.0;
+        const double dth = (stage == 2) ? dt : 0.5 * dt;                 // (dt k) half == k (dt half): half is a power of two
+        am = fma(wgt, km, am); tm = m + dth * km;
+        aP = fma(wgt, kP, aP);
+        tP = P + dth * kP;
+    }
+    m = m + (dt * am) * kSixth;
+    P = P + (dt * aP) * kSixth;
+}
+
+// The chunks of workgroup (trial, seg) of a time-split smoother launch (SmootherIO::bsegs): [j_first, j_last] walked, [j_own, j_last] stored;
+// chunk j covers the rows T - 2 - 64 j - 63 .. T - 2 - 64 j, and the carry starts from the filtering row t_start.
+struct SmootherSpan { int64_t j_own, j_first, j_last, t_start; bool empty; };
+template <bool SPLIT> CGP_DEV SmootherSpan smoother_span(const SmootherIO& io, int seg) {
+    const int64_t n_chunks = (io.T - 1 + 63) / 64;
+    SmootherSpan sp{0, 0, n_chunks - 1, io.T - 1, false};
+    if constexpr (SPLIT) {
+        sp.j_own = (int64_t)seg * io.chunks_per_bseg;
+        sp.j_last = sp.j_own + io.chunks_per_bseg - 1 < n_chunks - 1 ? sp.j_own + io.chunks_per_bseg - 1 : n_chunks - 1;
+        sp.j_first = sp.j_own - io.burn_chunks > 0 ? sp.j_own - io.burn_chunks : 0;
+        sp.empty = sp.j_own >= n_chunks;                                 // (more segments than chunks: nothing to do)
+        sp.t_start = io.T - 1 - 64 * sp.j_first;
+    }
+    return sp;
+}
+// A continuous-discrete smoother's side of it: which (trial, segment) the workgroup is, its rows in and out, its span.  The chunks of a
+// segment's burn-in store through the empty window; at the junction the carry goes on record for the fix-up pass.
+struct Tile4SmootherIO {
+    int64_t trial; int seg;
+    const double* __restrict__ mfs; const double* __restrict__ Pfs;
+    OobWindow wP, wm, wnull;
+    unsigned offP, offm;
+    SmootherSpan sp;
+    template <bool SPLIT> CGP_DEV void decode(const SmootherIO& io) {
+        trial = SPLIT ? (int64_t)(blockIdx.x / (unsigned)io.bsegs) : (int64_t)blockIdx.x;
+        seg = SPLIT ? (int)(blockIdx.x % (unsigned)io.bsegs) : 0;
+    }
+    // false: a segment without chunks.  The segment last in time also copies row T - 1 (filters_smoothers.py:140-142, verbatim)
+    template <bool SPLIT> CGP_DEV bool init(const SmootherIO& io, int lane) {
+        const int64_t T = io.T;
+        mfs = io.mfs + trial * T * 4; Pfs = io.Pfs + trial * T * 16;
+        double* __restrict__ mss = io.mss + trial * T * 4;
+        double* __restrict__ Pss = io.Pss + trial * T * 16;
+        wP.init(Pss, T * 128);
+        wm.init(mss, T * 32);
+        wnull.init(nullptr, 0);
+        offP = (((lane >> 2) & 3) == 0) ? 8u * (4 * (lane >> 4) + (lane & 3)) : kOobOffset;
+        offm = (lane < 4) ? 8u * lane : kOobOffset;
+        sp = smoother_span<SPLIT>(io, seg);
+        if (sp.empty) return false;
+        if (sp.j_first == 0 && sp.j_own == 0) {
+            if (lane < 16) Pss[(T - 1) * 16 + lane] = Pfs[(T - 1) * 16 + lane];
+            if (lane < 4) mss[(T - 1) * 4 + lane] = mfs[(T - 1) * 4 + lane];
+        }
+        return true;
+    }
+    CGP_DEV const OobWindow& P_window(bool own) const { return own ? wP : wnull; }
+    CGP_DEV const OobWindow& m_window(bool own) const { return own ? wm : wnull; }
+    // the state a segment's burn-in arrived at (the carry in front of its first own chunk): m in column form, P one entry per lane
+    CGP_DEV void junction_store(const SmootherIO& io, int lane, double ms, double Ps) const {
+        if (seg > 0 && io.junction) {
+            double* __restrict__ jn = io.junction + (trial * io.bsegs + seg) * SmootherIO::kJunctionDoubles;
+            if (lane < 4) jn[lane] = ms;
+            if (((lane >> 2) & 3) == 0) jn[4 + 4 * (lane >> 4) + (lane & 3)] = Ps;
+        }
+    }
+};
 
 #ifndef CGP_COOP4_HELPERS_ONLY      // cgp_inst_mfma4.hip takes the helpers above and not a second copy of this kernel
 __global__ void __launch_bounds__(64) ekf4_coop_kernel(FilterIO io, ModelArgs ma) {
@@ -162,10 +284,7 @@ __global__ void __launch_bounds__(64) ekf4_coop_kernel(FilterIO io, ModelArgs ma
     Coop4Meas meas;
     meas.load(io, trial, li, lj);
 
-    // Sigma[i][j] of this lane (models.py:302-308)
-    double Sig = 0.0;
-    if (li == lj) Sig = (li < 2) ? model.q : (li == 2 ? model.MS[0] : model.MS[2]);
-    else if (li + lj == 5) Sig = model.MS[1];
+    const double Sig = lane_sigma_entry(model, li, lj);
 
     // J[j][l], l = 0..3 (row j, for Q = P J^T)
     const double ac0 = (lj == 0) ? 1.0 : 0.0, bc0 = (lj == 1) ? 1.0 : 0.0;       // J[j][0] = ac0 c + bc0 s

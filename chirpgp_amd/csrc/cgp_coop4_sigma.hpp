@@ -168,13 +168,7 @@ __global__ void __launch_bounds__(64) sgp4_coop_kernel(FilterIO io, ModelArgs ma
     sg.stage(dyn_lds(), lane, 64, 4);
     Coop4Meas meas;
     meas.load(io, trial, li, lj);
-    double Sig = 0.0;                                   // the lane's entry of the transition covariance
-    {
-        Sym<4> Sg;
-        CGP_UNROLL for (int k = 0; k < Sym<4>::N; k++) Sg.a[k] = 0.0;
-        model.add_sigma(Sg, 1.0);
-        CGP_UNROLL for (int i = 0; i < 4; i++) CGP_UNROLL for (int j = 0; j < 4; j++) if (li == i && lj == j) Sig = Sg(i, j);
-    }
+    const double Sig = lane_sigma_entry(model, li, lj);  // the lane's entry of the transition covariance
     const int s2_idx = 5 + Sym<4>::idx(li, lj);         // this lane's entry among the totals: [wsum, mean x4, second moment x10]
 
     const double* __restrict__ m0p = io.m0 + trial * io.m0_stride;

@@ -200,7 +200,7 @@ __global__ void __launch_bounds__(64) sgp8_coop_kernel(FilterIO io, ModelArgs ma
     const unsigned offm = mean_lane ? (unsigned)i * 8u : kOobOffset;
 
     double cum = 0.0;
-    constexpr int kN = D + D * D;                                        // doubles of one (m, P) record of FilterIO::seg_state
+    using Seg = SegRecord<D>;
     for (int64_t t0 = span.t_begin; t0 < span.t_end; t0 += 64) {
         double ychunk = (t0 + lane < span.t_end) ? ys[t0 + lane] : 0.0;
         asm volatile("" : "+v"(ychunk));
@@ -208,8 +208,8 @@ __global__ void __launch_bounds__(64) sgp8_coop_kernel(FilterIO io, ModelArgs ma
         const bool burn = t0 < span.t_out;                               // burn-in chunks of a segment write nothing
         const OobWindow wPc = burn ? wnull : wP, wmc = burn ? wnull : wm;   // an empty window drops the stores; the lane offsets stay loop-invariant
         if (span.state && span.seg > 0 && t0 == span.t_out) {            // the junction: the state the burn-in arrived at
-            if (entry) span.state[D + i * D + j] = P;
-            if (mean_lane) span.state[i] = mrow;
+            Seg::put_cov(span.state, Seg::kJunction, entry, i, j, P);
+            Seg::put_mean(span.state, Seg::kJunction, mean_lane, i, mrow);
         }
         ybuf[lane] = ychunk;
         wave_lds_fence();
@@ -307,9 +307,9 @@ __global__ void __launch_bounds__(64) sgp8_coop_kernel(FilterIO io, ModelArgs ma
         }
     }
     if (span.state) {                                                    // the segment's last state and its NLL total, for the fix-up pass
-        if (entry) span.state[kN + D + i * D + j] = P;
-        if (mean_lane) span.state[kN + i] = mrow;
-        if (lane == 0) span.state[2 * kN] = cum;
+        Seg::put_cov(span.state, Seg::kEnd, entry, i, j, P);
+        Seg::put_mean(span.state, Seg::kEnd, mean_lane, i, mrow);
+        Seg::put_nll(span.state, lane, cum);
     } else if (lane == 0 && io.nll && nll_final) io.nll[trial] = cum;
 }
 

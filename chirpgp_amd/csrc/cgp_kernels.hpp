@@ -35,8 +35,8 @@ struct FilterIO {
     unsigned long long* __restrict__ counters = nullptr;      // cgp_debug_set(CGP_DBG_COUNT_REGIMES): regime counters of the context, or NULL
     // Time-split filters with burn-in (cgp_filter_time_split; round 4): `segs` wavefronts per trial.  Wavefront (b, s) filters the
     // steps [s seg_len - burn_in, (s + 1) seg_len) of trial b from (m0, P0), writes rows from s seg_len on, and leaves in
-    // seg_state[(b segs + s) seg_stride ..] its state at the junction (after its last burn-in step), its state after its last step
-    // and its NLL total: (m, P) | (m, P) | nll.  seg_len and burn_in are multiples of 64 (the kernels' chunk).  segs <= 1: off.
+    // seg_state[(b segs + s) seg_stride ..] its record (SegRecord below): its state at the junction (after its last burn-in step), its
+    // state after its last step and its NLL total.  seg_len and burn_in are multiples of 64 (the kernels' chunk).  segs <= 1: off.
     int segs = 1;
     int64_t seg_len = 0, burn_in = 0;
     double* __restrict__ seg_state = nullptr;
@@ -70,6 +70,32 @@ __device__ __forceinline__ FilterSpan filter_span(const FilterIO& io, int64_t v)
     int64_t t_end = t_out + io.seg_len;
     if (t_end > io.T) t_end = io.T;
     return {b, t_begin, t_out, t_end, s, io.seg_state ? io.seg_state + (b * io.segs + s) * io.seg_stride : nullptr};
+}
+// The record of one segment, FilterSpan::state: (m, P) at the junction | (m, P) after the last step | NLL total, each (m, P) as d doubles of
+// mean and d x d of covariance, row-major.  THE definition: the kernels write through SegRecord<D>, the fix-up pass and the host (whose d
+// is a run-time value) read seg_layout(d).
+struct SegLayout { int junction, end, nll, stride; };
+constexpr SegLayout seg_layout(int d) { return {0, d + d * d, 2 * (d + d * d), 2 * (d + d * d) + 1}; }
+template <int D> struct SegRecord {
+    static constexpr int kJunction = seg_layout(D).junction, kEnd = seg_layout(D).end, kNll = seg_layout(D).nll, kStride = seg_layout(D).stride;
+    // `at` = kJunction or kEnd.  One entry per owning lane: m[i] (the column-form mean of the d = 4 tile layout: lanes 0..3, i = lane) ...
+    CGP_DEV static void put_mean(double* rec, int at, bool owner, int i, double mi) { if (owner) rec[at + i] = mi; }
+    // ... or the replicated mean of d = 4, from lane 0
+    CGP_DEV static void put_mean(double* rec, int at, int lane, double u0, double u1, double u2, double u3) {
+        if (lane == 0) { rec[at] = u0; rec[at + 1] = u1; rec[at + 2] = u2; rec[at + 3] = u3; }
+    }
+    CGP_DEV static void put_cov(double* rec, int at, bool owner, int i, int j, double Pij) { if (owner) rec[at + D + i * D + j] = Pij; }
+    CGP_DEV static void put_nll(double* rec, int lane, double total) { if (lane == 0) rec[kNll] = total; }
+};
+// Junction mismatch of the time-split fix-up passes: max |a - ref| / max |ref| over the d entries of the mean and, apart, the d x d of the
+// covariance; inf if a NaN sits on either side.
+CGP_DEV double junction_mismatch(const double* am, const double* aP, const double* rm, const double* rP, int d) {
+    double dm = 0.0, sm = 0.0, dp = 0.0, sp = 0.0;
+    bool nan = false;
+    for (int i = 0; i < d; i++) { const double e = fabs(am[i] - rm[i]); nan = nan || !(e == e); dm = fmax(dm, e); sm = fmax(sm, fabs(rm[i])); }
+    for (int i = 0; i < d * d; i++) { const double e = fabs(aP[i] - rP[i]); nan = nan || !(e == e); dp = fmax(dp, e); sp = fmax(sp, fabs(rP[i])); }
+    const double err = fmax(sm > 0.0 ? dm / sm : dm, sp > 0.0 ? dp / sp : dp);
+    return nan ? __builtin_inf() : err;
 }
 
 // Selected outputs of a smoother launch (cgp_smoother_select; SURVEY 8f-2: the step right behind the smoother in every driver of the
@@ -189,8 +215,9 @@ struct SmootherIO {
     // Time-split with burn-in of the continuous-discrete smoothers (cgp_smoother_time_split; round 6): their backward ODE is not affine in the
     // carry, so a segment cannot be composed exactly -- but the recursion FORGETS its terminal condition like the filters forget their initial
     // one: segment s (0 = the last in time) starts `burn_chunks` 64-step chunks LATER than its piece from the filtering row there, writes
-    // nothing until its piece begins, and leaves its state at the junction in junction[(trial * bsegs + s) * 20] (m 4 | P 16) for the
-    // fix-up pass to compare with the row the segment before it wrote.  bsegs <= 1: off.
+    // nothing until its piece begins, and leaves its state at the junction in junction[(trial * bsegs + s) * kJunctionDoubles] (m 4 | P 16)
+    // for the fix-up pass to compare with the row the segment before it wrote.  bsegs <= 1: off.
+    static constexpr int kJunctionDoubles = 4 + 16;
     int bsegs = 1, chunks_per_bseg = 0, burn_chunks = 0;
     double* __restrict__ junction = nullptr;
     SmoothSel sel;                // cgp_smoother_select: selected outputs (mss / Pss may then be NULL); comp < 0: off
@@ -686,7 +713,6 @@ int dispatch_filter_mfma4(const FilterIO&, const ModelArgs&, hipStream_t);
 int dispatch_filter_mfma4_sgp(const FilterIO&, const ModelArgs&, hipStream_t);
 int dispatch_filter_mfma4_cdsgp(const FilterIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_mfma4_cdsgp(const SmootherIO&, const ModelArgs&, hipStream_t);
-int dispatch_smoother_split_fixup(const SmootherIO&, double* junction_err, hipStream_t);
 int dispatch_filter_mfma4_cdekf(const FilterIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_mfma4_cdeks(const SmootherIO&, const ModelArgs&, hipStream_t);
 // the matrix-core EKF addresses a trial's outputs through 2 GiB buffer windows (cgp_mfma4.hpp)

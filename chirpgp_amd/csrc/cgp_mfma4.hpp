@@ -70,6 +70,24 @@ struct Ekf4MfmaConst {
         m1 = r == q ? 1.0 : 0.0;
         m2 = r == (q ^ 1) ? 1.0 : 0.0;
     }
+    // lane (r, q)'s constants of one trial.  J = [c -s jv0 0; s c jv1 0; 0 0 M0 M1; 0 0 M2 M3], this lane holds J[q][r]
+    template <bool E1> CGP_DEV void load(const HarmonicLCD<1>& model, const FilterIO& io, int64_t trial, int r, int q) {
+        M0 = model.M[0]; M1 = model.M[1]; M2 = model.M[2]; M3 = model.M[3];
+        rho = model.rho;
+        ang = (model.dt * kTwoPi) * model.fs;
+        Hr = io.H[trial * io.H_stride + r];
+        Xi = io.Xi[trial * io.Xi_stride];
+        Sig = lane_sigma_entry(model, r, q);
+        const double mq = model.q;
+        SigHq = (q == 1) ? mq : 0.0;                                    // Sigma[1][q]: the chirp block of Sigma is q I
+        c0 = mq + Xi;
+        kc = ((q == 0 && r == 0) || (q == 1 && r == 1)) ? 1.0 : 0.0;
+        ks = (q == 0 && r == 1) ? -1.0 : ((q == 1 && r == 0) ? 1.0 : 0.0);
+        kj = (r == 2 && q == 0) ? -1.0 : ((r == 2 && q == 1) ? 1.0 : 0.0);
+        kk = (q == 2) ? (r == 2 ? M0 : (r == 3 ? M1 : 0.0)) : ((q == 3) ? (r == 2 ? M2 : (r == 3 ? M3 : 0.0)) : 0.0);
+        if constexpr (E1) fold_e1(r, q);
+        else fold();
+    }
 };
 // The mean is distributed like the covariance: ur = u[r] (row layout) and uq = u[q] (column layout) at lane (r, q); the
 // frequency state u[2] every lane needs is one quad broadcast of uq.  The H = e_1 form carries uq ALONE (ur is neither read
@@ -79,6 +97,11 @@ struct Ekf4State {
     double P, ur, uq;                                                          // (ur: read and updated by the general form only; 0 in the H = e_1 form)
     CGP_DEV double u2() const { return dpp_f64<kQuadBcast2>(uq); }
     CGP_DEV double u2_replicated() const { return row_bcast_f64<2>(uq); }      // one trial per wavefront: the four blocks are replicas
+    template <bool E1> CGP_DEV void load(const FilterIO& io, int64_t trial, int r, int q) {
+        const double* __restrict__ m0p = io.m0 + trial * io.m0_stride;
+        ur = E1 ? 0.0 : m0p[r]; uq = m0p[q];                                   // (H = e_1: the mean by column only)
+        P = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, r, q);
+    }
 };
 
 // Everything of a step after the rotation (c1, s1) = (cos, sin)(theta) and the softplus derivative dsp are known -- the
@@ -375,50 +398,26 @@ CGP_DEV void ekf4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
     const int lane = threadIdx.x;
     const int r = lane >> 4, q = lane & 3;
     const FilterSpan span = filter_span(io, blockIdx.x);                 // (a time-split launch: one SEGMENT of the trial's record)
+    using Seg = SegRecord<4>;
     const int64_t trial = span.trial;
 
     HarmonicLCD<1> model;
     model.setup(ma.params + trial * ma.param_stride, ma.dt, ma.model_id);
     Ekf4MfmaConst K;
-    K.M0 = model.M[0]; K.M1 = model.M[1]; K.M2 = model.M[2]; K.M3 = model.M[3];
-    K.rho = model.rho;
-    K.ang = (model.dt * kTwoPi) * model.fs;
-    const double* __restrict__ Hp = io.H + trial * io.H_stride;
-    K.Hr = Hp[r];
-    K.Xi = io.Xi[trial * io.Xi_stride];
-    // Sigma[r][q] (models.py:302-308)
-    K.Sig = 0.0;
-    if (r == q) K.Sig = (r < 2) ? model.q : (r == 2 ? model.MS[0] : model.MS[2]);
-    else if (r + q == 5) K.Sig = model.MS[1];
-    // J = [c -s jv0 0; s c jv1 0; 0 0 M0 M1; 0 0 M2 M3], this lane holds J[q][r]
-    K.SigHq = (q == 1) ? model.q : 0.0;                                 // Sigma[1][q]: the chirp block of Sigma is q I
-    K.c0 = model.q + K.Xi;
-    K.kc = ((q == 0 && r == 0) || (q == 1 && r == 1)) ? 1.0 : 0.0;
-    K.ks = (q == 0 && r == 1) ? -1.0 : ((q == 1 && r == 0) ? 1.0 : 0.0);
-    K.kj = (r == 2 && q == 0) ? -1.0 : ((r == 2 && q == 1) ? 1.0 : 0.0);
-    K.kk = (q == 2) ? (r == 2 ? K.M0 : (r == 3 ? K.M1 : 0.0)) : ((q == 3) ? (r == 2 ? K.M2 : (r == 3 ? K.M3 : 0.0)) : 0.0);
-    if constexpr (E1) K.fold_e1(r, q);
-    else K.fold();
-
-    const double* __restrict__ m0p = io.m0 + trial * io.m0_stride;
+    K.template load<E1>(model, io, trial, r, q);
     Ekf4State x;
-    x.ur = E1 ? 0.0 : m0p[r]; x.uq = m0p[q];                             // (H = e_1: the mean by column only)
-    x.P = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, r, q);
-
-    const int64_t T = io.T;
+    x.template load<E1>(io, trial, r, q);
     const double* __restrict__ ys = io.record(trial);
-    OobWindow mfs, Pfs, mnull, Pnull;
-    mfs.init(io.mfs ? io.mfs + trial * T * 4 : nullptr, T * 32);
-    Pfs.init(io.Pfs ? io.Pfs + trial * T * 16 : nullptr, T * 128);
-    mnull.init(nullptr, 0); Pnull.init(nullptr, 0);                      // the burn-in chunks of a time-split segment store through these
+    // (the step's row offset t * 128 / t * 32 rides in the stores' scalar offset -- no vector instruction per step for addressing)
+    Tile4FilterOut out;
+    out.init(io, trial, lane);
+    const unsigned p_off = out.offP, m_off = out.offm;
+    // The NLL side of Tile4FilterOut is spelled out in this kernel, here and behind the chunk: this unit is built without machine LICM and
+    // is issue-bound, and with the struct's members in their place the chunk loop compiled to other code (scalar spills 54 -> 53, 73
+    // instructions more); in this form its loops are the parent's instruction for instruction
     const bool nll_final = (io.flags & CGP_NLL_FINAL_ONLY) != 0;
-    double* __restrict__ nll = (io.nll && !nll_final) ? io.nll + trial * T : nullptr;
+    double* __restrict__ nll = (io.nll && !nll_final) ? io.nll + trial * io.T : nullptr;
     const bool want_nll = io.nll != nullptr;
-    // Output rows leave through buffer windows: the per-lane byte offset is a CONSTANT (block 0 stores the 16 entries of Pf,
-    // lanes 0..3 the mean; every other lane carries an out-of-range offset and is dropped by the hardware), the step's
-    // row offset t * 128 / t * 32 rides in the instruction's scalar offset -- no vector instruction per step for addressing.
-    const unsigned p_off = (((lane >> 2) & 3) == 0) ? 8u * (4 * r + q) : kOobOffset;
-    const unsigned m_off = (lane < 4) ? 8u * lane : kOobOffset;
 
     SpecRegs R;
     R.init(K.angm);
@@ -446,14 +445,12 @@ CGP_DEV void ekf4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
     double ynext = (span.t_begin + lane < Te) ? ys[span.t_begin + lane] : 0.0;
     for (int64_t t0 = span.t_begin; t0 < Te; t0 += 64) {
         wave_lds_fence();                                                   // the previous chunk's NLL flush has read its slots
-        // a segment's burn-in chunks write nothing (whole chunks: t_out is a multiple of 64); at the junction the state goes on record
-        // (which WINDOW a chunk stores through is a scalar choice of the buffer descriptor: an empty window drops every store, and the
-        // per-lane offsets stay the loop-invariant constants they were -- as per-chunk offsets they cost two vector adds a step)
+        // a segment's burn-in chunks write nothing (Tile4FilterOut); at the junction the state goes on record
         const bool burn = t0 < span.t_out;
-        const OobWindow Pw = burn ? Pnull : Pfs, mw = burn ? mnull : mfs;
+        const OobWindow Pw = out.P_window(burn), mw = out.m_window(burn);
         if (span.state && span.seg > 0 && t0 == span.t_out) {
-            if (lane < 4) span.state[lane] = x.uq;
-            if (((lane >> 2) & 3) == 0) span.state[4 + 4 * r + q] = x.P;
+            Seg::put_mean(span.state, Seg::kJunction, lane < 4, lane, x.uq);
+            Seg::put_cov(span.state, Seg::kJunction, ((lane >> 2) & 3) == 0, r, q, x.P);
         }
         // The empty asm consumes the loaded register here, so the compiler's s_waitcnt for it sits in this outer loop and
         // not in front of every step's v_readlane
@@ -638,9 +635,9 @@ CGP_DEV void ekf4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
         }
     }
     if (span.state) {                                                       // the segment's last state and its NLL total, for the fix-up pass
-        if (lane < 4) span.state[20 + lane] = x.uq;
-        if (((lane >> 2) & 3) == 0) span.state[24 + 4 * r + q] = x.P;
-        if (lane == 0) span.state[40] = cum;
+        Seg::put_mean(span.state, Seg::kEnd, lane < 4, lane, x.uq);
+        Seg::put_cov(span.state, Seg::kEnd, ((lane >> 2) & 3) == 0, r, q, x.P);
+        Seg::put_nll(span.state, lane, cum);
     } else if (lane == 0 && io.nll && nll_final) io.nll[trial] = cum;
     if (io.counters && lane == 0) {
         atomicAdd(io.counters + 0, (unsigned long long)n_high); atomicAdd(io.counters + 1, (unsigned long long)n_common);
@@ -675,14 +672,8 @@ CGP_DEV void kf4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
 
     const int64_t T = io.T;
     const double* __restrict__ ys = io.record(trial);
-    OobWindow mfs, Pfs;
-    mfs.init(io.mfs ? io.mfs + trial * T * 4 : nullptr, T * 32);
-    Pfs.init(io.Pfs ? io.Pfs + trial * T * 16 : nullptr, T * 128);
-    const bool nll_final = (io.flags & CGP_NLL_FINAL_ONLY) != 0;
-    double* __restrict__ nll = (io.nll && !nll_final) ? io.nll + trial * T : nullptr;
-    const bool want_nll = io.nll != nullptr;
-    const unsigned p_off = (((lane >> 2) & 3) == 0) ? 8u * (4 * r + q) : kOobOffset;
-    const unsigned m_off = (lane < 4) ? 8u * lane : kOobOffset;
+    Tile4FilterOut out;
+    out.init(io, trial, lane);
 
     __shared__ double2 park[64];
     __shared__ double ybuf[64 + 8];
@@ -718,8 +709,8 @@ CGP_DEV void kf4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
             uq = fma(PHq, g, f_q);
             park[slot] = make_double2(S, innov);
             const unsigned t = (unsigned)(t0 + slot);
-            Pfs.store_s(P, p_off, t * 128u);
-            mfs.store_s(uq, m_off, t * 32u);
+            out.wP.store_s(P, out.offP, t * 128u);
+            out.wm.store_s(uq, out.offm, t * 32u);
         };
         ybuf[lane] = ychunk;                                                     // measurements through LDS, as in ekf4_mfma_trial
         wave_lds_fence();
@@ -731,20 +722,14 @@ CGP_DEV void kf4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
             ya = na; yb = nb;
         }
         for (; slot < nsteps; slot++) one(slot, readlane_f64(ychunk, slot));
-        if (want_nll) {
-            wave_lds_fence();
-            const double2 si = park[lane < nsteps ? lane : 0];
-            cum = nll_flush_wave(si.x, si.y, lane, nsteps, cum, nll ? nll + t0 : nullptr);
-        }
+        if (out.want_nll) cum = out.flush_nll(park, lane, nsteps, cum, t0);
     }
-    if (lane == 0 && io.nll && nll_final) io.nll[trial] = cum;
+    out.store_nll_total(io, trial, lane, cum);
 }
 __global__ void __launch_bounds__(64) kf4_mfma_kernel(FilterIO io, ModelArgs ma) {
     const int64_t trial = blockIdx.x;
     if (trial >= io.B) return;
-    const double* __restrict__ Hp = io.H + trial * io.H_stride;
-    const bool e1 = Hp[0] == 0.0 && Hp[1] == 1.0 && Hp[2] == 0.0 && Hp[3] == 0.0;
-    if (e1) kf4_mfma_trial<true>(io, ma);
+    if (h_is_e1(io.H + trial * io.H_stride)) kf4_mfma_trial<true>(io, ma);
     else kf4_mfma_trial<false>(io, ma);
 }
 inline int launch_kf4_mfma(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
@@ -759,9 +744,7 @@ __global__ void __launch_bounds__(64) ekf4_mfma_kernel(FilterIO io, ModelArgs ma
     if (trial >= io.B) return;
     // the measurement vector of every chirp / La Scala builder is e_1 (models.py:118): the short-chain form of the update;
     // any other H (the API takes one per trial) runs the general form -- a wave-uniform choice
-    const double* __restrict__ Hp = io.H + trial * io.H_stride;
-    const bool e1 = Hp[0] == 0.0 && Hp[1] == 1.0 && Hp[2] == 0.0 && Hp[3] == 0.0;
-    if (e1) ekf4_mfma_trial<true>(io, ma);
+    if (h_is_e1(io.H + trial * io.H_stride)) ekf4_mfma_trial<true>(io, ma);
     else ekf4_mfma_trial<false>(io, ma);
 }
 
@@ -821,28 +804,9 @@ CGP_DEV void ekf4_mfma_x4_trials(const FilterIO& io, const ModelArgs& ma) {
     HarmonicLCD<1> model;
     model.setup(ma.params + trial * ma.param_stride, ma.dt, ma.model_id);
     Ekf4MfmaConst K;
-    K.M0 = model.M[0]; K.M1 = model.M[1]; K.M2 = model.M[2]; K.M3 = model.M[3];
-    K.rho = model.rho;
-    K.ang = (model.dt * kTwoPi) * model.fs;
-    const double* __restrict__ Hp = io.H + trial * io.H_stride;
-    K.Hr = Hp[r];
-    K.Xi = io.Xi[trial * io.Xi_stride];
-    K.Sig = 0.0;
-    if (r == q) K.Sig = (r < 2) ? model.q : (r == 2 ? model.MS[0] : model.MS[2]);
-    else if (r + q == 5) K.Sig = model.MS[1];
-    K.SigHq = (q == 1) ? model.q : 0.0;                                 // Sigma[1][q]: the chirp block of Sigma is q I
-    K.c0 = model.q + K.Xi;
-    K.kc = ((q == 0 && r == 0) || (q == 1 && r == 1)) ? 1.0 : 0.0;
-    K.ks = (q == 0 && r == 1) ? -1.0 : ((q == 1 && r == 0) ? 1.0 : 0.0);
-    K.kj = (r == 2 && q == 0) ? -1.0 : ((r == 2 && q == 1) ? 1.0 : 0.0);
-    K.kk = (q == 2) ? (r == 2 ? K.M0 : (r == 3 ? K.M1 : 0.0)) : ((q == 3) ? (r == 2 ? K.M2 : (r == 3 ? K.M3 : 0.0)) : 0.0);
-    if constexpr (E1) K.fold_e1(r, q);
-    else K.fold();
-
-    const double* __restrict__ m0p = io.m0 + trial * io.m0_stride;
+    K.template load<E1>(model, io, trial, r, q);
     Ekf4State x;
-    x.ur = E1 ? 0.0 : m0p[r]; x.uq = m0p[q];
-    x.P = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, r, q);
+    x.template load<E1>(io, trial, r, q);
 
     const int64_t T = io.T;
     // output windows over the wave's consecutive trials: a block past the batch lies beyond the window and is dropped
@@ -924,8 +888,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, DENS
     // the H = e_1 form of the update when all four trials of the wave have it (a wave-uniform choice)
     const int bq = (threadIdx.x >> 2) & 3;
     const int ntr0 = (io.B - first < 4) ? (int)(io.B - first) : 4;
-    const double* __restrict__ Hp = io.H + (first + (bq < ntr0 ? bq : ntr0 - 1)) * io.H_stride;
-    const bool e1 = Hp[0] == 0.0 && Hp[1] == 1.0 && Hp[2] == 0.0 && Hp[3] == 0.0;
+    const bool e1 = h_is_e1(io.H + (first + (bq < ntr0 ? bq : ntr0 - 1)) * io.H_stride);
     if (__builtin_amdgcn_ballot_w64(!e1) == 0) ekf4_mfma_x4_trials<DENSE, true>(io, ma);
     else ekf4_mfma_x4_trials<DENSE, false>(io, ma);
 }

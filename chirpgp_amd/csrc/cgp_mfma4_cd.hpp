@@ -25,9 +25,6 @@
 
 namespace cgp {
 
-// RK4's "/ 6" (quadratures.py:53) as a multiplication: within an ulp of the division, a dozen instructions less per use.
-constexpr double kSixth = 1.0 / 6.0;
-
 // Per-lane constants of the moment ODE in the matrix-core layout.
 struct Cd4LaneCoef {
     bool odd;                          // q & 1: the pass whose softplus this lane evaluates
@@ -132,6 +129,7 @@ __global__ void __launch_bounds__(64) cdsgp4_mfma_kernel(FilterIO io, ModelArgs 
     const int lane = threadIdx.x;
     const int r = lane >> 4, b = (lane >> 2) & 3, q = lane & 3;
     const FilterSpan span = filter_span<SPLIT>(io, blockIdx.x);          // (a time-split launch: one SEGMENT of the trial's record)
+    using Seg = SegRecord<4>;
     const int64_t trial = span.trial;
     if (trial >= io.B) return;
 
@@ -153,17 +151,12 @@ __global__ void __launch_bounds__(64) cdsgp4_mfma_kernel(FilterIO io, ModelArgs 
 
     double u = io.m0[trial * io.m0_stride + q];                          // the mean in column form
     double P = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, r, q);
-    const int64_t T = io.T;
     const double* __restrict__ ys = io.record(trial);
-    OobWindow wP, wm, wnull;
-    wnull.init(nullptr, 0);                                              // (the burn-in chunks of a time-split segment store through it)
-    wP.init(io.Pfs ? io.Pfs + trial * T * 16 : nullptr, T * 128);
-    wm.init(io.mfs ? io.mfs + trial * T * 4 : nullptr, T * 32);
-    const unsigned offP = (b == 0) ? (unsigned)(4 * r + q) * 8u : kOobOffset;      // block 0 stores the 16 entries: one 128-B row
-    const unsigned offm = (lane < 4) ? (unsigned)lane * 8u : kOobOffset;           // lanes 0..3 store the mean
-    const bool nll_final = (io.flags & CGP_NLL_FINAL_ONLY) != 0;
-    double* __restrict__ nll = (io.nll && !nll_final) ? io.nll + trial * T : nullptr;
-    const bool want_nll = io.nll != nullptr;
+    Tile4FilterOut out;
+    out.init(io, trial, lane);
+    // (the struct's own offsets, formed before this kernel's lane range is known, cost its <false, true> form a register: 229 -> 230)
+    const unsigned offP = (b == 0) ? (unsigned)(4 * r + q) * 8u : kOobOffset;
+    const unsigned offm = (lane < 4) ? (unsigned)lane * 8u : kOobOffset;
 
     double cum = 0.0;
     for (int64_t t0 = span.t_begin; t0 < span.t_end; t0 += 64) {
@@ -171,27 +164,16 @@ __global__ void __launch_bounds__(64) cdsgp4_mfma_kernel(FilterIO io, ModelArgs 
         asm volatile("" : "+v"(ychunk));
         const int nsteps = (span.t_end - t0 < 64) ? (int)(span.t_end - t0) : 64;
         const bool burn = t0 < span.t_out;                               // burn-in chunks of a segment write nothing
-        const OobWindow wPc = burn ? wnull : wP, wmc = burn ? wnull : wm;   // an empty window drops the stores; the lane offsets stay loop-invariant
+        const OobWindow wPc = out.P_window(burn), wmc = out.m_window(burn);
         if (span.state && span.seg > 0 && t0 == span.t_out) {            // the junction: the state the burn-in arrived at
-            if (lane < 4) span.state[lane] = u;
-            if (b == 0) span.state[4 + 4 * r + q] = P;
+            Seg::put_mean(span.state, Seg::kJunction, lane < 4, lane, u);
+            Seg::put_cov(span.state, Seg::kJunction, b == 0, r, q, P);
         }
         for (int slot = 0; slot < nsteps; slot++) {
             const unsigned t = (unsigned)(t0 + slot);
             const double y = readlane_f64(ychunk, slot);
-            // ---- RK4 on (m, P) (quadratures.py:34-54), same operation order as cgp_steps.hpp:rk4_m_cov
-            double tm = u, am = 0.0, km, tP = P, aP = 0.0, kP;
-#pragma unroll 1
-            for (int stage = 0; stage < 4; stage++) {
-                cd4_mfma_rhs<TWO>(model, R, K, grp, tm, tP, km, kP);
-                const double wgt = (stage == 0 || stage == 3) ? 1.0 : 2.0;
-                const double dth = (stage == 2) ? dt : 0.5 * dt;                 // (dt k) half == k (dt half): half is a power of two
-                am = fma(wgt, km, am); tm = u + dth * km;
-                aP = fma(wgt, kP, aP);
-                tP = P + dth * kP;
-            }
-            const double f = u + (dt * am) * kSixth;
-            const double Pp = P + (dt * aP) * kSixth;
+            double f = u, Pp = P;
+            rk4_lane(dt, f, Pp, [&](double tm, double tP, double& km, double& kP) { cd4_mfma_rhs<TWO>(model, R, K, grp, tm, tP, km, kP); });
             // ---- update
             double S, innov;
             mfma4_update_col(Pp, f, Hk, Hq, Xi, y, P, u, S, innov);
@@ -199,48 +181,22 @@ __global__ void __launch_bounds__(64) cdsgp4_mfma_kernel(FilterIO io, ModelArgs 
             wPc.store(P, t * 128u + offP);
             wmc.store(u, t * 32u + offm);
         }
-        if (want_nll && !burn) {
-            wave_lds_fence();
-            const double2 si = park[lane < nsteps ? lane : 0];
-            cum = nll_flush_wave(si.x, si.y, lane, nsteps, cum, nll ? nll + t0 : nullptr);
+        if (out.want_nll && !burn) {
+            cum = out.flush_nll(park, lane, nsteps, cum, t0);
             wave_lds_fence();
         }
     }
     if (span.state) {                                                    // the segment's last state and its NLL total, for the fix-up pass
-        if (lane < 4) span.state[20 + lane] = u;
-        if (b == 0) span.state[24 + 4 * r + q] = P;
-        if (lane == 0) span.state[40] = cum;
-    } else if (lane == 0 && io.nll && nll_final) io.nll[trial] = cum;
+        Seg::put_mean(span.state, Seg::kEnd, lane < 4, lane, u);
+        Seg::put_cov(span.state, Seg::kEnd, b == 0, r, q, P);
+        Seg::put_nll(span.state, lane, cum);
+    } else out.store_nll_total(io, trial, lane, cum);
 }
 
 // ------------------------------------------------------------------------------------------------ cd_sgp_smoother, d = 4
 // Backward RK4 with  dm = _m + G^T (m - mf),  dP = _P + G^T P + P G - 2 gamma,  G = Pf^{-1} gamma  (filters_smoothers.py:615-621).
 // G is constant over the four stages and computed a chunk of 64 steps at a time, lane-parallel (cgp_coop4_sigma.hpp:
 // coop4_chunk_gains); the walk reads it back from LDS one entry per lane, and mf in column form.
-// The chunks of workgroup (trial, seg) of a time-split smoother launch (SmootherIO::bsegs): [j_first, j_last] walked, [j_own, j_last] stored;
-// chunk j covers the rows T - 2 - 64 j - 63 .. T - 2 - 64 j, and the carry starts from the filtering row t_start.
-struct SmootherSpan { int64_t j_own, j_first, j_last, t_start; bool empty; };
-template <bool SPLIT> CGP_DEV SmootherSpan smoother_span(const SmootherIO& io, int seg) {
-    const int64_t n_chunks = (io.T - 1 + 63) / 64;
-    SmootherSpan sp{0, 0, n_chunks - 1, io.T - 1, false};
-    if constexpr (SPLIT) {
-        sp.j_own = (int64_t)seg * io.chunks_per_bseg;
-        sp.j_last = sp.j_own + io.chunks_per_bseg - 1 < n_chunks - 1 ? sp.j_own + io.chunks_per_bseg - 1 : n_chunks - 1;
-        sp.j_first = sp.j_own - io.burn_chunks > 0 ? sp.j_own - io.burn_chunks : 0;
-        sp.empty = sp.j_own >= n_chunks;                                 // (more segments than chunks: nothing to do)
-        sp.t_start = io.T - 1 - 64 * sp.j_first;
-    }
-    return sp;
-}
-// the state a segment's burn-in arrived at (the carry in front of its first own chunk): m in column form, P one entry per lane
-CGP_DEV void smoother_junction_store(const SmootherIO& io, int64_t trial, int seg, int r, int b, int q, double ms, double Ps) {
-    if (seg > 0 && io.junction) {
-        double* __restrict__ jn = io.junction + (trial * io.bsegs + seg) * 20;
-        if (r == 0 && b == 0) jn[q] = ms;
-        if (b == 0) jn[4 + 4 * r + q] = Ps;
-    }
-}
-
 // SPLIT (round 6; cgp_smoother_time_split): one wavefront per (trial, segment) -- see SmootherIO::bsegs.  Chunk j covers the rows
 // T - 2 - 64 j - 63 .. T - 2 - 64 j; segment s owns the chunks [s cps, (s + 1) cps) and starts burn_chunks chunks earlier in its walk
 // (later in time) from the FILTERING row there; the burn-in chunks store through a zero-byte window.
@@ -250,8 +206,9 @@ __global__ void __launch_bounds__(64) cdsgps4_mfma_kernel(SmootherIO io, ModelAr
     __shared__ __attribute__((aligned(16))) double gbuf[64 * kGainPitch];
     const int lane = threadIdx.x;
     const int r = lane >> 4, b = (lane >> 2) & 3, q = lane & 3;
-    const int64_t trial = SPLIT ? (int64_t)(blockIdx.x / (unsigned)io.bsegs) : (int64_t)blockIdx.x;
-    const int seg = SPLIT ? (int)(blockIdx.x % (unsigned)io.bsegs) : 0;
+    Tile4SmootherIO sio;
+    sio.template decode<SPLIT>(io);
+    const int64_t trial = sio.trial;
     if (trial >= io.B) return;
 
     SM model;
@@ -269,33 +226,20 @@ __global__ void __launch_bounds__(64) cdsgps4_mfma_kernel(SmootherIO io, ModelAr
     R.init();
     const double dt = -ma.dt;
 
+    if (!sio.template init<SPLIT>(io, lane)) return;
     const int64_t T = io.T;
-    const double* __restrict__ mfs = io.mfs + trial * T * 4;
-    const double* __restrict__ Pfs = io.Pfs + trial * T * 16;
-    double* __restrict__ mss = io.mss + trial * T * 4;
-    double* __restrict__ Pss = io.Pss + trial * T * 16;
-    OobWindow wP, wm, wPnull, wmnull;
-    wP.init(Pss, T * 128);
-    wm.init(mss, T * 32);
-    wPnull.init(nullptr, 0); wmnull.init(nullptr, 0);                    // the burn-in chunks of a segment store through these
-    const unsigned offP = (b == 0) ? (unsigned)(4 * r + q) * 8u : kOobOffset;
-    const unsigned offm = (lane < 4) ? (unsigned)lane * 8u : kOobOffset;
-
-    const SmootherSpan sp = smoother_span<SPLIT>(io, seg);
-    if (sp.empty) return;
+    const double* __restrict__ mfs = sio.mfs;
+    const double* __restrict__ Pfs = sio.Pfs;
+    const SmootherSpan sp = sio.sp;
     double ms = mfs[sp.t_start * 4 + q];                                 // the mean in column form
     double Ps = coop4_load_sym_entry(Pfs + sp.t_start * 16, r, q);
-    if (sp.j_first == 0 && sp.j_own == 0) {
-        if (lane < 16) Pss[(T - 1) * 16 + lane] = Pfs[(T - 1) * 16 + lane];      // filters_smoothers.py:140-142, verbatim copy
-        if (lane < 4) mss[(T - 1) * 4 + lane] = mfs[(T - 1) * 4 + lane];
-    }
 
     for (int64_t j = sp.j_first; j <= sp.j_last; j++) {
         const int64_t t_hi = T - 2 - 64 * j;
         const bool own = j >= sp.j_own;
-        if constexpr (SPLIT) { if (j == sp.j_own) smoother_junction_store(io, trial, seg, r, b, q, ms, Ps); }
-        const OobWindow& oP = own ? wP : wPnull;
-        const OobWindow& om = own ? wm : wmnull;
+        if constexpr (SPLIT) { if (j == sp.j_own) sio.junction_store(io, lane, ms, Ps); }
+        const OobWindow& oP = sio.P_window(own);
+        const OobWindow& om = sio.m_window(own);
         const int nsteps = t_hi + 1 < 64 ? (int)(t_hi + 1) : 64;
         coop4_chunk_gains(gbuf, lane, nsteps, t_hi, mfs, Pfs, gamma);
         for (int slot = 0; slot < nsteps; slot++) {
@@ -303,55 +247,18 @@ __global__ void __launch_bounds__(64) cdsgps4_mfma_kernel(SmootherIO io, ModelAr
             const double* gl = gbuf + slot * kGainPitch;
             const double Gd = gl[r * 4 + q];                             // G[r][q]: A operand G[k][r'], B operand G[k][q']
             const double mf = gl[16 + q];
-
-            double tm = ms, am = 0.0, km, tP = Ps, aP = 0.0, kP;
-#pragma unroll 1
-            for (int stage = 0; stage < 4; stage++) {
+            rk4_lane(dt, ms, Ps, [&](double tm, double tP, double& km, double& kP) {
                 cd4_mfma_rhs<TWO>(model, R, K, grp, tm, tP, km, kP);    // (_m, _P), _P includes + gamma
                 const double drow = mfma4x4(tm - mf, K.ident, 0.0);     // m - mf from column to row form: [r][q] <- [q][r]
                 km = mfma4x4(drow, Gd, km);                             // _m + G^T (m - mf): sum_k (m - mf)[k] G[k][q]
                 const double sym = mfma4x4(Gd, tP, mfma4x4(tP, Gd, 0.0));                           // G^T P + P G (P symmetric)
                 kP = (kP + sym) - 2.0 * K.gam;
-                const double wgt = (stage == 0 || stage == 3) ? 1.0 : 2.0;
-                const double dth = (stage == 2) ? dt : 0.5 * dt;                 // (dt k) half == k (dt half): half is a power of two
-                am = fma(wgt, km, am); tm = ms + dth * km;
-                aP = fma(wgt, kP, aP);
-                tP = Ps + dth * kP;
-            }
-            ms = ms + (dt * am) * kSixth;
-            Ps = Ps + (dt * aP) * kSixth;
-            oP.store(Ps, t * 128u + offP);
-            om.store(ms, t * 32u + offm);
+            });
+            oP.store(Ps, t * 128u + sio.offP);
+            om.store(ms, t * 32u + sio.offm);
         }
         wave_lds_fence();
     }
-}
-
-// Fix-up pass of a time-split smoother launch (one wavefront per trial): junction_err[b] = the largest relative mismatch, over the junctions of
-// trial b, between the state a segment's burn-in arrived at and the row the segment before it (later in time) wrote there -- max |difference| /
-// max |reference| over the mean and, separately, the covariance; inf if a NaN sits at a junction.  A heuristic like the filters' (include/chirpgp_hip.h).
-template <int UNIT = 0>      // (a template: the header is included by more than one translation unit)
-__global__ void __launch_bounds__(64) smoother_split_fixup_kernel(SmootherIO io, double* __restrict__ junction_err) {
-    const int64_t trial = blockIdx.x;
-    if (threadIdx.x != 0) return;
-    const int64_t T = io.T;
-    double worst = 0.0;
-    for (int s = 1; s < io.bsegs; s++) {
-        const int64_t j_own = (int64_t)s * io.chunks_per_bseg;
-        if (j_own >= (T - 1 + 63) / 64) break;
-        const int64_t row = T - 1 - 64 * j_own;                          // the row both sides hold: segment s - 1 wrote it, segment s arrived at it
-        const double* __restrict__ jn = io.junction + (trial * io.bsegs + s) * 20;
-        const double* __restrict__ mr = io.mss + (trial * T + row) * 4;
-        const double* __restrict__ Pr = io.Pss + (trial * T + row) * 16;
-        double dm = 0.0, rm = 0.0, dp = 0.0, rp = 0.0;
-        bool nan = false;
-        for (int i = 0; i < 4; i++) { const double e = fabs(jn[i] - mr[i]); nan = nan || !(e == e); dm = fmax(dm, e); rm = fmax(rm, fabs(mr[i])); }
-        for (int i = 0; i < 16; i++) { const double e = fabs(jn[4 + i] - Pr[i]); nan = nan || !(e == e); dp = fmax(dp, e); rp = fmax(rp, fabs(Pr[i])); }
-        double err = fmax(rm > 0.0 ? dm / rm : dm, rp > 0.0 ? dp / rp : dp);
-        if (nan) err = __builtin_inf();
-        worst = fmax(worst, err);
-    }
-    junction_err[trial] = worst;
 }
 
 // ------------------------------------------------------------------------------------------------ cd_ekf / cd_eks, d = 4
@@ -384,7 +291,7 @@ CGP_DEV void cd4_ekf_eval(const SoftplusRegs& R, const Cd4LaneCoef& K, const Cd4
 __global__ void __launch_bounds__(64) cdekf4_mfma_kernel(FilterIO io, ModelArgs ma) {
     __shared__ double2 park[64];                                         // (S, innovation) of the chunk's steps, for the NLL
     const int lane = threadIdx.x;
-    const int r = lane >> 4, b = (lane >> 2) & 3, q = lane & 3;
+    const int r = lane >> 4, q = lane & 3;
     const int64_t trial = blockIdx.x;
     if (trial >= io.B) return;
 
@@ -406,14 +313,8 @@ __global__ void __launch_bounds__(64) cdekf4_mfma_kernel(FilterIO io, ModelArgs 
     double P = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, r, q);
     const int64_t T = io.T;
     const double* __restrict__ ys = io.record(trial);
-    OobWindow wP, wm;
-    wP.init(io.Pfs ? io.Pfs + trial * T * 16 : nullptr, T * 128);
-    wm.init(io.mfs ? io.mfs + trial * T * 4 : nullptr, T * 32);
-    const unsigned offP = (b == 0) ? (unsigned)(4 * r + q) * 8u : kOobOffset;
-    const unsigned offm = (lane < 4) ? (unsigned)lane * 8u : kOobOffset;
-    const bool nll_final = (io.flags & CGP_NLL_FINAL_ONLY) != 0;
-    double* __restrict__ nll = (io.nll && !nll_final) ? io.nll + trial * T : nullptr;
-    const bool want_nll = io.nll != nullptr;
+    Tile4FilterOut out;
+    out.init(io, trial, lane);
 
     double cum = 0.0;
     for (int64_t t0 = 0; t0 < T; t0 += 64) {
@@ -423,44 +324,35 @@ __global__ void __launch_bounds__(64) cdekf4_mfma_kernel(FilterIO io, ModelArgs 
         for (int slot = 0; slot < nsteps; slot++) {
             const unsigned t = (unsigned)(t0 + slot);
             const double y = readlane_f64(ychunk, slot);
-            double tm = u, am = 0.0, tP = P, aP = 0.0;
-#pragma unroll 1
-            for (int stage = 0; stage < 4; stage++) {
-                double km, JT;
+            double f = u, Pp = P;
+            rk4_lane(dt, f, Pp, [&](double tm, double tP, double& km, double& kP) {
+                double JT;
                 cd4_ekf_eval(R, K, Jc, fs, tm, km, JT);
                 const double JP = mfma4x4(JT, tP, 0.0);                  // sum_k J[r][k] P[k][q]
-                const double kP = mfma4x4(JP, K.ident, JP + K.gam);      // (J P)^T + J P + gamma
-                const double wgt = (stage == 0 || stage == 3) ? 1.0 : 2.0;
-                const double dth = (stage == 2) ? dt : 0.5 * dt;                 // (dt k) half == k (dt half): half is a power of two
-                am = fma(wgt, km, am); tm = u + dth * km;
-                aP = fma(wgt, kP, aP);
-                tP = P + dth * kP;
-            }
-            const double f = u + (dt * am) * kSixth;
-            const double Pp = P + (dt * aP) * kSixth;
+                kP = mfma4x4(JP, K.ident, JP + K.gam);                   // (J P)^T + J P + gamma
+            });
             double S, innov;
             mfma4_update_col(Pp, f, Hk, Hq, Xi, y, P, u, S, innov);
             park[slot] = make_double2(S, innov);
-            wP.store(P, t * 128u + offP);
-            wm.store(u, t * 32u + offm);
+            out.wP.store(P, t * 128u + out.offP);
+            out.wm.store(u, t * 32u + out.offm);
         }
-        if (want_nll) {
-            wave_lds_fence();
-            const double2 si = park[lane < nsteps ? lane : 0];
-            cum = nll_flush_wave(si.x, si.y, lane, nsteps, cum, nll ? nll + t0 : nullptr);
+        if (out.want_nll) {
+            cum = out.flush_nll(park, lane, nsteps, cum, t0);
             wave_lds_fence();
         }
     }
-    if (lane == 0 && io.nll && nll_final) io.nll[trial] = cum;
+    out.store_nll_total(io, trial, lane, cum);
 }
 
 template <bool SPLIT = false>      // SPLIT: cgp_smoother_time_split, as cdsgps4_mfma_kernel
 __global__ void __launch_bounds__(64) cdeks4_mfma_kernel(SmootherIO io, ModelArgs ma) {
     __shared__ __attribute__((aligned(16))) double gbuf[64 * kGainPitch];
     const int lane = threadIdx.x;
-    const int r = lane >> 4, b = (lane >> 2) & 3, q = lane & 3;
-    const int64_t trial = SPLIT ? (int64_t)(blockIdx.x / (unsigned)io.bsegs) : (int64_t)blockIdx.x;
-    const int seg = SPLIT ? (int)(blockIdx.x % (unsigned)io.bsegs) : 0;
+    const int r = lane >> 4, q = lane & 3;
+    Tile4SmootherIO sio;
+    sio.template decode<SPLIT>(io);
+    const int64_t trial = sio.trial;
     if (trial >= io.B) return;
 
     HarmonicSDE<1> model;
@@ -476,33 +368,20 @@ __global__ void __launch_bounds__(64) cdeks4_mfma_kernel(SmootherIO io, ModelArg
     load_sym<4>(ma.gamma + trial * ma.gamma_stride, gamma);
     const double dt = -ma.dt, fs = model.fs;
 
+    if (!sio.template init<SPLIT>(io, lane)) return;
     const int64_t T = io.T;
-    const double* __restrict__ mfs = io.mfs + trial * T * 4;
-    const double* __restrict__ Pfs = io.Pfs + trial * T * 16;
-    double* __restrict__ mss = io.mss + trial * T * 4;
-    double* __restrict__ Pss = io.Pss + trial * T * 16;
-    OobWindow wP, wm, wPnull, wmnull;
-    wP.init(Pss, T * 128);
-    wm.init(mss, T * 32);
-    wPnull.init(nullptr, 0); wmnull.init(nullptr, 0);                    // the burn-in chunks of a segment store through these
-    const unsigned offP = (b == 0) ? (unsigned)(4 * r + q) * 8u : kOobOffset;
-    const unsigned offm = (lane < 4) ? (unsigned)lane * 8u : kOobOffset;
-
-    const SmootherSpan sp = smoother_span<SPLIT>(io, seg);
-    if (sp.empty) return;
+    const double* __restrict__ mfs = sio.mfs;
+    const double* __restrict__ Pfs = sio.Pfs;
+    const SmootherSpan sp = sio.sp;
     double ms = mfs[sp.t_start * 4 + q];
     double Ps = coop4_load_sym_entry(Pfs + sp.t_start * 16, r, q);
-    if (sp.j_first == 0 && sp.j_own == 0) {
-        if (lane < 16) Pss[(T - 1) * 16 + lane] = Pfs[(T - 1) * 16 + lane];      // filters_smoothers.py:140-142, verbatim copy
-        if (lane < 4) mss[(T - 1) * 4 + lane] = mfs[(T - 1) * 4 + lane];
-    }
 
     for (int64_t j = sp.j_first; j <= sp.j_last; j++) {
         const int64_t t_hi = T - 2 - 64 * j;
         const bool own = j >= sp.j_own;
-        if constexpr (SPLIT) { if (j == sp.j_own) smoother_junction_store(io, trial, seg, r, b, q, ms, Ps); }
-        const OobWindow& oP = own ? wP : wPnull;
-        const OobWindow& om = own ? wm : wmnull;
+        if constexpr (SPLIT) { if (j == sp.j_own) sio.junction_store(io, lane, ms, Ps); }
+        const OobWindow& oP = sio.P_window(own);
+        const OobWindow& om = sio.m_window(own);
         const int nsteps = t_hi + 1 < 64 ? (int)(t_hi + 1) : 64;
         coop4_chunk_gains(gbuf, lane, nsteps, t_hi, mfs, Pfs, gamma);  // Pf^{-1} gamma of the chunk's steps, one step per lane
         for (int slot = 0; slot < nsteps; slot++) {
@@ -510,25 +389,16 @@ __global__ void __launch_bounds__(64) cdeks4_mfma_kernel(SmootherIO io, ModelArg
             const double* gl = gbuf + slot * kGainPitch;
             const double Gd = gl[r * 4 + q];                             // G[r][q] = (G^T)[q][r]: the lane's entry of A^T - J^T
             const double mf = gl[16 + q];
-            double tm = ms, am = 0.0, tP = Ps, aP = 0.0;
-#pragma unroll 1
-            for (int stage = 0; stage < 4; stage++) {
-                double km, JT;
+            rk4_lane(dt, ms, Ps, [&](double tm, double tP, double& km, double& kP) {
+                double JT;
                 cd4_ekf_eval(R, K, Jc, fs, tm, km, JT);
                 const double drow = mfma4x4(tm - mf, K.ident, 0.0);     // m - mf from column to row form
                 km = mfma4x4(drow, Gd, km);                             // a(m) + G^T (m - mf)
                 const double AP = mfma4x4(JT + Gd, tP, 0.0);            // sum_k A[r][k] P[k][q], A = J + G^T
-                const double kP = mfma4x4(AP, K.ident, AP - K.gam);     // (A P)^T + A P - gamma
-                const double wgt = (stage == 0 || stage == 3) ? 1.0 : 2.0;
-                const double dth = (stage == 2) ? dt : 0.5 * dt;                 // (dt k) half == k (dt half): half is a power of two
-                am = fma(wgt, km, am); tm = ms + dth * km;
-                aP = fma(wgt, kP, aP);
-                tP = Ps + dth * kP;
-            }
-            ms = ms + (dt * am) * kSixth;
-            Ps = Ps + (dt * aP) * kSixth;
-            oP.store(Ps, t * 128u + offP);
-            om.store(ms, t * 32u + offm);
+                kP = mfma4x4(AP, K.ident, AP - K.gam);                  // (A P)^T + A P - gamma
+            });
+            oP.store(Ps, t * 128u + sio.offP);
+            om.store(ms, t * 32u + sio.offm);
         }
         wave_lds_fence();
     }
@@ -578,11 +448,6 @@ inline int launch_cdsgps4_mfma(const SmootherIO& io, const ModelArgs& ma, hipStr
     }
     if (ma.sg.n_groups > 16) hipLaunchKernelGGL((cdsgps4_mfma_kernel<SM, true>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
     else hipLaunchKernelGGL((cdsgps4_mfma_kernel<SM, false>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
-    return hip_rc(hipGetLastError());
-}
-// (the fix-up pass of a split launch: instantiated with the kernel, called by cgp_smoother_time_split)
-inline int launch_smoother_split_fixup(const SmootherIO& io, double* junction_err, hipStream_t stream) {
-    hipLaunchKernelGGL((smoother_split_fixup_kernel<0>), dim3((unsigned)io.B), dim3(64), 0, stream, io, junction_err);
     return hip_rc(hipGetLastError());
 }
 

@@ -121,6 +121,7 @@ CGP_DEV void sgp4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
     const int r = lane >> 4, b = (lane >> 2) & 3, q = lane & 3;
     // (time-split launches, cgp_filter_time_split: this wavefront is one SEGMENT of its trial's record -- cgp_kernels.hpp: FilterSpan)
     const FilterSpan span = filter_span<SPLIT>(io, blockIdx.x);
+    using Seg = SegRecord<4>;
     const int64_t trial = span.trial;
 
     DM model;
@@ -140,13 +141,7 @@ CGP_DEV void sgp4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
     const double Hk = Hp[r];                                             // H[k] for the lane's k = lane >> 4, as A or B operand
     const double Xi = io.Xi[trial * io.Xi_stride];
     const double M0 = model.M[0], M1 = model.M[1], M2 = model.M[2], M3 = model.M[3];
-    double Sig = 0.0;                                                    // Sigma[r][q] (models.py:302-308)
-    {
-        Sym<4> Sg;
-        CGP_UNROLL for (int k = 0; k < Sym<4>::N; k++) Sg.a[k] = 0.0;
-        model.add_sigma(Sg, 1.0);
-        CGP_UNROLL for (int i = 0; i < 4; i++) CGP_UNROLL for (int j = 0; j < 4; j++) if (r == i && q == j) Sig = Sg(i, j);
-    }
+    const double Sig = lane_sigma_entry(model, r, q);
     const double K1 = (r >= 2 && q >= 2) ? model.M[2 * (r - 2) + 1] * model.M[2 * (q - 2) + 1] : 0.0;
     Sgp4LaneCoef K;
     K.init(q, model.M);
@@ -159,19 +154,13 @@ CGP_DEV void sgp4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
     const double* __restrict__ m0p = io.m0 + trial * io.m0_stride;
     const double* __restrict__ P0p = io.P0 + trial * io.P0_stride;
     double u0 = m0p[0], u1 = m0p[1], u2 = m0p[2], u3 = m0p[3];
-    double P = (r >= q) ? P0p[r * 4 + q] : P0p[q * 4 + r];
+    double P = coop4_load_sym_entry(P0p, r, q);
 
-    const int64_t T = io.T;
     const double* __restrict__ ys = io.record(trial);
-    OobWindow wP, wm, wnull;
-    wnull.init(nullptr, 0);                                              // (the burn-in chunks of a time-split segment store through it)
-    wP.init(io.Pfs ? io.Pfs + trial * T * 16 : nullptr, T * 128);
-    wm.init(io.mfs ? io.mfs + trial * T * 4 : nullptr, T * 32);
-    const unsigned offP = (b == 0) ? (unsigned)(4 * r + q) * 8u : kOobOffset;      // block 0 stores the 16 entries: one 128-B row
-    const unsigned offm = (lane == 0) ? 0u : kOobOffset;                           // lane 0 stores the mean: two 16-byte stores
-    const bool nll_final = (io.flags & CGP_NLL_FINAL_ONLY) != 0;
-    double* __restrict__ nll = (io.nll && !nll_final) ? io.nll + trial * T : nullptr;
-    const bool want_nll = io.nll != nullptr;
+    Tile4FilterOut out;
+    out.init(io, trial, lane);
+    const unsigned offP = out.offP;
+    const unsigned offm = (lane == 0) ? 0u : kOobOffset;                 // the mean is replicated here: lane 0 stores it, two 16-byte stores
 
     double cum = 0.0;
     for (int64_t t0 = span.t_begin; t0 < span.t_end; t0 += 64) {
@@ -180,10 +169,10 @@ CGP_DEV void sgp4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
         const int nsteps = (span.t_end - t0 < 64) ? (int)(span.t_end - t0) : 64;
         // a segment's burn-in chunks (whole chunks: t_out is a multiple of 64) write nothing: their rows belong to the segment before
         const bool burn = t0 < span.t_out;
-        const OobWindow wPc = burn ? wnull : wP, wmc = burn ? wnull : wm;   // an empty window drops the stores; the lane offsets stay loop-invariant
+        const OobWindow wPc = out.P_window(burn), wmc = out.m_window(burn);
         if (span.state && span.seg > 0 && t0 == span.t_out) {          // the junction: the state the burn-in arrived at
-            if (lane == 0) { span.state[0] = u0; span.state[1] = u1; span.state[2] = u2; span.state[3] = u3; }
-            if (b == 0) span.state[4 + 4 * r + q] = P;
+            Seg::put_mean(span.state, Seg::kJunction, lane, u0, u1, u2, u3);
+            Seg::put_cov(span.state, Seg::kJunction, b == 0, r, q, P);
         }
         // the chunk's measurements go through LDS: one broadcast ds_read_b64 per step, issued a step ahead, where a v_readlane
         // pair costs 24 issue cycles (tools/ubench/issue_costs.hip)
@@ -250,25 +239,22 @@ CGP_DEV void sgp4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
             wmc.store2(u0, u1, t * 32u + offm);
             wmc.store2(u2, u3, t * 32u + 16u + offm);
         }
-        if (want_nll && !burn) {
-            wave_lds_fence();
-            const double2 si = park[lane < nsteps ? lane : 0];
-            cum = nll_flush_wave(si.x, si.y, lane, nsteps, cum, nll ? nll + t0 : nullptr);
+        if (out.want_nll && !burn) {
+            cum = out.flush_nll(park, lane, nsteps, cum, t0);
             wave_lds_fence();
         }
     }
     if (span.state) {                                                   // the segment's last state and its NLL total, for the fix-up pass
-        if (lane == 0) { span.state[20] = u0; span.state[21] = u1; span.state[22] = u2; span.state[23] = u3; span.state[40] = cum; }
-        if (b == 0) span.state[24 + 4 * r + q] = P;
-    } else if (lane == 0 && io.nll && nll_final) io.nll[trial] = cum;
+        Seg::put_mean(span.state, Seg::kEnd, lane, u0, u1, u2, u3);
+        Seg::put_cov(span.state, Seg::kEnd, b == 0, r, q, P);
+        Seg::put_nll(span.state, lane, cum);
+    } else out.store_nll_total(io, trial, lane, cum);
 }
 template <class DM, bool TWO, bool SPLIT>
 __global__ void __launch_bounds__(64) sgp4_mfma_kernel(FilterIO io, ModelArgs ma) {
     const int64_t trial = filter_span<SPLIT>(io, blockIdx.x).trial;
     if (trial >= io.B) return;
-    const double* __restrict__ Hp = io.H + trial * io.H_stride;
-    const bool e1 = Hp[0] == 0.0 && Hp[1] == 1.0 && Hp[2] == 0.0 && Hp[3] == 0.0;      // a wave-uniform choice
-    if (e1) sgp4_mfma_trial<DM, TWO, true, SPLIT>(io, ma);
+    if (h_is_e1(io.H + trial * io.H_stride)) sgp4_mfma_trial<DM, TWO, true, SPLIT>(io, ma);
     else sgp4_mfma_trial<DM, TWO, false, SPLIT>(io, ma);
 }
 

@@ -180,6 +180,38 @@ def test_the_other_kernels_that_know_segments(method):
     assert _rel(last, seq_last) <= 5 * err + 1e-12
 
 
+@pytest.mark.parametrize('T,segments,burn_in', [(130, 2, 64), (65, 5, 64)])
+@pytest.mark.parametrize('method', ['ekf', 'lascala_ekf', 'ekf_general_H', 'sgp_filter', 'cd_sgp_filter'])
+def test_short_records_split_through_every_d4_segment_record(method, T, segments, burn_in):
+    """The d = 4 kernels that write a segment record (csrc/cgp_kernels.hpp: SegRecord), at the smallest shapes that use all of it: two
+    chunks and a ragged tail of 2 steps, and more segments asked for than there are chunks.  A wrong offset into the record reads
+    the workspace's NaN fill: the junction mismatch is then not finite."""
+    from chirpgp_amd import filters_smoothers as fs, _engine
+    B = 3
+    c = cs.lascala_case(T=T, seed=96) if method == 'lascala_ekf' else cs.chirp_case(T=T, seed=97)
+    ys = _noisy(c, B, T)
+    H = np.array([0.2, 1.0, 0.0, 0.1]) if method == 'ekf_general_H' else c.H
+    if method == 'sgp_filter':
+        run = lambda **kw: fs.sgp_filter(c.disc, c.sgps, H, c.Xi, c.m0, c.P0, c.dt, ys, **kw)
+    elif method == 'cd_sgp_filter':
+        run = lambda **kw: fs.cd_sgp_filter(c.drift, c.disp(None), c.sgps, H, c.Xi, c.m0, c.P0, c.dt, ys, **kw)
+    else:
+        run = lambda **kw: fs.ekf(c.disc, H, c.Xi, c.m0, c.P0, c.dt, ys, **kw)
+    seq = run()
+    got = run(time_split=(segments, burn_in))
+    errs = _engine.last_junction_error.cpu().numpy()
+    print(method, T, segments, burn_in, 'junction mismatch', errs, [f'{_rel(g, s_):.1e}' for g, s_ in zip(got, seq)])
+    assert errs.shape == (B,) and np.isfinite(errs).all()
+    err = float(errs.max())
+    seg_len = -(-(-(-T // segments)) // 64) * 64
+    for g, s_, n in zip(got, seq, ('mfs', 'Pfs', 'nll')):
+        assert _rel(g, s_) <= 5 * err + 1e-14, (n, _rel(g, s_), err)
+        assert np.array_equal(g[:, :seg_len], s_[:, :seg_len]), n                      # segment 0 is the sequential filter
+    # the total of an NLL-only launch: the same segment totals, summed in another order (at most five additions of O(1) numbers)
+    last = np.asarray(run(time_split=(segments, burn_in), nll_final_only=True, want=(False, False, True))[2]).reshape(B)
+    assert (np.abs(last - got[2][:, -1]) <= 1e-12 * np.abs(got[2][:, -1])).all(), (last, got[2][:, -1])
+
+
 # ------------------------------------------------------------------------------------------------ the smoother's counterpart (round 6)
 def _cd_filtered(c, B, T, seed):
     """Filtering rows of B noisy copies of the case's record from the C port (the smoothers are compared on identical inputs)."""
