@@ -57,7 +57,7 @@ class CgpSmoothOut(C.Structure):
 EXPORTS = ('cgp_version', 'cgp_create', 'cgp_destroy', 'cgp_last_error', 'cgp_filter', 'cgp_smoother',
            'cgp_gaussian_expectation', 'cgp_debug_math', 'cgp_simulate', 'cgp_add_noise', 'cgp_debug_philox',
            'cgp_debug_set', 'cgp_debug_counters', 'cgp_gaussian_expectation_fn', 'cgp_filter_time_split', 'cgp_squared_error_sums',
-           'cgp_reserve_workspace', 'cgp_release_workspace', 'cgp_source_hash', 'cgp_smoother_select', 'cgp_ekf_nll_grad', 'cgp_sgp_nll_grad', 'cgp_model_from_source', 'cgp_custom_model_destroy',
+           'cgp_reserve_workspace', 'cgp_release_workspace', 'cgp_source_hash', 'cgp_smoother_select', 'cgp_ekf_nll_grad', 'cgp_sgp_nll_grad', 'cgp_ekf_nll_fisher', 'cgp_sgp_nll_fisher', 'cgp_model_from_source', 'cgp_custom_model_destroy',
            'cgp_filter_custom', 'cgp_smoother_custom', 'cgp_smoother_time_split')
 
 _lib = None
@@ -106,6 +106,12 @@ def load_library():
         lib.cgp_sgp_nll_grad.restype = C.c_int
         lib.cgp_sgp_nll_grad.argtypes = [_vp, C.POINTER(CgpModel), C.POINTER(CgpSigma), C.POINTER(CgpInit), C.c_double, _vp, C.c_int64, C.c_int64,
                                          _vp, C.c_int64, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_uint32, _vp]
+        lib.cgp_ekf_nll_fisher.restype = C.c_int
+        lib.cgp_ekf_nll_fisher.argtypes = [_vp, C.POINTER(CgpModel), C.POINTER(CgpInit), C.c_double, _vp, C.c_int64, C.c_int64, _vp,
+                                           C.c_int64, C.c_int64, _vp, C.c_int32, _vp, _vp, _vp, C.c_uint32, _vp]
+        lib.cgp_sgp_nll_fisher.restype = C.c_int
+        lib.cgp_sgp_nll_fisher.argtypes = [_vp, C.POINTER(CgpModel), C.POINTER(CgpSigma), C.POINTER(CgpInit), C.c_double, _vp, C.c_int64, C.c_int64,
+                                           _vp, C.c_int64, C.c_int64, _vp, C.c_int32, _vp, _vp, _vp, C.c_uint32, _vp]
         lib.cgp_model_from_source.restype = C.c_int
         lib.cgp_model_from_source.argtypes = [_vp, C.c_int, C.c_int32, C.c_char_p, C.c_char_p, C.POINTER(_vp)]
         lib.cgp_custom_model_destroy.restype = None
@@ -563,6 +569,7 @@ def run_smoother_custom(spec, gamma, dt, mfs, Pfs, flags=0, sgps=None):
 
 
 DIR_DOUBLES = 24        # include/chirpgp_hip.h: CGP_DIR_DOUBLES
+FISHER_MAX_DIR = 16     # include/chirpgp_hip.h: CGP_FISHER_MAX_DIR
 
 
 def run_ekf_nll_grad(spec, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None):
@@ -576,6 +583,18 @@ def run_sgp_nll_grad(spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=
     -- forward tangents through the scan, one launch; arguments and results as run_ekf_nll_grad.  The kernel sums over the points
     literally, so the set goes over ungrouped."""
     return _run_nll_grad('cgp_sgp_nll_grad', spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
+
+
+def run_ekf_nll_fisher(spec, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None):
+    """cgp_ekf_nll_fisher: run_ekf_nll_grad's results and the Fisher information of the EKF's Gaussian innovations model along `dirs`
+    (B, n_dir <= 16, 24), sum_t (d nu_i d nu_j / S + d S_i d S_j / (2 S^2)) -- one launch.  Returns (nll (B,), grad (B, n_dir),
+    fisher (B, n_dir, n_dir)) as device tensors."""
+    return _run_nll_grad('cgp_ekf_nll_fisher', spec, None, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
+
+
+def run_sgp_nll_fisher(spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None):
+    """cgp_sgp_nll_fisher: the same for the sigma-point filter, any d = 4 SigmaPoints `sgps`; arguments and results as run_ekf_nll_fisher."""
+    return _run_nll_grad('cgp_sgp_nll_fisher', spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
 
 
 def _run_nll_grad(entry, spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index):
@@ -608,18 +627,22 @@ def _run_nll_grad(entry, spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_rec
         dirs_d = dev(dirs_h, ys_d.device.index)
         opts = dict(dtype=torch.float64, device=ys_d.device)
         nll, grad = torch.empty((B,), **opts), torch.empty((B, n_dir), **opts)
+        outs = [nll, grad]
+        if entry.endswith('_fisher'):
+            outs.append(torch.empty((B, n_dir, n_dir), **opts))
+        out_ptrs = [_ptr(o) for o in outs]
         lib = load_library()
-        if entry == 'cgp_sgp_nll_grad':
+        if entry in ('cgp_sgp_nll_grad', 'cgp_sgp_nll_fisher'):
             sig = _sigma_struct(sgps, d, keep, None)
             if sig is None:
-                raise ValueError('cgp_sgp_nll_grad needs a sigma-point set')
-            rc = _timed('filter', lambda: lib.cgp_sgp_nll_grad(ctx, C.byref(model), C.byref(sig), C.byref(init), float(dt), _ptr(ys_d), T, rep, _ptr(idx_d),
-                                                               B, T, _ptr(dirs_d), n_dir, _ptr(nll), _ptr(grad), 0, _stream()))
+                raise ValueError(f'{entry} needs a sigma-point set')
+            rc = _timed('filter', lambda: getattr(lib, entry)(ctx, C.byref(model), C.byref(sig), C.byref(init), float(dt), _ptr(ys_d), T, rep, _ptr(idx_d),
+                                                              B, T, _ptr(dirs_d), n_dir, *out_ptrs, 0, _stream()))
         else:
-            rc = _timed('filter', lambda: lib.cgp_ekf_nll_grad(ctx, C.byref(model), C.byref(init), float(dt), _ptr(ys_d), T, rep, _ptr(idx_d),
-                                                               B, T, _ptr(dirs_d), n_dir, _ptr(nll), _ptr(grad), 0, _stream()))
+            rc = _timed('filter', lambda: getattr(lib, entry)(ctx, C.byref(model), C.byref(init), float(dt), _ptr(ys_d), T, rep, _ptr(idx_d),
+                                                              B, T, _ptr(dirs_d), n_dir, *out_ptrs, 0, _stream()))
         _check(ctx, rc, entry)
-        return nll, grad
+        return tuple(outs)
 
 
 E_UNSUPPORTED = -2

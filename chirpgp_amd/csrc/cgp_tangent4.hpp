@@ -19,12 +19,23 @@
 // Layout: lane g = trial * n_dir + direction -- a trial's directions sit in neighbouring lanes and read the same measurements (one
 // 64-byte request per eight steps, served once per trial by the cache).  Every lane repeats the primal (200 of its ~520 instructions a step):
 // cheaper than exchanging it.  value = nll[trial] (written by direction 0), grad[trial][direction].
+//
+// The Fisher form (cgp_ekf_nll_fisher, kFisher): the same step, and from its two tangents d nu and d S the information of the Gaussian
+// innovations model along the directions, F[i][j] = sum_t (d nu_i d nu_j / S + d S_i d S_j / (2 S^2)) -- the Gauss-Newton part of the
+// NLL's Hessian.  Lane `dir` keeps row `dir` in registers and reads d nu_j, d S_j from lane base + j of its trial's group (ds_bpermute:
+// no LDS memory, no barrier), so a trial must not straddle two wavefronts: 64 / n_dir whole trials per wavefront, the rest of the lanes
+// idle.  F[i][j] and F[j][i] are the same instructions on commuted products: the matrix comes out exactly symmetric.
+// The kernel is compiled for 4, 6, 8 and 16 row slots (kSlots >= n_dir; 6 is the chirp model's parameter count, cgp_inst_fisher4.hip): a step issues all its kSlots shuffles in one basic block, right
+// after d nu and d S are known, and folds them into the row after the update -- their LDS round trip runs under the update's arithmetic.
+// (Guarded by j < n_dir one by one, every pair of shuffles was a basic block of its own with a wait of its own: 1.40 x the gradient
+// kernel's time at six directions.)  Slots from n_dir on read some other lane and gather numbers nobody writes out.
 #pragma once
 #include "cgp_kernels.hpp"
 
 namespace cgp {
 
 constexpr int kDirDoubles = 24;      // d log rho | d q | d M (4) | d MS (3) | d Xi | d m0 (4) | d P0 (10)
+constexpr int kFisherMaxDir = CGP_FISHER_MAX_DIR;      // a Fisher row lives in registers: 2 VGPRs per slot
 
 struct TangentIO {
     const double* __restrict__ H;  int64_t H_stride;
@@ -37,6 +48,7 @@ struct TangentIO {
     int n_dir;
     double* __restrict__ nll;            // [B]
     double* __restrict__ grad;           // [B][n_dir]
+    double* __restrict__ fisher;         // [B][n_dir][n_dir]: the Fisher forms only (NULL otherwise)
     __device__ __forceinline__ const double* record(int64_t trial) const {
         int64_t g = trial;
         if (ys_repeat > 1) g = (int64_t)((uint64_t)trial / (uint64_t)ys_repeat);
@@ -45,9 +57,29 @@ struct TangentIO {
     }
 };
 
-#ifndef CGP_TANGENT4_IO_ONLY      // cgp_inst_tangent4_sgp.hip takes TangentIO and not a second copy of this kernel
+// x of lane `src` of the wavefront (any lane: ds_bpermute on the two halves; the source lane must be active)
+CGP_DEV double shuffle_f64(double x, int src) {
+    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
+    const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
+    return __hiloint2double(hi, lo);
+}
+
+#ifndef CGP_TANGENT4_IO_ONLY      // the sigma-point units take TangentIO and not a second copy of this kernel
+template <int kSlots>                 // 0: cgp_ekf_nll_grad; 4 / 6 / 8 / 16: cgp_ekf_nll_fisher with n_dir <= kSlots
 __global__ void __launch_bounds__(64) ekf4_tangent_kernel(TangentIO io, ModelArgs ma) {
-    const int64_t gidx = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    constexpr bool kFisher = kSlots > 0;
+    int64_t gidx;
+    int base = 0;                                                         // kFisher: the first lane of this trial's group
+    if constexpr (kFisher) {
+        const int slot = (int)threadIdx.x / io.n_dir;                     // whole trials only: lanes from (64 / n_dir) n_dir on stay idle
+        if (slot >= 64 / io.n_dir) return;
+        base = slot * io.n_dir;
+        const int64_t tr = (int64_t)blockIdx.x * (64 / io.n_dir) + slot;
+        if (tr >= io.B) return;
+        gidx = tr * io.n_dir + ((int)threadIdx.x - base);
+    } else {
+        gidx = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    }
     const int64_t total = io.B * io.n_dir;
     const bool active = gidx < total;
     if (!active) return;                                                  // (a partial wavefront runs with a partial EXEC mask)
@@ -76,6 +108,9 @@ __global__ void __launch_bounds__(64) ekf4_tangent_kernel(TangentIO io, ModelArg
         CGP_UNROLL for (int i = 0; i < 4; i++) CGP_UNROLL for (int j = 0; j <= i; j++) { P[k] = p0[i * 4 + j]; dP[k] = dp[14 + k]; k++; }
     }
     double nll = 0.0, dnll = 0.0;
+    double Frow[kFisher ? kSlots : 1];                                    // kFisher: row `dir` of F, constant indices only (registers)
+    CGP_UNROLL for (int j = 0; j < (kFisher ? kSlots : 1); j++) Frow[j] = 0.0;
+    (void)Frow;
     const double* __restrict__ rec = io.record(trial);
     auto S_ = [](const double (&A)[10], int i, int j) { return i >= j ? A[i * (i + 1) / 2 + j] : A[j * (j + 1) / 2 + i]; };
 
@@ -145,6 +180,10 @@ __global__ void __launch_bounds__(64) ekf4_tangent_kernel(TangentIO io, ModelArg
             const double pred = h[0] * mp0 + h[1] * mp1 + h[2] * mp2 + h[3] * mp3;
             const double nu = y - pred;
             const double dnu = -(h[0] * dmp0 + h[1] * dmp1 + h[2] * dmp2 + h[3] * dmp3);
+            double nj[kFisher ? kSlots : 1], sj[kFisher ? kSlots : 1];    // kFisher: d nu and d S of the trial's other directions
+            if constexpr (kFisher) {
+                CGP_UNROLL for (int j = 0; j < kSlots; j++) { nj[j] = shuffle_f64(dnu, base + j); sj[j] = shuffle_f64(dS, base + j); }
+            }
             double K[4], dK[4];
             CGP_UNROLL for (int i = 0; i < 4; i++) { K[i] = PH[i] * iS; dK[i] = (dPH[i] - K[i] * dS) * iS; }
             const double mpv[4] = {mp0, mp1, mp2, mp3}, dmpv[4] = {dmp0, dmp1, dmp2, dmp3};
@@ -160,20 +199,38 @@ __global__ void __launch_bounds__(64) ekf4_tangent_kernel(TangentIO io, ModelArg
             }
             nll += nll_increment(S, nu);
             dnll += 0.5 * (dS * iS + (2.0 * nu * dnu - nu * nu * dS * iS) * iS);
+            if constexpr (kFisher) {
+                // F[dir][j] += d nu_dir d nu_j / S + d S_dir d S_j / (2 S^2): S is the trial's (the same bits in all its lanes), and a
+                // product of two lanes' tangents is the same number in both of them
+                const double wn = iS, ws = 0.5 * iS * iS;
+                CGP_UNROLL for (int j = 0; j < kSlots; j++) Frow[j] = fma(dnu * nj[j], wn, fma(dS * sj[j], ws, Frow[j]));
+            }
         }
     }
     if (active) {
+        if constexpr (kFisher) {
+            const bool diverged = nll != nll;                             // a diverged filter: NaN in all three outputs
+            if (diverged) dnll = nll;
+            double* __restrict__ row = io.fisher + gi * io.n_dir;
+            CGP_UNROLL for (int j = 0; j < kSlots; j++) {
+                if (j < io.n_dir) row[j] = diverged ? nll : Frow[j];
+            }
+        }
         if (dir == 0) io.nll[trial] = nll;
         io.grad[gi] = dnll;
     }
 }
 
+// kSlots > 0: 64 / n_dir whole trials per wavefront; 1 <= n_dir <= kSlots and ceil(B / (64 / n_dir)) < 2^31 (the caller).
+template <int kSlots = 0>
 inline hipError_t launch_ekf4_tangent(const TangentIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.n_dir <= 0) return hipSuccess;                    // (T == 0 launches: the kernel skips its loop and writes nll = 0, grad = 0)
-    const int64_t total = io.B * io.n_dir;
-    hipLaunchKernelGGL(ekf4_tangent_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, stream, io, ma);
+    const int64_t total = io.B * io.n_dir, tpw = 64 / io.n_dir;
+    const int64_t blocks = kSlots > 0 ? (io.B + tpw - 1) / tpw : (total + 63) / 64;
+    hipLaunchKernelGGL(ekf4_tangent_kernel<kSlots>, dim3((unsigned)blocks), dim3(64), 0, stream, io, ma);
     return hipGetLastError();
 }
+
 #endif  // CGP_TANGENT4_IO_ONLY
 
 }  // namespace cgp

@@ -24,6 +24,10 @@
 //     kept (sets of up to 128 points; larger ones are re-evaluated in every pass).
 // Up to kSgpMaxDir directions per launch; more run as slices, one launch each.  A failed Cholesky poisons L and with it every sum: nll
 // and grad are NaN, as sgp_filter writes.  T == 0 writes nll = 0, grad = 0.
+//
+// The Fisher form (cgp_sgp_nll_fisher, kFisher): owner k also keeps row k of F[i][j] = sum_t (d nu_i d nu_j / S + d S_i d S_j / (2 S^2))
+// in registers; the source lane j is uniform, so d nu_j and d S_j come by v_readlane.  F couples all the directions of a launch: no
+// slices, n_dir <= kSgpMaxDir.
 #pragma once
 #include "cgp_coop4_sigma.hpp"
 #include "cgp_tangent4.hpp"
@@ -93,6 +97,7 @@ struct FanPoint {
     }
 };
 
+template <bool kFisher>
 __global__ void __launch_bounds__(64) sgp4_tangent_kernel(SgpTangentIO sio, ModelArgs ma) {
     __shared__ double red[kFanLdsDoubles];
     __shared__ __attribute__((aligned(16))) double dtab[(kSgpMaxDir + 1) * kSgpDirPitch];
@@ -153,6 +158,9 @@ __global__ void __launch_bounds__(64) sgp4_tangent_kernel(SgpTangentIO sio, Mode
         CGP_UNROLL for (int i = 0; i < 4; i++) CGP_UNROLL for (int j = 0; j <= i; j++) P(i, j) = p0[i * 4 + j];
     }
     double nll = 0.0, dnll = 0.0;
+    double Frow[kFisher ? kFisherMaxDir : 1];                             // kFisher: row `lane` of F, constant indices only (registers)
+    CGP_UNROLL for (int j = 0; j < (kFisher ? kFisherMaxDir : 1); j++) Frow[j] = 0.0;
+    (void)Frow;
     const double* __restrict__ ys = io.record(trial);
     const int64_t T = io.T;
     const bool narrow = s <= 32;                                          // only lanes 0..31 hold points: half the reduction work
@@ -248,21 +256,43 @@ __global__ void __launch_bounds__(64) sgp4_tangent_kernel(SgpTangentIO sio, Mode
                 }
             nll += nll_increment(S, nu);
             dnll += 0.5 * (dS_ * iS + (2.0 * nu * dnu - nu * nu * dS_ * iS) * iS);
+            if constexpr (kFisher) {
+                // F[lane][j] += d nu_lane d nu_j / S + d S_lane d S_j / (2 S^2), as cgp_tangent4.hpp: S is replicated, the products commute
+                const double wn = iS, ws = 0.5 * iS * iS;
+                CGP_UNROLL for (int j = 0; j < kFisherMaxDir; j++) {
+                    if (j < nd) {                                         // (uniform)
+                        const double nj = readlane_f64(dnu, j), sj = readlane_f64(dS_, j);
+                        Frow[j] = fma(dnu * nj, wn, fma(dS_ * sj, ws, Frow[j]));
+                    }
+                }
+            }
         }
     }
-    // (T == 0: nll = 0, grad = 0)
+    // (T == 0: nll = 0, grad = 0, fisher = 0)
+    if constexpr (kFisher) {
+        const bool diverged = nll != nll;                                 // a Cholesky that broke down: NaN in all three outputs
+        if (diverged) dnll = nll;
+        if (owner) {
+            double* __restrict__ row = io.fisher + (trial * io.n_dir + lane) * io.n_dir;      // (one launch: dir0 = 0, nd = n_dir)
+            CGP_UNROLL for (int j = 0; j < kFisherMaxDir; j++) {
+                if (j < nd) row[j] = diverged ? nll : Frow[j];
+            }
+        }
+    }
     if (lane == 0 && sio.dir0 == 0) io.nll[trial] = nll;
     if (owner) io.grad[trial * io.n_dir + sio.dir0 + lane] = dnll;
 }
 
 // One launch per slice of kSgpMaxDir directions; every slice repeats the primal (nll is written by the first).  B < 2^31 (the caller).
+// kFisher: n_dir <= kSgpMaxDir (the caller), so there is one slice with every direction in it.
+template <bool kFisher = false>
 inline hipError_t launch_sgp4_tangent(const TangentIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.n_dir <= 0) return hipSuccess;
     for (int dir0 = 0; dir0 < io.n_dir; dir0 += kSgpMaxDir) {
         SgpTangentIO sio;
         sio.t = io; sio.dir0 = dir0;
         sio.nd = io.n_dir - dir0 < kSgpMaxDir ? io.n_dir - dir0 : kSgpMaxDir;
-        hipLaunchKernelGGL(sgp4_tangent_kernel, dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, sio, ma);
+        hipLaunchKernelGGL(sgp4_tangent_kernel<kFisher>, dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, sio, ma);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

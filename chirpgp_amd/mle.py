@@ -13,7 +13,8 @@ import numpy as np
 from chirpgp_amd import filters_smoothers as fs
 from chirpgp_amd import models as M
 
-__all__ = ['batched_nll', 'make_objective', 'fit', 'fit_many', 'grid_search', 'value_and_grad', 'tangent_directions', 'has_exact_gradient']
+__all__ = ['batched_nll', 'make_objective', 'fit', 'fit_many', 'grid_search', 'value_and_grad', 'tangent_directions', 'has_exact_gradient',
+           'value_grad_fisher', 'covariance_from_fisher', 'standard_errors', 'scoring_step', 'fit_scoring']
 
 
 def batched_nll(method, build, thetas, ys, Xi, dt, sgps=None, record_index=None, **build_kw):
@@ -213,6 +214,157 @@ def value_and_grad(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf'
     else:
         nll, grad = E.run_ekf_nll_grad(disc, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=G // n_rec, record_index=record_index)
     return nll.cpu().numpy(), grad.cpu().numpy()
+
+
+def value_grad_fisher(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf', sgps=None):
+    """value_and_grad's results and, from the same launch, the Fisher information of the filter's Gaussian innovations model
+    F[i][j] = sum_t (d nu_i d nu_j / S + d S_i d S_j / (2 S^2)) (cgp_ekf_nll_fisher, cgp_sgp_nll_fisher): the Gauss-Newton part of the NLL's
+    Hessian, taken along tangent_directions -- the information in the UNCONSTRAINED theta.  Same eligibility and record addressing as
+    value_and_grad.  -> (nll (G,), grad (G, P), fisher (G, P, P)); fisher is exactly symmetric."""
+    from chirpgp_amd import _engine as E
+    if not has_exact_gradient(method, build, Xi, sgps):
+        raise _exact_unsupported()
+    thetas = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
+    G = thetas.shape[0]
+    n_rec = 1 if np.ndim(ys) == 1 else int(np.shape(ys)[0])
+    if record_index is not None:
+        n_rec = int(np.size(record_index))
+    if n_rec < 1 or G % n_rec:
+        raise ValueError(f'{G} parameter vectors cannot be shared out evenly over {n_rec} records')
+    with np.errstate(all='ignore'):
+        drift, disp, disc, m0, P0, H = build(M.g(thetas))
+    dirs = tangent_directions(build, thetas, dt, Xi)
+    if method == 'sgp_filter':
+        out = E.run_sgp_nll_fisher(disc, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=G // n_rec, record_index=record_index)
+    else:
+        out = E.run_ekf_nll_fisher(disc, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=G // n_rec, record_index=record_index)
+    return tuple(o.cpu().numpy() for o in out)
+
+
+SINGULAR_RCOND = 1e-12       # covariance_from_fisher: below this 1 / cond of the scaled information, the estimate has a flat direction
+
+
+def covariance_from_fisher(F, theta):
+    """Standard errors from a Fisher information F (P, P) in the unconstrained theta (P,): pure NumPy.
+
+    F is scaled by its diagonal, C = D^-1/2 F D^-1/2, so that the parameters' units do not decide its conditioning.  If C has no Cholesky
+    factor or 1 / cond(C) < SINGULAR_RCOND the information is singular: singular = True and every entry is inf -- a pseudo-inverse would
+    UNDERSTATE the uncertainty along a flat direction.  Otherwise cov_theta = F^-1 = D^-1/2 C^-1 D^-1/2 and the standard errors of the
+    positive parameters g(theta) follow by the delta method through the reference's g (softplus, models.py:50):
+    se_params = g'(theta) sqrt(diag cov_theta), g' = sigmoid.  -> (se_params (P,), cov_theta (P, P), cond, singular)."""
+    F = np.asarray(F, dtype=np.float64)
+    theta = np.asarray(theta, dtype=np.float64).reshape(-1)
+    P = theta.size
+    if F.shape != (P, P):
+        raise ValueError(f'F must be ({P}, {P}); got {F.shape}')
+    flat = (np.full(P, np.inf), np.full((P, P), np.inf), np.inf, True)
+    d = np.diag(F)
+    if not np.all(np.isfinite(F)) or not np.all(d > 0):
+        return flat
+    s = 1.0 / np.sqrt(d)
+    C = F * s[:, None] * s[None, :]
+    C = 0.5 * (C + C.T)
+    try:
+        np.linalg.cholesky(C)
+    except np.linalg.LinAlgError:
+        return flat
+    cond = float(np.linalg.cond(C))
+    if not np.isfinite(cond) or 1.0 / cond < SINGULAR_RCOND:
+        return flat[0], flat[1], cond, True
+    cov = np.linalg.inv(C) * s[:, None] * s[None, :]
+    cov = 0.5 * (cov + cov.T)
+    with np.errstate(over='ignore'):
+        dg = 1.0 / (1.0 + np.exp(-theta))
+    return dg * np.sqrt(np.diag(cov)), cov, cond, False
+
+
+def standard_errors(build, theta_hat, ys, Xi, dt, *, method='ekf', sgps=None):
+    """Standard errors of the fitted positive parameters g(theta_hat) of ONE record ys (T,) from the Fisher information at theta_hat (one
+    launch of value_grad_fisher; covariance_from_fisher).  -> (se_params (P,), cov_theta (P, P), info) with info['fisher'], ['cond'],
+    ['singular'], ['nll'] and ['grad']; a singular information gives inf everywhere and info['singular'] = True."""
+    theta_hat = np.asarray(theta_hat, dtype=np.float64).reshape(-1)
+    nll, grad, F = value_grad_fisher(build, theta_hat[None, :], ys, Xi, dt, method=method, sgps=sgps)
+    se, cov, cond, singular = covariance_from_fisher(F[0], theta_hat)
+    return se, cov, dict(fisher=F[0], cond=cond, singular=singular, nll=float(nll[0]), grad=grad[0])
+
+
+def scoring_step(F, grad, mu):
+    """The damped scoring step of fit_scoring, pure NumPy: (F + mu diag F) step = -grad.
+
+    With mu > 0 and a positive semi-definite F the matrix is singular only where a diagonal entry of F is exactly 0, and then that
+    parameter's whole row and column are 0: the likelihood does not see it along these directions (lam = 0, or a chirp noise b that has
+    underflowed).  Such a parameter STAYS WHERE IT IS (step 0, whatever its gradient entry) and the others take the step of the system
+    without it, which is positive definite.  -> step (P,)."""
+    F, grad = np.asarray(F, dtype=np.float64), np.asarray(grad, dtype=np.float64)
+    seen = np.diag(F) > 0
+    step = np.zeros(grad.size)
+    if seen.any():
+        A = F[np.ix_(seen, seen)]
+        step[seen] = np.linalg.solve(A + mu * np.diag(np.diag(A)), -grad[seen])
+    return step
+
+
+def fit_scoring(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=100, gtol=1e-5, mu0=1e-3, nu=4.0, mu_max=1e12):
+    """Maximum likelihood for R records in lock step by damped Fisher scoring: every iteration is ONE launch of value_grad_fisher for all
+    the records still active, each with its own iterate and damping.  A tangent launch costs the same whatever the batch
+    (EXACT_FROM_RECORDS), so the launches are the cost; scoring uses the curvature the kernel already carries instead of building it up
+    from gradient differences as fit_many's L-BFGS does.
+
+    Step: (F + mu diag F) step = -grad.  It is accepted only if the NLL decreases (a non-finite trial value is a rejection); then
+    mu /= nu, else mu *= nu, from mu = mu0.  A record leaves the active set when max |grad| <= gtol max(1, |f|) or when mu exceeds
+    mu_max (no decrease along any damped direction).  The methods of has_exact_gradient only.
+
+    yss (R, T); init_params (P,) or (R, P) positive model parameters -> (opt_params (R, P), info): fit_many's fun, grad, nit, launches,
+    converged (by the gradient rule), and fisher (R, P, P) at the final iterates, mu (R,), and per launch history (the (R,) NLLs of the
+    iterates after it) and iterates (those iterates, (R, P), in the unconstrained theta = g_inv(params))."""
+    from chirpgp_amd import _engine as E
+    if not has_exact_gradient(method, build, Xi, sgps):
+        raise _exact_unsupported()
+    yss = E.dev(yss)
+    if yss.ndim == 1:
+        yss = yss[None, :]
+    R = yss.shape[0]
+    x = np.array(np.broadcast_to(M.g_inv(np.asarray(init_params, dtype=np.float64)), (R, np.shape(init_params)[-1])))
+    P = x.shape[1]
+
+    def evaluate(xt, idx):
+        ft, gt, Ft = value_grad_fisher(build, xt, yss, Xi, dt, record_index=idx, method=method, sgps=sgps)
+        ok = np.isfinite(ft) & np.isfinite(gt).all(axis=1) & np.isfinite(Ft).all(axis=(1, 2))
+        return np.where(ok, ft, np.inf), gt, Ft, ok
+
+    f, g, F, ok = evaluate(x, None)
+    launches = 1
+    mu = np.full(R, float(mu0))
+    nit = np.zeros(R, dtype=int)
+    stalled = ~ok                                      # a start at which the filter diverges stays where it is
+
+    def small(f_, g_):
+        return np.abs(g_).max(axis=1) <= gtol * np.maximum(1.0, np.abs(f_))
+
+    converged = ok & small(np.where(ok, f, 0.0), np.where(ok[:, None], g, 0.0))
+    history, iterates = [f.copy()], [x.copy()]         # every record's NLL and iterate after every launch
+    for _ in range(maxiter):
+        active = ~(converged | stalled)
+        if not active.any():
+            break
+        idx = np.flatnonzero(active)
+        xt = x[idx].copy()
+        for n, r in enumerate(idx):
+            xt[n] += scoring_step(F[r], g[r], mu[r])
+        with np.errstate(all='ignore'):
+            ft, gt, Ft, okt = evaluate(xt, idx)
+        launches += 1
+        acc = okt & (ft < f[idx])
+        a = idx[acc]
+        x[a], f[a], g[a], F[a] = xt[acc], ft[acc], gt[acc], Ft[acc]
+        nit[a] += 1
+        mu[a] /= nu
+        mu[idx[~acc]] *= nu
+        converged[a] = small(f[a], g[a])
+        stalled |= active & (mu > mu_max)
+        history.append(f.copy())
+        iterates.append(x.copy())
+    return M.g(x), dict(fun=f, grad=g, nit=nit, launches=launches, converged=converged, fisher=F, mu=mu, history=history, iterates=iterates)
 
 
 def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=None, **build_kw):

@@ -1,10 +1,12 @@
 """Counterpart of the reference's demos/ekfs_mle.py on the MI355X engine: MLE -> EKF -> EKS -> E[g(V)] -> RMSE.
 
-    python demos/ekfs_mle.py [--method ekf|sgp_filter|cd_ekf] [--T 3141] [--seed 555] [--exact]
+    python demos/ekfs_mle.py [--method ekf|sgp_filter|cd_ekf] [--T 3141] [--seed 555] [--exact] [--stderr]
 
 --exact: the objective's gradient from a tangent kernel (forward tangents through the scan, what jax.value_and_grad gives the
 reference, demos/ekfs_mle.py:43-48) instead of 13-probe central differences: the EKF's (cgp_ekf_nll_grad) or, with --method sgp_filter,
 the sigma-point filter's (cgp_sgp_nll_grad).  cd_ekf has none.  The estimate E[g(V)] rides in the smoother launch.
+--stderr: the estimates with their standard errors, from the Fisher information of the filter's innovations at the optimum (one more
+launch: cgp_ekf_nll_fisher / cgp_sgp_nll_fisher, mle.standard_errors); "flat" where the information is singular.  Methods ekf, sgp_filter.
 """
 import argparse
 import math
@@ -29,7 +31,10 @@ def main():
     ap.add_argument('--T', type=int, default=3141)
     ap.add_argument('--seed', type=int, default=555)
     ap.add_argument('--exact', action='store_true', help='exact gradients (methods ekf and sgp_filter)')
+    ap.add_argument('--stderr', action='store_true', help='standard errors of the estimates (methods ekf and sgp_filter)')
     args = ap.parse_args()
+    if args.stderr and args.method == 'cd_ekf':
+        ap.error('--stderr: the Fisher kernels are built for the methods ekf and sgp_filter')
 
     dt, T = 0.001, args.T
     ts = np.linspace(dt, dt * T, T)
@@ -58,6 +63,10 @@ def main():
         assert np.allclose(est, gaussian_expectation(ms=mss[:, 2], chol_Ps=np.sqrt(Pss[:, 2, 2]), func=g, force_shape=True)[:, 0], rtol=1e-12)
         print(f'{name:10s} params {np.array2string(opt_params, precision=3)}  nll {res.fun:.2f}  iters {res.nit} '
               f'({res.nfev} launches)  RMSE {rmse(true_freq_func(ts), est):.3f} Hz  [{time.time() - t0:.2f} s]')
+        if args.stderr:
+            se, _, info = mle.standard_errors(build_chirp_model, res.x, ys, Xi, dt, method=args.method, sgps=sgps)
+            print(f'{"":10s} +-     {np.array2string(se, precision=3) if not info["singular"] else "flat: the information is singular"}'
+                  f'  (cond of the scaled information {info["cond"]:.3g})')
 
 
 if __name__ == '__main__':

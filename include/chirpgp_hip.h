@@ -20,6 +20,7 @@
  *                                                                      (demos/ekfs_mle.py:69-77: mss[:, k], Pss[:, k, k], gaussian_expectation), fused
  *   cgp_ekf_nll_grad                                                   value_and_grad of ekf(...)[-1][-1] through the scan, demos/ekfs_mle.py:43-51
  *   cgp_sgp_nll_grad                                                   value_and_grad of sgp_filter(...)[-1][-1] through the scan, demos/ghfs_mle.py:53-56
+ *   cgp_ekf_nll_fisher / cgp_sgp_nll_fisher                            (no counterpart: the reference's jobs report point estimates only)
  *   cgp_model_from_source, cgp_filter_custom, cgp_smoother_custom      ekf / eks / cd_ekf / cd_eks on ANY model (the reference traces any callable:
  *                                                                      filters_smoothers.py:255, 342, 382, 425; test/test_ekfs.py:11-62), compiled at run time
  *   cgp_gaussian_expectation                                           gaussian_expectation quadratures.py:234-274
@@ -241,6 +242,23 @@ int cgp_ekf_nll_grad(cgp_ctx* ctx, const cgp_model* model, const cgp_init* init,
 int cgp_sgp_nll_grad(cgp_ctx* ctx, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init, double dt,
                      const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
                      const double* dirs, int32_t n_dir, double* nll, double* grad, uint32_t flags, void* stream);
+
+/* cgp_ekf_nll_grad / cgp_sgp_nll_grad with one more output: the Fisher information of the filter's Gaussian innovations model,
+ *     fisher[b][i][j] = sum over steps t of ( d nu_i d nu_j / S  +  d S_i d S_j / (2 S^2) ),
+ * nu_t = y_t - H mp_t the innovation, S_t = H Pp_t H^T + Xi its variance, d . the tangents the gradient kernels carry along directions
+ * i and j.  It is the information ALONG THE CALLER'S DIRECTIONS (in chirpgp_amd/mle.py: in the unconstrained theta), the Gauss-Newton part
+ * of the NLL's Hessian, and needs no second derivatives: standard errors, flat directions, Fisher scoring.  fisher: [B][n_dir][n_dir],
+ * row-major, device; exactly symmetric (both triangles are written, by the same operations).  nll and grad as the gradient entry points
+ * write them; every other argument as theirs.  The matrix couples all the directions of a launch, so they are not sliced:
+ * n_dir <= CGP_FISHER_MAX_DIR, CGP_E_UNSUPPORTED beyond.  The EKF form runs 64 / n_dir whole trials per wavefront.  T = 0 writes
+ * nll = 0, grad = 0, fisher = 0; a diverged filter (a non-positive S, a Cholesky that breaks down) writes NaN to all three. */
+#define CGP_FISHER_MAX_DIR 16
+int cgp_ekf_nll_fisher(cgp_ctx* ctx, const cgp_model* model, const cgp_init* init, double dt,
+                       const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
+                       const double* dirs, int32_t n_dir, double* nll, double* grad, double* fisher, uint32_t flags, void* stream);
+int cgp_sgp_nll_fisher(cgp_ctx* ctx, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init, double dt,
+                       const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
+                       const double* dirs, int32_t n_dir, double* nll, double* grad, double* fisher, uint32_t flags, void* stream);
 
 /* ---- models compiled at run time ------------------------------------------------------------------------------------------
  * The reference's filters take any JAX-traceable callable (filters_smoothers.py:255, 304, 382, 425); the enumerated models above are the
