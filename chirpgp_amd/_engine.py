@@ -297,19 +297,27 @@ def _batched_operand(x, base_ndim, B, name):
     raise ValueError(f'{name}: expected {base_ndim} dims (shared) or a leading batch axis of {B}, got shape {tuple(t.shape)}')
 
 
-def _model_struct(spec, gamma, B, keep):
+def _model_operands(spec, gamma, B, keep):
+    """The model's device operands: (params, param_stride, b b^T or None, its stride)."""
     params = dev_const(spec.params)
     if params.ndim == 2 and params.shape[0] != B:
         raise ValueError(f'model parameters have batch {params.shape[0]} but the data has batch {B}')
     keep.append(params)
-    m = CgpModel()
-    m.model_id, m.d, m.n_harm, m.n_params = int(spec.model_id), int(spec.d), int(spec.n_harm), int(params.shape[-1])
-    m.params, m.param_stride = _ptr(params), (int(params.shape[-1]) if params.ndim == 2 else 0)
+    g, gs = None, 0
     if gamma is not None:
         g, gs = _batched_operand(gamma, 2, B, 'dispersion')
         if tuple(g.shape[-2:]) != (spec.d, spec.d):
             raise ValueError(f'b b^T must be {spec.d} x {spec.d}, got {tuple(g.shape)}')
         keep.append(g)
+    return params, (int(params.shape[-1]) if params.ndim == 2 else 0), g, gs
+
+
+def _model_struct(spec, gamma, B, keep):
+    params, pstride, g, gs = _model_operands(spec, gamma, B, keep)
+    m = CgpModel()
+    m.model_id, m.d, m.n_harm, m.n_params = int(spec.model_id), int(spec.d), int(spec.n_harm), int(params.shape[-1])
+    m.params, m.param_stride = _ptr(params), pstride
+    if g is not None:
         m.gamma, m.gamma_stride = _ptr(g), gs
     return m
 
@@ -392,6 +400,21 @@ def __getattr__(name):
     raise AttributeError(name)
 
 
+def _record_addressing(R, trials_per_record, record_index):
+    """The shared-record addressing of include/chirpgp_hip.h (cgp_filter) over R records: -> (ys_repeat, the int32 record numbers
+    for ys_index or None, B)."""
+    rep = 1 if trials_per_record is None else int(trials_per_record)
+    if rep < 1:
+        raise ValueError('trials_per_record must be >= 1')
+    idx_h = None
+    if record_index is not None:
+        idx_h = np.ascontiguousarray(np.asarray(record_index, dtype=np.int64).reshape(-1))
+        if idx_h.size and (idx_h.min() < 0 or idx_h.max() >= R):
+            raise ValueError(f'record_index outside 0..{R - 1}')
+        idx_h = idx_h.astype(np.int32)
+    return rep, idx_h, (R if idx_h is None else int(idx_h.size)) * rep
+
+
 def run_filter(method, spec, sgps, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=False, flags=0, want=(True, True, True),
                trials_per_record=None, record_index=None, time_split=None, split_tol=None, return_junction_error=False):
     """cgp_filter with NumPy / torch marshalling.  ys (T,) or (B, T) -> (mfs, Pfs, nll) with matching leading axes.
@@ -416,25 +439,15 @@ def run_filter(method, spec, sgps, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=
         ys_d = ys_d[None, :]
     if ys_d.ndim != 2:
         raise ValueError(f'ys must be (T,) or (B, T), got {tuple(ys_d.shape)}')
-    R, T = int(ys_d.shape[0]), int(ys_d.shape[1])
-    rep = 1 if trials_per_record is None else int(trials_per_record)
-    if rep < 1:
-        raise ValueError('trials_per_record must be >= 1')
-    idx_h = None
-    if record_index is not None:
-        idx_h = np.ascontiguousarray(np.asarray(record_index, dtype=np.int64).reshape(-1))
-        if idx_h.size and (idx_h.min() < 0 or idx_h.max() >= R):
-            raise ValueError(f'record_index outside 0..{R - 1}')
-    B = (R if idx_h is None else int(idx_h.size)) * rep
+    T = int(ys_d.shape[1])
+    rep, idx_h, B = _record_addressing(int(ys_d.shape[0]), trials_per_record, record_index)
     d = _check_dimension(spec)
     # constants, stream, outputs and the launch all belong to the device the data lives on, whatever the current one is
     with torch.cuda.device(ys_d.device):
         ctx = context(ys_d.device.index)
         keep = [ys_d]
-        idx_d = None
-        if idx_h is not None:
-            idx_d = _index_const(idx_h.astype(np.int32))
-            keep.append(idx_d)
+        idx_d = _index_const(idx_h) if idx_h is not None else None
+        keep.append(idx_d)
         model = _model_struct(spec, gamma, B, keep)
         sig = _sigma_struct(sgps, d, keep, _nonlinear_coord(spec))
         init = _init_struct(H, Xi, m0, P0, d, B, keep)
@@ -499,20 +512,6 @@ def release_custom_models():
     return n
 
 
-def _custom_params(spec, gamma, B, keep):
-    params = dev_const(spec.params)
-    if params.ndim == 2 and params.shape[0] != B:
-        raise ValueError(f'model parameters have batch {params.shape[0]} but the data has batch {B}')
-    keep.append(params)
-    g = gs = None
-    if gamma is not None:
-        g, gs = _batched_operand(gamma, 2, B, 'dispersion')
-        if tuple(g.shape[-2:]) != (spec.d, spec.d):
-            raise ValueError(f'b b^T must be {spec.d} x {spec.d}, got {tuple(g.shape)}')
-        keep.append(g)
-    return params, (int(params.shape[-1]) if params.ndim == 2 else 0), g, (gs or 0)
-
-
 def run_filter_custom(spec, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=False, want=(True, True, True), flags=0, sgps=None):
     """ekf / cd_ekf -- with `sgps`: sgp_filter / cd_sgp_filter -- on a model compiled at run time (cgp_filter_custom): the generic
     one-lane-per-trial kernel instantiated on the caller's source.  ys (T,) or (B, T)."""
@@ -528,7 +527,7 @@ def run_filter_custom(spec, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=False, 
         ctx = context(ys_d.device.index)
         handle = custom_model(spec, ys_d.device.index)
         keep = [ys_d]
-        params, pstride, g, gstride = _custom_params(spec, gamma, B, keep)
+        params, pstride, g, gstride = _model_operands(spec, gamma, B, keep)
         sig = _sigma_struct(sgps, d, keep, None)
         init = _init_struct(H, Xi, m0, P0, d, B, keep)
         opts = dict(dtype=torch.float64, device=ys_d.device)
@@ -559,7 +558,7 @@ def run_smoother_custom(spec, gamma, dt, mfs, Pfs, flags=0, sgps=None):
         ctx = context(m.device.index)
         handle = custom_model(spec, m.device.index)
         keep = [m, P]
-        params, pstride, g, gstride = _custom_params(spec, gamma, B, keep)
+        params, pstride, g, gstride = _model_operands(spec, gamma, B, keep)
         sig = _sigma_struct(sgps, d, keep, None)
         mss, Pss = torch.empty_like(m), torch.empty_like(P)
         rc = _timed('smoother', lambda: load_library().cgp_smoother_custom(ctx, handle, C.byref(sig) if sig is not None else None, _ptr(params), pstride, _ptr(g), gstride, float(dt), _ptr(m), _ptr(P),
@@ -575,41 +574,42 @@ FISHER_MAX_DIR = 16     # include/chirpgp_hip.h: CGP_FISHER_MAX_DIR
 def run_ekf_nll_grad(spec, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None):
     """cgp_ekf_nll_grad: the EKF's final NLL and its derivative along `dirs` (B, n_dir, 24) -- forward tangents through the scan, one
     launch.  ys (T,) or (R, T) with the shared-record addressing of run_filter.  Returns (nll (B,), grad (B, n_dir)) as device tensors."""
-    return _run_nll_grad('cgp_ekf_nll_grad', spec, None, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
+    return _run_nll_grad(spec, None, False, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
 
 
 def run_sgp_nll_grad(spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None):
     """cgp_sgp_nll_grad: the sigma-point filter's final NLL and its derivative along `dirs` (B, n_dir, 24), any d = 4 SigmaPoints `sgps`
     -- forward tangents through the scan, one launch; arguments and results as run_ekf_nll_grad.  The kernel sums over the points
     literally, so the set goes over ungrouped."""
-    return _run_nll_grad('cgp_sgp_nll_grad', spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
+    return _run_nll_grad(spec, _need_sigma(sgps, 'cgp_sgp_nll_grad'), False, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
 
 
 def run_ekf_nll_fisher(spec, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None):
     """cgp_ekf_nll_fisher: run_ekf_nll_grad's results and the Fisher information of the EKF's Gaussian innovations model along `dirs`
     (B, n_dir <= 16, 24), sum_t (d nu_i d nu_j / S + d S_i d S_j / (2 S^2)) -- one launch.  Returns (nll (B,), grad (B, n_dir),
     fisher (B, n_dir, n_dir)) as device tensors."""
-    return _run_nll_grad('cgp_ekf_nll_fisher', spec, None, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
+    return _run_nll_grad(spec, None, True, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
 
 
 def run_sgp_nll_fisher(spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None):
     """cgp_sgp_nll_fisher: the same for the sigma-point filter, any d = 4 SigmaPoints `sgps`; arguments and results as run_ekf_nll_fisher."""
-    return _run_nll_grad('cgp_sgp_nll_fisher', spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
+    return _run_nll_grad(spec, _need_sigma(sgps, 'cgp_sgp_nll_fisher'), True, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
 
 
-def _run_nll_grad(entry, spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index):
+def _need_sigma(sgps, entry):
+    if sgps is None:
+        raise ValueError(f'{entry} needs a sigma-point set')
+    return sgps
+
+
+def _run_nll_grad(spec, sgps, fisher, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index):
+    """The four tangent entry points: the sigma-point filter's with `sgps`, the EKF's with None; `fisher`: the matrix as a third output."""
     torch = _torch()
     ys_d = dev(ys)
     if ys_d.ndim == 1:
         ys_d = ys_d[None, :]
-    R, T = int(ys_d.shape[0]), int(ys_d.shape[1])
-    rep = 1 if trials_per_record is None else int(trials_per_record)
-    idx_h = None
-    if record_index is not None:
-        idx_h = np.ascontiguousarray(np.asarray(record_index, dtype=np.int64).reshape(-1))
-        if idx_h.size and (idx_h.min() < 0 or idx_h.max() >= R):
-            raise ValueError(f'record_index outside 0..{R - 1}')
-    B = (R if idx_h is None else int(idx_h.size)) * rep
+    T = int(ys_d.shape[1])
+    rep, idx_h, B = _record_addressing(int(ys_d.shape[0]), trials_per_record, record_index)
     d = _check_dimension(spec)
     dirs_h = np.ascontiguousarray(np.asarray(dirs, dtype=np.float64))
     if dirs_h.ndim != 3 or dirs_h.shape[0] != B or dirs_h.shape[2] != DIR_DOUBLES:
@@ -617,30 +617,17 @@ def _run_nll_grad(entry, spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_rec
     n_dir = int(dirs_h.shape[1])
     with torch.cuda.device(ys_d.device):
         ctx = context(ys_d.device.index)
-        keep = [ys_d]
-        idx_d = None
-        if idx_h is not None:
-            idx_d = _index_const(idx_h.astype(np.int32))
-            keep.append(idx_d)
+        idx_d = _index_const(idx_h) if idx_h is not None else None
+        keep = [ys_d, idx_d]
         model = _model_struct(spec, None, B, keep)
         init = _init_struct(H, Xi, m0, P0, d, B, keep)
         dirs_d = dev(dirs_h, ys_d.device.index)
         opts = dict(dtype=torch.float64, device=ys_d.device)
-        nll, grad = torch.empty((B,), **opts), torch.empty((B, n_dir), **opts)
-        outs = [nll, grad]
-        if entry.endswith('_fisher'):
-            outs.append(torch.empty((B, n_dir, n_dir), **opts))
-        out_ptrs = [_ptr(o) for o in outs]
-        lib = load_library()
-        if entry in ('cgp_sgp_nll_grad', 'cgp_sgp_nll_fisher'):
-            sig = _sigma_struct(sgps, d, keep, None)
-            if sig is None:
-                raise ValueError(f'{entry} needs a sigma-point set')
-            rc = _timed('filter', lambda: getattr(lib, entry)(ctx, C.byref(model), C.byref(sig), C.byref(init), float(dt), _ptr(ys_d), T, rep, _ptr(idx_d),
-                                                              B, T, _ptr(dirs_d), n_dir, *out_ptrs, 0, _stream()))
-        else:
-            rc = _timed('filter', lambda: getattr(lib, entry)(ctx, C.byref(model), C.byref(init), float(dt), _ptr(ys_d), T, rep, _ptr(idx_d),
-                                                              B, T, _ptr(dirs_d), n_dir, *out_ptrs, 0, _stream()))
+        outs = [torch.empty((B,), **opts), torch.empty((B, n_dir), **opts)] + ([torch.empty((B, n_dir, n_dir), **opts)] if fisher else [])
+        entry = f'cgp_{"ekf" if sgps is None else "sgp"}_nll_{"fisher" if fisher else "grad"}'
+        sig = [] if sgps is None else [C.byref(_sigma_struct(sgps, d, keep, None))]
+        rc = _timed('filter', lambda: getattr(load_library(), entry)(ctx, C.byref(model), *sig, C.byref(init), float(dt), _ptr(ys_d), T, rep, _ptr(idx_d),
+                                                                     B, T, _ptr(dirs_d), n_dir, *(_ptr(o) for o in outs), 0, _stream()))
         _check(ctx, rc, entry)
         return tuple(outs)
 

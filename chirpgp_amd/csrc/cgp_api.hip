@@ -62,19 +62,6 @@ static int check_model(cgp_ctx* ctx, const cgp_model* m, bool sde, bool need_sig
     return CGP_OK;
 }
 
-static ModelArgs model_args(const cgp_model* m, const cgp_sigma* sg, double dt, uint32_t flags) {
-    ModelArgs a;
-    a.params = m->params; a.param_stride = m->param_stride;
-    a.gamma = m->gamma; a.gamma_stride = m->gamma_stride;
-    a.model_id = m->model_id;
-    a.sg.xi = sg ? sg->xi : nullptr; a.sg.w = sg ? sg->w : nullptr; a.sg.s = sg ? sg->s : 0;
-    a.sg.group_start = sg ? sg->group_start : nullptr; a.sg.n_groups = (sg && sg->group_start) ? sg->n_groups : 0;
-    a.sg.lds_xi = 0; a.sg.lds_w = 0; a.sg.lds_gs = 0; a.sg.lds_tab = 0;
-    a.sg.flags = (sg && !(flags & CGP_LITERAL_SIGMA_SUM)) ? sg->flags : 0u;
-    a.dt = dt;
-    return a;
-}
-
 template <int FN>
 __global__ void __launch_bounds__(256) gaussian_expectation_kernel(const double* __restrict__ ms, const double* __restrict__ sd,
                                                                    int64_t n, int64_t stride, const double* __restrict__ xi,

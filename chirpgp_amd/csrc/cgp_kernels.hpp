@@ -233,6 +233,19 @@ CGP_DEV double* dyn_lds() {
 inline size_t sigma_lds_bytes(const ModelArgs& ma, int d) {
     return ma.sg.xi ? SigmaSet::stage_bytes(ma.sg.s, d, ma.sg.n_groups, ma.sg.group_start != nullptr) : 0;
 }
+// The kernels' view of the caller's model and sigma-point set (sg NULL: none; CGP_LITERAL_SIGMA_SUM: the set without its assertions)
+inline ModelArgs model_args(const cgp_model* m, const cgp_sigma* sg, double dt, uint32_t flags) {
+    ModelArgs a;
+    a.params = m->params; a.param_stride = m->param_stride;
+    a.gamma = m->gamma; a.gamma_stride = m->gamma_stride;
+    a.model_id = m->model_id;
+    a.sg.xi = sg ? sg->xi : nullptr; a.sg.w = sg ? sg->w : nullptr; a.sg.s = sg ? sg->s : 0;
+    a.sg.group_start = sg ? sg->group_start : nullptr; a.sg.n_groups = (sg && sg->group_start) ? sg->n_groups : 0;
+    a.sg.lds_xi = 0; a.sg.lds_w = 0; a.sg.lds_gs = 0; a.sg.lds_tab = 0;
+    a.sg.flags = (sg && !(flags & CGP_LITERAL_SIGMA_SUM)) ? sg->flags : 0u;
+    a.dt = dt;
+    return a;
+}
 
 // Linear scalar measurement y = H x + noise (every filter but ekf_for_kpt).
 template <int D> struct LinearMeasurement {

@@ -25,10 +25,15 @@
 // NLL's Hessian.  Lane `dir` keeps row `dir` in registers and reads d nu_j, d S_j from lane base + j of its trial's group (ds_bpermute:
 // no LDS memory, no barrier), so a trial must not straddle two wavefronts: 64 / n_dir whole trials per wavefront, the rest of the lanes
 // idle.  F[i][j] and F[j][i] are the same instructions on commuted products: the matrix comes out exactly symmetric.
-// The kernel is compiled for 4, 6, 8 and 16 row slots (kSlots >= n_dir; 6 is the chirp model's parameter count, cgp_inst_fisher4.hip): a step issues all its kSlots shuffles in one basic block, right
-// after d nu and d S are known, and folds them into the row after the update -- their LDS round trip runs under the update's arithmetic.
-// (Guarded by j < n_dir one by one, every pair of shuffles was a basic block of its own with a wait of its own: 1.40 x the gradient
-// kernel's time at six directions.)  Slots from n_dir on read some other lane and gather numbers nobody writes out.
+// The kernel is compiled for 4, 6, 8 and 16 row slots (kSlots >= n_dir; 6 is the chirp model's parameter count, cgp_inst_tangent4.hip).
+// The source asks for a step's kSlots pairs of shuffles after the update (tangent_update hands back d nu and d S), unguarded, so that
+// they and the update are one basic block; where they go is the compiler's scheduling.  In the gfx950 code of the 6-slot kernel all 24
+// ds_bpermute stand in one run of 37 instructions at the END of the step, behind the covariance update (there too when the source asked
+// for them between d nu and the gain), with the last operations of the NLL's increments between them; the row is then folded pair by
+// pair under waits that count down (lgkmcnt 14, 12, .. 0) beside the tail of the mean's update.  So the layout buys one basic block
+// and one stream of waits, not an overlap of the LDS round trip with the whole update.  (Guarded by j < n_dir one by one, every pair
+// of shuffles was a basic block of its own with a wait of its own: 1.40 x the gradient kernel's time at six directions.)  Slots from
+// n_dir on read some other lane and gather numbers nobody writes out.
 #pragma once
 #include "cgp_kernels.hpp"
 
@@ -62,6 +67,107 @@ CGP_DEV double shuffle_f64(double x, int src) {
     const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
     const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
     return __hiloint2double(hi, lo);
+}
+
+// The scalar update (filters_smoothers.py:55-68) with its tangent along one direction: from the predicted moments (mp, Pp) and their
+// tangents to the filtered ones and the NLL's increments.  Symmetric matrices are packed lower triangles (00 10 11 20 21 22 30 31 32 33:
+// Sym<4>::a).  The EKF kernel below calls it; the sigma-point kernel of cgp_tangent4_sigma.hpp spells the same expressions out, because
+// through this function it compiled to fewer instructions and spills and yet measured 4 % slower (profiles/README.md).
+struct TangentUpdate {
+    double S, dS, iS, nu, dnu;           // the innovation, its variance and their tangents: what the Fisher forms take from a step
+    // F[i][j] + d nu_i d nu_j / S + d S_i d S_j / (2 S^2) from this lane's (i) and another's (j) tangents: S is the trial's (the same bits
+    // in all its lanes), and a product of two lanes' tangents is the same number in both of them
+    CGP_DEV double fisher_add(double Fij, double nj, double sj) const {
+        const double wn = iS, ws = 0.5 * iS * iS;
+        return fma(dnu * nj, wn, fma(dS * sj, ws, Fij));
+    }
+};
+CGP_DEV TangentUpdate tangent_update(const double (&h)[4], double Xi, double dXi, double y, const double (&mp)[4], const double (&dmp)[4],
+                                     const double (&Pp)[10], const double (&dPp)[10], double (&m)[4], double (&dm)[4],
+                                     double (&P)[10], double (&dP)[10], double& nll, double& dnll) {
+    auto S_ = [](const double (&A)[10], int i, int j) { return A[Sym<4>::idx(i, j)]; };
+    double PH[4], dPH[4];
+    CGP_UNROLL for (int i = 0; i < 4; i++) {
+        PH[i] = S_(Pp, i, 0) * h[0] + S_(Pp, i, 1) * h[1] + S_(Pp, i, 2) * h[2] + S_(Pp, i, 3) * h[3];
+        dPH[i] = S_(dPp, i, 0) * h[0] + S_(dPp, i, 1) * h[1] + S_(dPp, i, 2) * h[2] + S_(dPp, i, 3) * h[3];
+    }
+    TangentUpdate u;
+    u.S = h[0] * PH[0] + h[1] * PH[1] + h[2] * PH[2] + h[3] * PH[3] + Xi;
+    u.dS = h[0] * dPH[0] + h[1] * dPH[1] + h[2] * dPH[2] + h[3] * dPH[3] + dXi;
+    u.iS = rcp_nr(u.S);
+    const double pred = h[0] * mp[0] + h[1] * mp[1] + h[2] * mp[2] + h[3] * mp[3];
+    u.nu = y - pred;
+    u.dnu = -(h[0] * dmp[0] + h[1] * dmp[1] + h[2] * dmp[2] + h[3] * dmp[3]);
+    const double S = u.S, dS = u.dS, iS = u.iS, nu = u.nu, dnu = u.dnu;
+    double K[4], dK[4];
+    CGP_UNROLL for (int i = 0; i < 4; i++) { K[i] = PH[i] * iS; dK[i] = (dPH[i] - K[i] * dS) * iS; }
+    CGP_UNROLL for (int i = 0; i < 4; i++) { m[i] = mp[i] + K[i] * nu; dm[i] = dmp[i] + dK[i] * nu + K[i] * dnu; }
+    int kk = 0;
+    CGP_UNROLL for (int i = 0; i < 4; i++) CGP_UNROLL for (int j = 0; j <= i; j++) {
+        const double kk_ij = K[i] * K[j];
+        P[kk] = Pp[kk] - kk_ij * S;
+        dP[kk] = dPp[kk] - (dK[i] * K[j] + K[i] * dK[j]) * S - kk_ij * dS;
+        kk++;
+    }
+    nll += nll_increment(S, nu);
+    dnll += 0.5 * (dS * iS + (2.0 * nu * dnu - nu * nu * dS * iS) * iS);
+    return u;
+}
+
+// ---- the host side the four entry points share (cgp_inst_tangent4.hip, cgp_inst_tangent4_sgp.hip): each is tangent_args, then its own
+// limit, then tangent_launch of its kernel.
+struct TangentCall {
+    const char* entry;                   // the entry point's name, for its messages
+    bool sgp, fisher;                    // takes a sigma-point set (sigma-point sets beyond the LDS stage are refused) / writes the matrix
+};
+
+// The argument checks in the ABI's order, then io and ma filled.  -> CGP_OK with io.B > 0: launch; CGP_OK with io.B == 0: nothing to do
+// (B == 0 or n_dir == 0, decided before anything else is looked at); otherwise the code, with the message left in the context.
+inline int tangent_args(cgp_ctx* ctx, TangentCall call, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init, double dt,
+                        const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
+                        const double* dirs, int32_t n_dir, double* nll, double* grad, double* fisher, TangentIO& io, ModelArgs& ma) {
+    const std::string entry = call.entry;
+    io.B = 0;
+    if (!ctx) return CGP_E_ARG;
+    if (B < 0 || T < 0 || n_dir < 0) return fail(ctx, CGP_E_ARG, "negative B, T or n_dir");
+    if (B == 0 || n_dir == 0) return CGP_OK;
+    if (call.fisher && n_dir > kFisherMaxDir)      // a row of the matrix lives in registers, and the matrix couples all the directions of a launch
+        return fail(ctx, CGP_E_UNSUPPORTED, entry + " takes all directions in one launch: n_dir must be <= CGP_FISHER_MAX_DIR (16)");
+    if (!model || !model->params) return fail(ctx, CGP_E_ARG, "model or model.params is NULL");
+    const bool chirp = model->model_id == CGP_M_HARMONIC_LCD && model->n_harm == 1 && model->n_params == 5;
+    const bool lascala = model->model_id == CGP_M_LASCALA_LCD && model->n_params == 2;
+    if ((!chirp && !lascala) || model->d != 4) return fail(ctx, CGP_E_UNSUPPORTED, entry + " is built for the d = 4 chirp and La Scala LCD models");
+    if (model->param_stride != 0 && model->param_stride < model->n_params) return fail(ctx, CGP_E_ARG, "model.param_stride < n_params");
+    if (call.sgp) {
+        if (!sigma) return fail(ctx, CGP_E_ARG, "sigma is NULL");
+        if (sigma->d != 4) return fail(ctx, CGP_E_UNSUPPORTED, entry + " is built for d = 4 sigma-point sets");
+        if (!sigma->xi || !sigma->w || sigma->s < 1) return fail(ctx, CGP_E_ARG, "cgp_sigma.xi / w must be set and s >= 1");
+        if (SigmaSet::stage_bytes(sigma->s, 4, 0, false) > (size_t)kSigLdsMaxBytes)
+            return fail(ctx, CGP_E_UNSUPPORTED, "the sigma-point set does not fit the LDS stage of " + entry);
+    }
+    if (!init || !init->H || !init->Xi || !init->m0 || !init->P0) return fail(ctx, CGP_E_ARG, "init.H / Xi / m0 / P0 must be set");
+    if (T > 0 && !ys) return fail(ctx, CGP_E_ARG, "ys is NULL");
+    if (ys_stride < 0 || ys_repeat < 1) return fail(ctx, CGP_E_ARG, "ys_stride must be >= 0 and ys_repeat >= 1");
+    if (!dirs || !nll || !grad || (call.fisher && !fisher))
+        return fail(ctx, CGP_E_ARG, call.fisher ? "dirs / nll / grad / fisher must be set" : "dirs / nll / grad must be set");
+    io.H = init->H; io.H_stride = init->H_stride; io.Xi = init->Xi; io.Xi_stride = init->Xi_stride;
+    io.m0 = init->m0; io.m0_stride = init->m0_stride; io.P0 = init->P0; io.P0_stride = init->P0_stride;
+    io.ys = ys; io.ys_stride = ys_stride; io.ys_repeat = ys_repeat; io.ys_index = ys_index;
+    io.dirs = dirs; io.B = B; io.T = T; io.n_dir = n_dir; io.nll = nll; io.grad = grad; io.fisher = call.fisher ? fisher : nullptr;
+    // the literal per-point sums: the kernels take no groups, so a grouped set is staged without its group table
+    ma = model_args(model, call.sgp ? sigma : nullptr, dt, CGP_LITERAL_SIGMA_SUM);
+    ma.sg.group_start = nullptr; ma.sg.n_groups = 0;
+    return CGP_OK;
+}
+
+// launch() on the context's device, under its launch lock
+template <class Launch>
+inline int tangent_launch(cgp_ctx* ctx, Launch launch) {
+    DeviceScope on_device(ctx->device);
+    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
+    std::lock_guard<std::recursive_mutex> launches(ctx->launch_mutex);
+    if (launch() != hipSuccess) return fail(ctx, CGP_E_HIP, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return CGP_OK;
 }
 
 #ifndef CGP_TANGENT4_IO_ONLY      // the sigma-point units take TangentIO and not a second copy of this kernel
@@ -168,42 +274,13 @@ __global__ void __launch_bounds__(64) ekf4_tangent_kernel(TangentIO io, ModelArg
                 Pp[0] += q; Pp[2] += q; Pp[5] += model.MS[0]; Pp[8] += model.MS[1]; Pp[9] += model.MS[2];          // Sigma = blockdiag(q, q, M32_Sigma)
                 dPp[0] += dq; dPp[2] += dq; dPp[5] += dS0; dPp[8] += dS1; dPp[9] += dS2;
             }
-            // ---- update (filters_smoothers.py:55-68) and its tangent
-            double PH[4], dPH[4];
-            CGP_UNROLL for (int i = 0; i < 4; i++) {
-                PH[i] = S_(Pp, i, 0) * h[0] + S_(Pp, i, 1) * h[1] + S_(Pp, i, 2) * h[2] + S_(Pp, i, 3) * h[3];
-                dPH[i] = S_(dPp, i, 0) * h[0] + S_(dPp, i, 1) * h[1] + S_(dPp, i, 2) * h[2] + S_(dPp, i, 3) * h[3];
-            }
-            const double S = h[0] * PH[0] + h[1] * PH[1] + h[2] * PH[2] + h[3] * PH[3] + Xi;
-            const double dS = h[0] * dPH[0] + h[1] * dPH[1] + h[2] * dPH[2] + h[3] * dPH[3] + dXi;
-            const double iS = rcp_nr(S);
-            const double pred = h[0] * mp0 + h[1] * mp1 + h[2] * mp2 + h[3] * mp3;
-            const double nu = y - pred;
-            const double dnu = -(h[0] * dmp0 + h[1] * dmp1 + h[2] * dmp2 + h[3] * dmp3);
-            double nj[kFisher ? kSlots : 1], sj[kFisher ? kSlots : 1];    // kFisher: d nu and d S of the trial's other directions
-            if constexpr (kFisher) {
-                CGP_UNROLL for (int j = 0; j < kSlots; j++) { nj[j] = shuffle_f64(dnu, base + j); sj[j] = shuffle_f64(dS, base + j); }
-            }
-            double K[4], dK[4];
-            CGP_UNROLL for (int i = 0; i < 4; i++) { K[i] = PH[i] * iS; dK[i] = (dPH[i] - K[i] * dS) * iS; }
+            // ---- update and its tangent; kFisher: d nu and d S of the trial's other directions into this lane's row
             const double mpv[4] = {mp0, mp1, mp2, mp3}, dmpv[4] = {dmp0, dmp1, dmp2, dmp3};
-            CGP_UNROLL for (int i = 0; i < 4; i++) { m[i] = mpv[i] + K[i] * nu; dm[i] = dmpv[i] + dK[i] * nu + K[i] * dnu; }
-            {
-                int kk = 0;
-                CGP_UNROLL for (int i = 0; i < 4; i++) CGP_UNROLL for (int j = 0; j <= i; j++) {
-                    const double kk_ij = K[i] * K[j];
-                    P[kk] = Pp[kk] - kk_ij * S;
-                    dP[kk] = dPp[kk] - (dK[i] * K[j] + K[i] * dK[j]) * S - kk_ij * dS;
-                    kk++;
-                }
-            }
-            nll += nll_increment(S, nu);
-            dnll += 0.5 * (dS * iS + (2.0 * nu * dnu - nu * nu * dS * iS) * iS);
+            const TangentUpdate u = tangent_update(h, Xi, dXi, y, mpv, dmpv, Pp, dPp, m, dm, P, dP, nll, dnll);
             if constexpr (kFisher) {
-                // F[dir][j] += d nu_dir d nu_j / S + d S_dir d S_j / (2 S^2): S is the trial's (the same bits in all its lanes), and a
-                // product of two lanes' tangents is the same number in both of them
-                const double wn = iS, ws = 0.5 * iS * iS;
-                CGP_UNROLL for (int j = 0; j < kSlots; j++) Frow[j] = fma(dnu * nj[j], wn, fma(dS * sj[j], ws, Frow[j]));
+                double nj[kSlots], sj[kSlots];
+                CGP_UNROLL for (int j = 0; j < kSlots; j++) { nj[j] = shuffle_f64(u.dnu, base + j); sj[j] = shuffle_f64(u.dS, base + j); }
+                CGP_UNROLL for (int j = 0; j < kSlots; j++) Frow[j] = u.fisher_add(Frow[j], nj[j], sj[j]);
             }
         }
     }

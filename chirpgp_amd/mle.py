@@ -17,6 +17,14 @@ __all__ = ['batched_nll', 'make_objective', 'fit', 'fit_many', 'grid_search', 'v
            'value_grad_fisher', 'covariance_from_fisher', 'standard_errors', 'scoring_step', 'fit_scoring']
 
 
+def _rows_per_record(G, ys, record_index):
+    """G parameter vectors shared out evenly over the records of ys -- (T,) or (R, T) -- or over the record_index entries: rows each."""
+    n_rec = int(np.size(record_index)) if record_index is not None else 1 if np.ndim(ys) == 1 else int(np.shape(ys)[0])
+    if n_rec < 1 or G % n_rec:
+        raise ValueError(f'{G} parameter vectors cannot be shared out evenly over {n_rec} records')
+    return G // n_rec
+
+
 def batched_nll(method, build, thetas, ys, Xi, dt, sgps=None, record_index=None, **build_kw):
     """Final cumulative NLL of ``method`` for every row of ``thetas`` (unconstrained parameters, g() maps them to the
     positive model parameters as in the reference).  ``ys`` is ONE record (T,) read by all G rows, or R records (R, T) of
@@ -28,13 +36,8 @@ def batched_nll(method, build, thetas, ys, Xi, dt, sgps=None, record_index=None,
     build_harmonic_chirp_model, build_lascala_model), or 'ekf_for_kpt' with models.build_kpt_chirp_model (pass ``fs=``,
     ``num_harmonics=``): tetralith/jobs/kpt_mle.py:41-44."""
     thetas = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
-    G = thetas.shape[0]
-    n_rec = 1 if np.ndim(ys) == 1 else int(np.shape(ys)[0])
-    if record_index is not None:
-        n_rec = int(np.size(record_index))
-    if n_rec < 1 or G % n_rec:
-        raise ValueError(f'{G} parameter vectors cannot be shared out evenly over {n_rec} records')
-    kw = dict(nll_final_only=True, want=(False, False, True), trials_per_record=G // n_rec, record_index=record_index)
+    kw = dict(nll_final_only=True, want=(False, False, True), trials_per_record=_rows_per_record(thetas.shape[0], ys, record_index),
+              record_index=record_index)
     with np.errstate(all='ignore'):        # a probe whose parameters under- or overflow yields a NaN objective, which the line search rejects
         built = build(M.g(thetas), **build_kw)
     if method == 'ekf_for_kpt':
@@ -192,28 +195,28 @@ def _exact_unsupported():
                       'set, sgps=) on build_chirp_model / build_lascala_model with a scalar Xi')
 
 
-def value_and_grad(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf', sgps=None):
-    """Objective and its EXACT gradient (forward tangents through the scan) at every row of thetas (G, P), in ONE launch: the EKF's
-    (method='ekf', cgp_ekf_nll_grad: G P lanes) or the sigma-point filter's (method='sgp_filter' with a d = 4 SigmaPoints ``sgps``,
-    cgp_sgp_nll_grad: G wavefronts).  ys (T,) or (R, T) shared out evenly over the rows as in batched_nll.  -> (nll (G,), grad (G, P))."""
+def _tangent_launch(fisher, build, thetas, ys, Xi, dt, record_index, method, sgps):
+    """One launch of a tangent kernel along tangent_directions at every row of thetas: (nll, grad) or, fisher, (nll, grad, F) as NumPy."""
     from chirpgp_amd import _engine as E
     if not has_exact_gradient(method, build, Xi, sgps):
         raise _exact_unsupported()
     thetas = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
-    G = thetas.shape[0]
-    n_rec = 1 if np.ndim(ys) == 1 else int(np.shape(ys)[0])
-    if record_index is not None:
-        n_rec = int(np.size(record_index))
-    if n_rec < 1 or G % n_rec:
-        raise ValueError(f'{G} parameter vectors cannot be shared out evenly over {n_rec} records')
+    rows = _rows_per_record(thetas.shape[0], ys, record_index)
     with np.errstate(all='ignore'):
         drift, disp, disc, m0, P0, H = build(M.g(thetas))
     dirs = tangent_directions(build, thetas, dt, Xi)
     if method == 'sgp_filter':
-        nll, grad = E.run_sgp_nll_grad(disc, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=G // n_rec, record_index=record_index)
+        out = (E.run_sgp_nll_fisher if fisher else E.run_sgp_nll_grad)(disc, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=rows, record_index=record_index)
     else:
-        nll, grad = E.run_ekf_nll_grad(disc, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=G // n_rec, record_index=record_index)
-    return nll.cpu().numpy(), grad.cpu().numpy()
+        out = (E.run_ekf_nll_fisher if fisher else E.run_ekf_nll_grad)(disc, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=rows, record_index=record_index)
+    return tuple(o.cpu().numpy() for o in out)
+
+
+def value_and_grad(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf', sgps=None):
+    """Objective and its EXACT gradient (forward tangents through the scan) at every row of thetas (G, P), in ONE launch: the EKF's
+    (method='ekf', cgp_ekf_nll_grad: G P lanes) or the sigma-point filter's (method='sgp_filter' with a d = 4 SigmaPoints ``sgps``,
+    cgp_sgp_nll_grad: G wavefronts).  ys (T,) or (R, T) shared out evenly over the rows as in batched_nll.  -> (nll (G,), grad (G, P))."""
+    return _tangent_launch(False, build, thetas, ys, Xi, dt, record_index, method, sgps)
 
 
 def value_grad_fisher(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf', sgps=None):
@@ -221,24 +224,7 @@ def value_grad_fisher(build, thetas, ys, Xi, dt, record_index=None, *, method='e
     F[i][j] = sum_t (d nu_i d nu_j / S + d S_i d S_j / (2 S^2)) (cgp_ekf_nll_fisher, cgp_sgp_nll_fisher): the Gauss-Newton part of the NLL's
     Hessian, taken along tangent_directions -- the information in the UNCONSTRAINED theta.  Same eligibility and record addressing as
     value_and_grad.  -> (nll (G,), grad (G, P), fisher (G, P, P)); fisher is exactly symmetric."""
-    from chirpgp_amd import _engine as E
-    if not has_exact_gradient(method, build, Xi, sgps):
-        raise _exact_unsupported()
-    thetas = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
-    G = thetas.shape[0]
-    n_rec = 1 if np.ndim(ys) == 1 else int(np.shape(ys)[0])
-    if record_index is not None:
-        n_rec = int(np.size(record_index))
-    if n_rec < 1 or G % n_rec:
-        raise ValueError(f'{G} parameter vectors cannot be shared out evenly over {n_rec} records')
-    with np.errstate(all='ignore'):
-        drift, disp, disc, m0, P0, H = build(M.g(thetas))
-    dirs = tangent_directions(build, thetas, dt, Xi)
-    if method == 'sgp_filter':
-        out = E.run_sgp_nll_fisher(disc, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=G // n_rec, record_index=record_index)
-    else:
-        out = E.run_ekf_nll_fisher(disc, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=G // n_rec, record_index=record_index)
-    return tuple(o.cpu().numpy() for o in out)
+    return _tangent_launch(True, build, thetas, ys, Xi, dt, record_index, method, sgps)
 
 
 SINGULAR_RCOND = 1e-12       # covariance_from_fisher: below this 1 / cond of the scaled information, the estimate has a flat direction

@@ -13,69 +13,20 @@ Measured on MI355X (gfx950), every case of the fixture (gate 1e-8 of the matrix'
   * the perf test (CGP_RUN_PERF=1): cgp_ekf_nll_grad 3.298 ms, cgp_ekf_nll_fisher 3.892 ms, ratio 1.180 (1.260 in the 8-slot kernel);
   * every new test fails on the parent commit: the entry points do not exist there."""
 import ctypes as C
-import os
+import functools
 
 import numpy as np
 import numpy.testing as npt
 import pytest
 
+from tests.tangent_cases import ZF, builder as _builder, directions as _directions, fisher_case as _case, raw, run_dirs, sigma as _sigma
+
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-ZF = np.load(os.path.join(HERE, 'golden', 'exact_fisher.npz'))
-ZG = np.load(os.path.join(HERE, 'golden', 'exact_grad_cases.npz'))
 NAMES = [str(n) for n in ZF['names']]
 VALUE_RTOL, GRAD_GATE, FISHER_GATE = 1e-11, 1e-8, 1e-8
 INIT = np.array([0.1, 0.1, 0.1, 1., 1., 7.])
 _results = {}
-
-
-# ------------------------------------------------------------------------------------------------ helpers
-def _case(name):
-    """A case of exact_fisher.npz: its inputs from exact_grad_cases.npz (the first T samples of the source's record), the exact F, and the
-    exact value and gradient at that record length."""
-    src, T = str(ZF[f'{name}.source']), int(ZF[f'{name}.T'])
-    c = {k: ZG[f'{src}.{k}'] for k in ('theta', 'ys', 'H', 'with_dxi')}
-    c.update({k: float(ZG[f'{src}.{k}']) for k in ('Xi', 'dt')})
-    c.update({k: str(ZG[f'{src}.{k}']) for k in ('build', 'method', 'sigma')})
-    if T == c['ys'].size:
-        c['nll'], c['grad'] = float(ZG[f'{src}.nll']), ZG[f'{src}.grad']
-    else:
-        c['nll'], c['grad'] = float(ZG[f'{src}.nll_prefix'][T - 1]), ZG[f'{src}.grad_prefix'][T - 1]
-    c.update(name=name, ys=c['ys'][:T], fisher=ZF[f'{name}.fisher'], with_dxi=int(c['with_dxi']))
-    return c
-
-
-def _builder(name):
-    from chirpgp_amd import models as pm
-    return pm.build_chirp_model if name == 'chirp' else pm.build_lascala_model
-
-
-def _sigma(name):
-    from chirpgp_amd.quadratures import SigmaPoints
-    if not name:
-        return None
-    return SigmaPoints.cubature(4) if name == 'cubature' else SigmaPoints.gauss_hermite(4, int(name[2:]))
-
-
-def _directions(c, thetas=None):
-    from chirpgp_amd import mle
-    return mle.tangent_directions(_builder(c['build']), c['theta'][None, :] if thetas is None else thetas, c['dt'], c['Xi'])
-
-
-def _run_dirs(c, dirs, fisher=True, thetas=None, ys=None, H=None, P0=None, **kw):
-    """The raw engine call E.run_*_nll_fisher (or run_*_nll_grad) with the caller's directions (B, n_dir, 24)."""
-    from chirpgp_amd import _engine as E, models as pm
-    thetas = c['theta'][None, :] if thetas is None else thetas
-    with np.errstate(all='ignore'):
-        drift, disp, disc, m0, P0_, H_ = _builder(c['build'])(pm.g(thetas))
-    H, P0 = (H_ if H is None else H), (P0_ if P0 is None else P0)
-    ys = c['ys'] if ys is None else ys
-    tail = 'fisher' if fisher else 'grad'
-    if c['method'] == 'ekf':
-        out = getattr(E, f'run_ekf_nll_{tail}')(disc, H, c['Xi'], m0, P0, c['dt'], ys, dirs, **kw)
-    else:
-        out = getattr(E, f'run_sgp_nll_{tail}')(disc, _sigma(c['sigma']), H, c['Xi'], m0, P0, c['dt'], ys, dirs, **kw)
-    return tuple(o.cpu().numpy() for o in out)
+_run_dirs = functools.partial(run_dirs, fisher=True)     # the raw engine call E.run_*_nll_fisher (fisher=False: run_*_nll_grad)
 
 
 def _fixture_result(name):
@@ -200,27 +151,7 @@ def test_value_and_gradient_are_the_gradient_kernels(name):
 # ------------------------------------------------------------------------------------------------ 6. edges
 def _raw(entry, c, T, n_dir, B=1, fisher=True, fill=123.0, P0=None):
     """The C entry point itself with output buffers pre-filled with `fill`: -> (return code, message, nll, grad, fisher)."""
-    import torch
-    from chirpgp_amd import _engine as E, models as pm
-    lib, ctx = E.load_library(), E.context()
-    keep = []
-    drift, disp, disc, m0, P0_, H = _builder(c['build'])(pm.g(c['theta']))
-    model = E._model_struct(disc, None, max(B, 1), keep)
-    init = E._init_struct(H, c['Xi'], m0, P0_ if P0 is None else P0, 4, max(B, 1), keep)
-    ys = E.dev(np.ascontiguousarray(c['ys'][:max(T, 1)]))
-    base = _directions(c)[0]
-    dirs_d = E.dev(np.ascontiguousarray(np.resize(base, (max(B, 1), n_dir, 24)).reshape(-1)))
-    opts = dict(dtype=torch.float64, device='cuda')
-    nll, grad, F = torch.full((max(B, 1),), fill, **opts), torch.full((max(B, 1), n_dir), fill, **opts), torch.full((max(B, 1), n_dir, n_dir), fill, **opts)
-    tail = (dirs_d.data_ptr(), n_dir, nll.data_ptr(), grad.data_ptr(), F.data_ptr() if fisher else None, 0, E._stream())
-    if entry == 'cgp_sgp_nll_fisher':
-        sig = E._sigma_struct(_sigma(c['sigma'] or 'cubature'), 4, keep, None)
-        rc = lib.cgp_sgp_nll_fisher(ctx, C.byref(model), C.byref(sig), C.byref(init), c['dt'], ys.data_ptr(), max(T, 1), 1, None, B, T, *tail)
-    else:
-        rc = lib.cgp_ekf_nll_fisher(ctx, C.byref(model), C.byref(init), c['dt'], ys.data_ptr(), max(T, 1), 1, None, B, T, *tail)
-    torch.cuda.synchronize()
-    msg = lib.cgp_last_error(ctx) if rc else b''
-    return rc, msg, nll.cpu().numpy(), grad.cpu().numpy(), F.cpu().numpy()
+    return raw(entry, c, T, np.resize(_directions(c)[0], (n_dir, 24)), fill, B=B, P0=P0, edit=None if fisher else lambda a: a.update(fisher=None))
 
 
 @pytest.mark.parametrize('entry', ['cgp_ekf_nll_fisher', 'cgp_sgp_nll_fisher'])

@@ -23,18 +23,14 @@ tests (13 s with test_gpu_gradient.py and test_gpu_sgp_gradient.py in the same r
     cubature run and in the EKF kernel); grad(a d1 + b d2) against a grad(d1) + b grad(d2): <= 2.4e-15 of the scale.
   * on the parent commit's library the T = 0 test fails with `cgp_ekf_nll_grad T = 0: rc 0 nll [nan] grad [nan nan nan nan nan nan]`.
 """
-import ctypes as C
-import os
-
 import numpy as np
 import numpy.testing as npt
 import pytest
 
 from tests import mle_oracle as mo
+from tests.tangent_cases import ZG as Z, builder as _builder, directions as _directions, grad_case as _case, raw, run_dirs as _run_dirs, sigma as _sigma
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'exact_grad_cases.npz')
-Z = np.load(GOLD)
 NAMES = [str(n) for n in Z['names']]
 VALUE_RTOL, GRAD_GATE, PORT_RTOL, TWO_SIDED = 1e-11, 1e-8, 1e-9, 2e-8
 CANCELLING = ('lam1e-6', 'lam1e-9', 'ell30')           # the value carries the reference formula's own cancellation: gated against the port
@@ -42,29 +38,6 @@ E_UNSUPPORTED = -2
 
 
 # ------------------------------------------------------------------------------------------------ helpers
-def _case(name):
-    keys = ('theta', 'ys', 'Xi', 'dt', 'H', 'build', 'method', 'sigma', 'nll', 'grad', 'group', 'lost', 'with_dxi', 'moved_nll', 'moved_grad')
-    c = {k: Z[f'{name}.{k}'] for k in keys}
-    for k in ('Xi', 'dt', 'nll', 'moved_nll', 'moved_grad'):
-        c[k] = float(c[k])
-    for k in ('build', 'method', 'sigma', 'group'):
-        c[k] = str(c[k])
-    c['name'] = name
-    return c
-
-
-def _builder(name):
-    from chirpgp_amd import models as pm
-    return pm.build_chirp_model if name == 'chirp' else pm.build_lascala_model
-
-
-def _sigma(name):
-    from chirpgp_amd.quadratures import SigmaPoints
-    if not name:
-        return None
-    return SigmaPoints.cubature(4) if name == 'cubature' else SigmaPoints.gauss_hermite(4, int(name[2:]))
-
-
 def _padded(sg, s):
     """`sg` with zero-weight points at the origin up to s points: they add exact zeros to every sum."""
     from chirpgp_amd.quadratures import SigmaPoints
@@ -87,26 +60,6 @@ def _vg(c, T=None, sg=None, thetas=None, ys=None, **kw):
     return mle.value_and_grad(_builder(c['build']), thetas, ys, c['Xi'], c['dt'], method=c['method'], sgps=sg, **kw)
 
 
-def _run_dirs(c, dirs, T=None, H=None, Xi=None, m0=None, P0=None, thetas=None, ys=None, **kw):
-    """The raw engine call E.run_*_nll_grad with the caller's directions (B, n_dir, 24) and, on request, its own H / Xi / m0 / P0."""
-    from chirpgp_amd import _engine as E, models as pm
-    thetas = c['theta'][None, :] if thetas is None else thetas
-    with np.errstate(all='ignore'):
-        drift, disp, disc, m0_, P0_, H_ = _builder(c['build'])(pm.g(thetas))
-    H, Xi, m0, P0 = (H_ if H is None else H), (c['Xi'] if Xi is None else Xi), (m0_ if m0 is None else m0), (P0_ if P0 is None else P0)
-    ys = (c['ys'] if T is None else c['ys'][:T]) if ys is None else ys
-    if c['method'] == 'ekf':
-        nll, grad = E.run_ekf_nll_grad(disc, H, Xi, m0, P0, c['dt'], ys, dirs, **kw)
-    else:
-        nll, grad = E.run_sgp_nll_grad(disc, _sigma(c['sigma']), H, Xi, m0, P0, c['dt'], ys, dirs, **kw)
-    return nll.cpu().numpy(), grad.cpu().numpy()
-
-
-def _directions(c, thetas=None):
-    from chirpgp_amd import mle
-    return mle.tangent_directions(_builder(c['build']), c['theta'][None, :] if thetas is None else thetas, c['dt'], c['Xi'])
-
-
 def _errors(f, grad, want_f, want_g, label):
     """(value relative error, gradient error over its largest component); prints them and the per-component errors."""
     scale = np.abs(want_g).max()
@@ -119,28 +72,8 @@ def _errors(f, grad, want_f, want_g, label):
 
 def _raw(entry, c, T, dirs, fill, sg=None):
     """The C entry point itself with output buffers pre-filled with `fill`: -> (return code, message, nll (1,), grad (n_dir,))."""
-    import torch
-    from chirpgp_amd import _engine as E, models as pm
-    lib, ctx = E.load_library(), E.context()
-    keep = []
-    drift, disp, disc, m0, P0, H = _builder(c['build'])(pm.g(c['theta']))
-    model = E._model_struct(disc, None, 1, keep)
-    init = E._init_struct(H, c['Xi'], m0, P0, 4, 1, keep)
-    ys = E.dev(np.ascontiguousarray(c['ys'][:max(T, 1)]))
-    n_dir = int(dirs.shape[0])
-    dirs_d = E.dev(np.ascontiguousarray(dirs.reshape(-1)))
-    nll = torch.full((1,), fill, dtype=torch.float64, device='cuda')
-    grad = torch.full((n_dir,), fill, dtype=torch.float64, device='cuda')
-    if entry == 'cgp_sgp_nll_grad':
-        sig = E._sigma_struct(sg, 4, keep, None)
-        rc = lib.cgp_sgp_nll_grad(ctx, C.byref(model), C.byref(sig), C.byref(init), c['dt'], ys.data_ptr(), max(T, 1), 1, None, 1, T,
-                                  dirs_d.data_ptr(), n_dir, nll.data_ptr(), grad.data_ptr(), 0, E._stream())
-    else:
-        rc = lib.cgp_ekf_nll_grad(ctx, C.byref(model), C.byref(init), c['dt'], ys.data_ptr(), max(T, 1), 1, None, 1, T,
-                                  dirs_d.data_ptr(), n_dir, nll.data_ptr(), grad.data_ptr(), 0, E._stream())
-    torch.cuda.synchronize()
-    msg = lib.cgp_last_error(ctx) if rc else b''
-    return rc, msg, nll.cpu().numpy(), grad.cpu().numpy()
+    rc, msg, nll, grad, _ = raw(entry, c, T, dirs, fill, sg=sg)
+    return rc, msg, nll, grad[0]
 
 
 # ------------------------------------------------------------------------------------------------ 0. the fixture holds what it must
