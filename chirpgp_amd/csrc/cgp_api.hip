@@ -1,4 +1,4 @@
-// cgp_api.hip -- the C-ABI of include/chirpgp_hip.h: argument checks, launch-shape choice, dispatch.
+// cgp_api.hip -- the C-ABI of include/chirpgp_hip.h: argument checks, the route (cgp_route.hpp), dispatch.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -7,32 +7,6 @@
 #include "cgp_ctx.hpp"
 
 namespace cgp {
-
-// Launch-shape choice.  One wavefront per trial is the latency-optimal shape while the batch is about the number of
-// SIMDs (1024): a step then costs its dependent-instruction chain once.  One lane per trial costs more per step but
-// carries 64 trials per wave, so it wins as soon as enough wavefronts would have to share a SIMD -- how many depends on how
-// much faster the lane-cooperative (matrix-core) kernel's step is than the one-lane step.  Crossovers measured on MI355X in
-// round 3 (bench.py --batch B --flags 2 | 4; wave-per-trial time grows linearly with B beyond 1024, the lane-per-trial time is
-// flat until B ~ 64 K), in trials per SIMD:
-//     EKF, chirp / La Scala d = 4 (MFMA, four trials per wave above 1024)   1.25 ms vs 2.58 at 8 K, 2.29 vs 2.65 at 16 K, 3.33 vs 2.89 at 24 K   -> 20
-//     EKF, 2 / 3 harmonics d = 6 / 8 (tile layout)                          0.93 vs 1.81 at 4 K, 1.73 vs 1.82 at 8 K, 3.29 vs 1.88 at 16 K        -> 8
-//     sigma-point filter, d = 4 (MFMA sums)                                 1.38 vs 8.17 at 4 K, 5.12 vs 8.18 at 16 K, 6.2 vs 5.1 at 32 K         -> 24
-//     sigma-point filter, d = 6 / 8 (tile layout)                           2.52 vs 6.95 at 4 K, 9.58 vs 6.99 at 16 K                             -> 11
-//     cd_ekf / cd_eks, d = 4 (MFMA)                                         1.41 vs 1.38 / 1.38 vs 1.90 at 4 K, 4.95 vs 1.40 / 4.89 vs 2.07 at 16 K -> 4 / 5
-//     cd_sgp filter / smoother, d = 4 (MFMA)                                2.3 vs 28.6 at 4 K, 9.2 vs 28.7 at 16 K                               -> 48
-//     discrete smoothers on the cooperative walks (d = 4 .. 8)              never slower than one lane per trial: 0.36 vs 9.98 ms (sigma-point d = 4,
-//                                                                           4 K), 2.77 vs 18.4 (EKS d = 8, 16 K), 9.4 vs 10.6 (EKS d = 4, 256 K)   -> always
-//     everything on the generic kernels                                     as measured in round 1: 2.5 (EKF-type), 8 (sigma-point), 16 (affine scan)
-struct ShapeLimit { int num, den; };                      // one wavefront per trial while B * den < num * SIMDs; num < 0: always
-static bool choose_wave(const cgp_ctx* ctx, int64_t B, uint32_t flags, ShapeLimit limit, const cgp_sigma* sg = nullptr) {
-    // the wave-per-trial shapes stage the sigma-point set in LDS; a set that does not fit runs one lane per trial
-    if (sg && SigmaSet::stage_bytes(sg->s, sg->d, sg->n_groups, sg->group_start != nullptr) > (size_t)kSigLdsMaxBytes) return false;
-    if (flags & CGP_WAVE_PER_TRIAL) return true;
-    if (flags & CGP_THREAD_PER_TRIAL) return false;
-    if (limit.num < 0) return true;
-    const int64_t simds = (int64_t)(ctx ? ctx->num_cus : 256) * 4;
-    return B * limit.den < (int64_t)limit.num * simds;
-}
 
 static int check_model(cgp_ctx* ctx, const cgp_model* m, bool sde, bool need_sigma, const cgp_sigma* sg) {
     if (!m || !m->params) return fail(ctx, CGP_E_ARG, "model or model.params is NULL");
@@ -160,11 +134,6 @@ __global__ void __launch_bounds__(64) debug_math_uniform_kernel(int op, const do
         else fast_sincos_uniform(v, a, b);
         if (threadIdx.x == 0) { o0[i] = a; if (o1) o1[i] = b; }
     }
-}
-
-// Whether a d = 4 sigma-point launch takes the matrix-core kernel (cgp_inst_coop4.hip: sigma_mfma) -- the one that knows segments.
-static bool sigma_mfma_taken(uint32_t flags, int64_t T, const ModelArgs& ma) {
-    return !(flags & CGP_DPP_KERNEL) && (ma.sg.flags & CGP_SIGMA_STANDARD) && ma.sg.group_start && ma.sg.n_groups >= 1 && ma.sg.n_groups <= 32 && T * 128 <= 0x7FFFFF00LL;
 }
 
 // Fix-up pass of a time-split filter launch (one workgroup per trial):
@@ -358,93 +327,58 @@ static int filter_impl(cgp_ctx* ctx, int method, const cgp_model* model, const c
     io.ys = ys; io.ys_stride = ys_stride; io.ys_repeat = ys_repeat; io.ys_index = ys_index; io.B = B; io.T = T; io.mfs = mfs; io.Pfs = Pfs; io.nll = nll; io.flags = flags;
     io.counters = ctx->counters;
     const ModelArgs ma = model_args(model, sigma, dt, flags);
-    // ---- time-split with burn-in (cgp_filter_time_split): segments of whole 64-step chunks, one wavefront each
     const bool split = segments > 1;
-    double* seg_ws = nullptr;
     if (split) {
         if (burn_in < 0) return fail(ctx, CGP_E_ARG, "burn_in must be >= 0");
         if (!junction_err) return fail(ctx, CGP_E_ARG, "junction_err must be set: a time-split filter is only as good as its junctions");
-        // the kernels that know segments, under the conditions the dispatch below sends a launch to them
-        const bool lcd4 = model->n_harm == 1 && (model->model_id == CGP_M_HARMONIC_LCD || model->model_id == CGP_M_LASCALA_LCD);
-        bool known = false;
-        if (!(flags & (CGP_GENERIC_KERNEL | CGP_DPP_KERNEL | CGP_THREAD_PER_TRIAL | CGP_FOUR_TRIALS_PER_WAVE))) {
-            if (method == CGP_F_SGP && lcd4) known = sigma_mfma_taken(flags, T, ma);
-            else if (method == CGP_F_SGP && model->model_id == CGP_M_HARMONIC_LCD) known = coop8_filter_sgp_ok(model->n_harm, T, ma);
-            else if (method == CGP_F_CD_SGP && model->model_id == CGP_M_HARMONIC_SDE && model->n_harm == 1) known = sigma_mfma_taken(flags, T, ma);
-            else if (method == CGP_F_EKF && lcd4) known = T * 128 <= 0x7FFFFF00LL;
-        }
-        if (!known)
-            return fail(ctx, CGP_E_UNSUPPORTED, "time-split filters are built for ekf / sgp_filter / cd_sgp_filter on the d = 4 chirp and La Scala models "
-                                                "and sgp_filter on the 2- / 3-harmonic model (matrix-core and tile-layout kernels, standard sigma sets)");
-        int64_t seg_len = ((T + segments - 1) / segments + 63) / 64 * 64;
-        const int64_t segs = (T + seg_len - 1) / seg_len;                  // without the empty ones
-        io.segs = (int)segs; io.seg_len = seg_len; io.burn_in = (burn_in + 63) / 64 * 64;
+    }
+    const FilterDecision route = route_filter({method, model, sigma, &io, &ma, flags, segments, ctx->num_cus});
+    if (route.rc != CGP_OK) return fail(ctx, route.rc, route.message);
+    const bool wave = route.wave;
+    hipStream_t st = (hipStream_t)stream;
+    io.flags = route.flags;
+    if (split) {
+        // time-split with burn-in (cgp_filter_time_split): segments of whole 64-step chunks, one wavefront each
+        io.segs = route.segs; io.seg_len = route.seg_len; io.burn_in = (burn_in + 63) / 64 * 64;
         io.seg_stride = seg_layout(model->d).stride;
-        if (segs > 1) {
-            // (a set too large for the LDS stage runs one lane per trial whatever the flags say -- choose_wave -- and those kernels
-            // know no segments: refuse instead of reading records nobody wrote)
-            if (sig && SigmaSet::stage_bytes(sigma->s, sigma->d, sigma->n_groups, sigma->group_start != nullptr) > (size_t)kSigLdsMaxBytes)
-                return fail(ctx, CGP_E_UNSUPPORTED, "time-split filters need a sigma-point set that fits the LDS stage of the one-wavefront-per-trial kernels");
-            const size_t seg_doubles = (size_t)io.seg_stride * (size_t)B * (size_t)segs;
-            seg_ws = (double*)ctx_workspace(ctx, (hipStream_t)stream, sizeof(double) * seg_doubles);
+        if (io.segs > 1) {
+            const size_t seg_doubles = (size_t)io.seg_stride * (size_t)B * (size_t)io.segs;
+            double* seg_ws = (double*)ctx_workspace(ctx, st, sizeof(double) * seg_doubles);
             if (!seg_ws) return fail(ctx, CGP_E_HIP, "no workspace for the segment records (allocation failed, or the buffer would grow inside a graph capture: cgp_reserve_workspace first)");
             // NaN-filled: a kernel that ignored the segments would show as junction_err = inf, not as garbage
-            if (hipMemsetAsync(seg_ws, 0xFF, sizeof(double) * seg_doubles, (hipStream_t)stream) != hipSuccess) return fail(ctx, CGP_E_HIP, "hipMemsetAsync of the segment records failed");
+            if (hipMemsetAsync(seg_ws, 0xFF, sizeof(double) * seg_doubles, st) != hipSuccess) return fail(ctx, CGP_E_HIP, "hipMemsetAsync of the segment records failed");
             io.seg_state = seg_ws;
-            flags |= CGP_WAVE_PER_TRIAL;
-            io.flags = flags;
-        } else io.segs = 1;
+        }
     }
-    // which lane-cooperative kernel (if any) a wave-per-trial launch of this call would take decides the crossover
-    const bool spec = !(flags & CGP_GENERIC_KERNEL);
-    const bool chirp4 = spec && model->n_harm == 1 && (model->model_id == CGP_M_HARMONIC_LCD || model->model_id == CGP_M_LASCALA_LCD);
-    const bool harm8 = spec && model->model_id == CGP_M_HARMONIC_LCD && (model->n_harm == 2 || model->n_harm == 3);
-    const bool sde4 = spec && model->model_id == CGP_M_HARMONIC_SDE && model->n_harm == 1;
-    const bool mfma = !(flags & CGP_DPP_KERNEL);
-    ShapeLimit limit = sig ? ShapeLimit{8, 1} : ShapeLimit{5, 2};
-    // (round 5: where the large-batch lane kernel of cgp_lane4.hpp takes the launch, one lane per trial wins from 9 / 9 trials per
-    // SIMD on -- tools/lane_crossover.sh, profiles/r05_lane_crossover.txt: EKF 0.49 against 0.59 ms at 8192 x 500 and 0.71 against 0.59 at
-    // 10 240 (CRLB records, i.e. with the four-trials-per-wavefront kernel on its branch-free wide step), GH-3 4.3 against 5.0 ms at
-    // 8192 x 500 and 6.5 against 5.0 at 12 288 (after the lane kernel's fan stopped running twice on records outside the lean regime); the generic lane kernel it replaces there kept the round-3 limits of 20 / 24)
-    const bool lane4 = spec && lane4_filter_fits(io);
-    if (method == CGP_F_EKF && chirp4 && mfma && !(flags & CGP_ONE_TRIAL_PER_WAVE)) limit = lane4 ? ShapeLimit{9, 1} : ShapeLimit{20, 1};
-    else if (method == CGP_F_EKF && harm8) limit = {8, 1};
-    else if (method == CGP_F_SGP && chirp4 && mfma) limit = (lane4 && sigma_lds_bytes(ma, 4) <= (size_t)kLane4SigLdsMaxBytes) ? ShapeLimit{9, 1} : ShapeLimit{24, 1};
-    else if (method == CGP_F_SGP && harm8) limit = {11, 1};
-    else if (method == CGP_F_CD_EKF && sde4 && mfma) limit = {4, 1};
-    else if (method == CGP_F_CD_SGP && sde4 && mfma) limit = {48, 1};
-    const bool wave = choose_wave(ctx, B, flags, limit, sig ? sigma : nullptr);
-    if (split && io.segs > 1 && !wave) return fail(ctx, CGP_E_UNSUPPORTED, "time-split filters run one wavefront per trial only");
-    hipStream_t st = (hipStream_t)stream;
-    switch (model->model_id) {
-    case CGP_M_LINEAR:
-        // kf at d = 4, one wavefront per trial: the matrix-core step of the EKF with the constant Jacobian F
-        if (method == CGP_F_EKF && model->d == 4 && wave && !(flags & (CGP_GENERIC_KERNEL | CGP_DPP_KERNEL)) && T * 128 <= 0x7FFFFF00LL) rc = dispatch_filter_kf4_mfma(io, ma, st);
-        else rc = dispatch_filter_disc_linear(method, model->d, wave, io, ma, st);
+    switch (route.route) {
+    case FilterRoute::kGenericWave:
+    case FilterRoute::kGenericLane:
+        switch (model->model_id) {
+        case CGP_M_LINEAR:       rc = dispatch_filter_disc_linear(method, model->d, wave, io, ma, st); break;
+        case CGP_M_HARMONIC_LCD:
+        case CGP_M_LASCALA_LCD:  rc = dispatch_filter_disc_harm(method, model->n_harm, wave, io, ma, st); break;
+        case CGP_M_LINEAR_SDE:   rc = dispatch_filter_sde_linear(method, model->d, wave, io, ma, st); break;
+        case CGP_M_HARMONIC_SDE: rc = dispatch_filter_sde_harm(method, model->n_harm, wave, io, ma, st); break;
+        default: rc = CGP_E_ARG;
+        }
         break;
-    case CGP_M_HARMONIC_LCD:
-    case CGP_M_LASCALA_LCD:
-        // d = 4 EKF, one wavefront per trial: the lane-cooperative kernel (covariance spread over a 16-lane DPP row)
-        if (method == CGP_F_EKF && model->n_harm == 1 && wave && !(flags & CGP_GENERIC_KERNEL)) rc = dispatch_filter_coop4(io, ma, st);
-        else if (method == CGP_F_SGP && model->n_harm == 1 && wave && !(flags & CGP_GENERIC_KERNEL)) rc = dispatch_filter_coop4_sgp(io, ma, st);
-        else if (method == CGP_F_EKF && wave && !(flags & CGP_GENERIC_KERNEL) && model->model_id == CGP_M_HARMONIC_LCD && (model->n_harm == 2 || model->n_harm == 3)
-                 && io.T * model->d * model->d * 8 <= 0x7FFFFF00LL)                              // the kernel's output windows (cgp_coop4.hpp:kOobMaxBytes)
-            rc = dispatch_filter_coop8_ekf(model->n_harm, io, ma, st);
-        else if (method == CGP_F_SGP && wave && !(flags & CGP_GENERIC_KERNEL) && model->model_id == CGP_M_HARMONIC_LCD && coop8_filter_sgp_ok(model->n_harm, io.T, ma))
-            rc = dispatch_filter_coop8_sgp(model->n_harm, io, ma, st);
-        else if ((method == CGP_F_EKF || (method == CGP_F_SGP && sigma_lds_bytes(ma, 4) <= (size_t)kLane4SigLdsMaxBytes)) && model->n_harm == 1 && !wave &&
-                 !(flags & CGP_GENERIC_KERNEL) && lane4_filter_fits(io))
-            rc = dispatch_filter_lane4(method, io, ma, st);                                      // large batches: cgp_lane4.hpp
-        else rc = dispatch_filter_disc_harm(method, model->n_harm, wave, io, ma, st);
-        break;
-    case CGP_M_LINEAR_SDE:   rc = dispatch_filter_sde_linear(method, model->d, wave, io, ma, st); break;
-    case CGP_M_HARMONIC_SDE:
-        if (method == CGP_F_CD_SGP && model->n_harm == 1 && wave && !(flags & CGP_GENERIC_KERNEL)) rc = dispatch_filter_coop4_cdsgp(io, ma, st);
-        else if (method == CGP_F_CD_EKF && model->n_harm == 1 && wave && !(flags & CGP_GENERIC_KERNEL)) rc = dispatch_filter_coop4_cdekf(io, ma, st);
-        else rc = dispatch_filter_sde_harm(method, model->n_harm, wave, io, ma, st);
-        break;
-    case CGP_M_KPT:          rc = dispatch_filter_kpt(model->n_harm, wave, io, ma, st); break;
-    default: rc = CGP_E_ARG;
+    case FilterRoute::kKf4Mfma:     rc = dispatch_filter_kf4_mfma(io, ma, st); break;
+    case FilterRoute::kEkf4Mfma:
+    case FilterRoute::kEkf4MfmaSeg: rc = dispatch_filter_mfma4(io, ma, st); break;
+    case FilterRoute::kEkf4MfmaX4:  rc = launch_ekf4_mfma_x4(io, ma, st); break;
+    case FilterRoute::kEkf4Coop:    rc = dispatch_filter_coop4(io, ma, st); break;
+    case FilterRoute::kSgp4Mfma:    rc = dispatch_filter_mfma4_sgp(io, ma, st); break;
+    case FilterRoute::kSgp4Coop:    rc = dispatch_filter_coop4_sgp(io, ma, st); break;
+    case FilterRoute::kLane4Ekf:
+    case FilterRoute::kLane4Sgp:    rc = dispatch_filter_lane4(method, io, ma, st); break;
+    case FilterRoute::kEkf8Coop:    rc = dispatch_filter_coop8_ekf(model->n_harm, io, ma, st); break;
+    case FilterRoute::kSgp8Coop:    rc = dispatch_filter_coop8_sgp(model->n_harm, io, ma, st); break;
+    case FilterRoute::kCdEkf4Mfma:  rc = dispatch_filter_mfma4_cdekf(io, ma, st); break;
+    case FilterRoute::kCdEkf4Coop:  rc = dispatch_filter_coop4_cdekf(io, ma, st); break;
+    case FilterRoute::kCdSgp4Mfma:  rc = dispatch_filter_mfma4_cdsgp(io, ma, st); break;
+    case FilterRoute::kCdSgp4Coop:  rc = dispatch_filter_coop4_cdsgp(io, ma, st); break;
+    case FilterRoute::kKpt8Coop:    rc = dispatch_filter_kpt8(model->n_harm, io, ma, st); break;
+    case FilterRoute::kGenericKpt:  rc = dispatch_filter_kpt(model->n_harm, wave, io, ma, st); break;
     }
     if (split) {
         if (rc == CGP_OK) {
@@ -523,57 +457,12 @@ static int smoother_impl(cgp_ctx* ctx, int method, const cgp_model* model, const
         io.min_tiles = forced ? 1 : 4;
     }
     const ModelArgs ma = model_args(model, sigma, dt, flags);
-    const bool affine = (method == CGP_S_EKS || method == CGP_S_SGP) && !(flags & CGP_SEQUENTIAL_SCAN);
-    // launch shape (see choose_wave): the cooperative walks of the discrete smoothers are never slower than one lane per trial
-    const bool spec = !(flags & CGP_GENERIC_KERNEL);
-    const bool sde4 = spec && model->model_id == CGP_M_HARMONIC_SDE && model->n_harm == 1 && !(flags & CGP_DPP_KERNEL);
-    bool coop_walk = false;
-    if (affine && spec) {
-        if (model->model_id == CGP_M_LINEAR) coop_walk = coop8_smoother_ok(model->d, T, ma) || (model->d == 4 && walk4_smoother_fits(T, ma));
-        else if (model->model_id == CGP_M_HARMONIC_LCD || model->model_id == CGP_M_LASCALA_LCD)
-            coop_walk = (model->n_harm >= 2 && coop8_smoother_ok(model->d, T, ma) && coop8_smoother_harm_ok(method, ma)) || (model->n_harm == 1 && walk4_smoother_fits(T, ma));
-    }
-    ShapeLimit limit = affine ? ShapeLimit{16, 1} : (sig ? ShapeLimit{8, 1} : ShapeLimit{5, 2});
-    if (coop_walk) limit = {-1, 1};
-    else if (method == CGP_S_CD_EKS && sde4) limit = lane4_smoother_fits(io) ? ShapeLimit{3, 1} : ShapeLimit{5, 1};
-    // (round 5: eks on the d = 4 chirp models beyond 24 trials per SIMD runs one lane per trial in the kernel of cgp_lane4.hpp -- 1.21 against
-    // 1.48 ms at 32 768 x 500, 8.0 against 10.6 ms at 262 144 x 500, the walk ahead below: 0.70 against 0.93 ms at 16 384;
-    // profiles/r05_lane_smoothers.txt.  cd_eks: 1.74 against 2.48 ms at 4096 x 500)
-    if (coop_walk && method == CGP_S_EKS && spec && model->n_harm == 1 && (model->model_id == CGP_M_HARMONIC_LCD || model->model_id == CGP_M_LASCALA_LCD) &&
-        lane4_smoother_fits(io) && !(flags & CGP_SEQUENTIAL_SCAN)) limit = {24, 1};
-    else if (method == CGP_S_CD_SGP && sde4) limit = {48, 1};
-    const bool wave = choose_wave(ctx, B, flags, limit, sig ? sigma : nullptr);
-    hipStream_t st = (hipStream_t)stream;
     // which kernel takes the launch -- decided before anything is enqueued, because only some of them write the selected outputs themselves
-    enum Route { kCoop8Linear, kWalk4Linear, kDiscLinear, kCoop8Harm, kWalk4Harm, kLane4, kDiscHarm, kSdeLinear, kCoop4CdSgp, kCoop4CdEks, kSdeHarm, kNone };
-    Route route = kNone;
-    switch (model->model_id) {
-    case CGP_M_LINEAR:
-        // 5 <= d <= 8, one wavefront per trial: maps built per lane, applied cooperatively in the tile layout (cgp_coop8.hpp)
-        if (affine && wave && !(flags & CGP_GENERIC_KERNEL) && coop8_smoother_ok(model->d, T, ma)) route = kCoop8Linear;
-        // d = 4: gains per lane, the recursion walked on the matrix cores (cgp_walk4.hpp)
-        else if (affine && wave && !(flags & CGP_GENERIC_KERNEL) && model->d == 4 && walk4_smoother_fits(T, ma)) route = kWalk4Linear;
-        else route = kDiscLinear;
-        break;
-    case CGP_M_HARMONIC_LCD:
-    case CGP_M_LASCALA_LCD:
-        if (affine && wave && !(flags & CGP_GENERIC_KERNEL) && model->n_harm >= 2 && coop8_smoother_ok(model->d, T, ma) && coop8_smoother_harm_ok(method, ma)) route = kCoop8Harm;
-        else if (affine && wave && !(flags & CGP_GENERIC_KERNEL) && model->n_harm == 1 && walk4_smoother_fits(T, ma)) route = kWalk4Harm;
-        else if (method == CGP_S_EKS && model->n_harm == 1 && !wave && !(flags & CGP_GENERIC_KERNEL) && lane4_smoother_fits(io)) route = kLane4;      // one lane per trial: cgp_lane4.hpp
-        else route = kDiscHarm;
-        break;
-    case CGP_M_LINEAR_SDE:   route = kSdeLinear; break;
-    case CGP_M_HARMONIC_SDE:
-        if (method == CGP_S_CD_SGP && model->n_harm == 1 && wave && !(flags & CGP_GENERIC_KERNEL)) route = kCoop4CdSgp;
-        else if (method == CGP_S_CD_EKS && model->n_harm == 1 && wave && !(flags & CGP_GENERIC_KERNEL)) route = kCoop4CdEks;
-        else if (method == CGP_S_CD_EKS && model->n_harm == 1 && !wave && !(flags & CGP_GENERIC_KERNEL) && lane4_smoother_fits(io)) route = kLane4;   // one lane per trial: cgp_lane4.hpp
-        else route = kSdeHarm;
-        break;
-    default: break;
-    }
-    // selected outputs (cgp_smoother_select): written by the kernel itself where it is one of the d = 4 walks / lane kernels or the tile-layout
-    // kernels (mss / Pss then optional); any other kernel writes the full rows and a gather launch reads the marginal back out of them
-    const bool sel_native = route == kWalk4Linear || route == kWalk4Harm || route == kLane4 || route == kCoop8Linear || route == kCoop8Harm;
+    const SmootherDecision decided = route_smoother({method, model, sigma, &io, &ma, flags, ctx->num_cus});
+    const SmootherRoute route = decided.route;
+    const bool wave = decided.wave;
+    hipStream_t st = (hipStream_t)stream;
+    const bool sel_native = writes_selection(route);
     if (want_sel) {
         if (sel_native) {
             io.sel.comp = out->comp; io.sel.func = out->func; io.sel.order = out->order;
@@ -587,9 +476,7 @@ static int smoother_impl(cgp_ctx* ctx, int method, const cgp_model* model, const
         if (burn_in < 0) return fail(ctx, CGP_E_ARG, "burn_in must be >= 0");
         if (!junction_err) return fail(ctx, CGP_E_ARG, "junction_err must be set: a time-split smoother is only as good as its junctions");
         if (want_sel) return fail(ctx, CGP_E_UNSUPPORTED, "cgp_smoother_time_split writes full rows only");
-        const bool split_sgp = route == kCoop4CdSgp && !(flags & CGP_DPP_KERNEL) && sigma_mfma_taken(flags, T, ma);
-        const bool split_eks = route == kCoop4CdEks && !(flags & CGP_DPP_KERNEL) && T * 128 <= 0x7FFFFF00LL;        // cgp_inst_coop4.hip: the matrix-core kernel
-        if (!split_sgp && !split_eks)
+        if (!knows_segments(route))
             return fail(ctx, CGP_E_UNSUPPORTED, "time-split smoothers with burn-in are built for cd_eks and cd_sgp_smoother on the d = 4 chirp / La Scala SDE (matrix-core "
                                                 "kernels; standard sigma set); the discrete smoothers split exactly (CGP_TIME_SPLIT)");
         const int64_t chunks = (T - 1 + 63) / 64;
@@ -604,18 +491,20 @@ static int smoother_impl(cgp_ctx* ctx, int method, const cgp_model* model, const
         }
     }
     switch (route) {
-    case kCoop8Linear: rc = dispatch_smoother_coop8_linear(method, model->d, io, ma, st); break;
-    case kWalk4Linear: rc = dispatch_smoother_walk4_linear(method, io, ma, st); break;
-    case kDiscLinear:  rc = dispatch_smoother_disc_linear(method, model->d, wave, io, ma, st); break;
-    case kCoop8Harm:   rc = dispatch_smoother_coop8_harm(method, model->n_harm, io, ma, st); break;
-    case kWalk4Harm:   rc = dispatch_smoother_walk4_harm(method, io, ma, st); break;
-    case kLane4:       rc = dispatch_smoother_lane4(method, model->model_id, io, ma, st); break;
-    case kDiscHarm:    rc = dispatch_smoother_disc_harm(method, model->n_harm, wave, io, ma, st); break;
-    case kSdeLinear:   rc = dispatch_smoother_sde_linear(method, model->d, wave, io, ma, st); break;
-    case kCoop4CdSgp:  rc = dispatch_smoother_coop4_cdsgp(io, ma, st); break;
-    case kCoop4CdEks:  rc = dispatch_smoother_coop4_cdeks(io, ma, st); break;
-    case kSdeHarm:     rc = dispatch_smoother_sde_harm(method, model->n_harm, wave, io, ma, st); break;
-    default: rc = CGP_E_ARG;
+    case SmootherRoute::kCoop8Linear: rc = dispatch_smoother_coop8_linear(method, model->d, io, ma, st); break;
+    case SmootherRoute::kWalk4Linear: rc = dispatch_smoother_walk4_linear(method, io, ma, st); break;
+    case SmootherRoute::kDiscLinear:  rc = dispatch_smoother_disc_linear(method, model->d, wave, io, ma, st); break;
+    case SmootherRoute::kCoop8Harm:   rc = dispatch_smoother_coop8_harm(method, model->n_harm, io, ma, st); break;
+    case SmootherRoute::kWalk4Harm:   rc = dispatch_smoother_walk4_harm(method, io, ma, st); break;
+    case SmootherRoute::kLane4:       rc = dispatch_smoother_lane4(method, model->model_id, io, ma, st); break;
+    case SmootherRoute::kDiscHarm:    rc = dispatch_smoother_disc_harm(method, model->n_harm, wave, io, ma, st); break;
+    case SmootherRoute::kSdeLinear:   rc = dispatch_smoother_sde_linear(method, model->d, wave, io, ma, st); break;
+    case SmootherRoute::kCdSgp4Mfma:  rc = dispatch_smoother_mfma4_cdsgp(io, ma, st); break;
+    case SmootherRoute::kCdSgp4Coop:  rc = dispatch_smoother_coop4_cdsgp(io, ma, st); break;
+    case SmootherRoute::kCdEks4Mfma:  rc = dispatch_smoother_mfma4_cdeks(io, ma, st); break;
+    case SmootherRoute::kCdEks4Coop:  rc = dispatch_smoother_coop4_cdeks(io, ma, st); break;
+    case SmootherRoute::kSdeHarm:     rc = dispatch_smoother_sde_harm(method, model->n_harm, wave, io, ma, st); break;
+    case SmootherRoute::kNone:        rc = CGP_E_ARG; break;
     }
     if (rc == CGP_OK && junction_err) {
         if (io.bsegs > 1) {

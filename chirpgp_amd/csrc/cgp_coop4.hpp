@@ -130,7 +130,6 @@ struct OobWindow {
         __builtin_amdgcn_raw_buffer_store_b128(d, rsrc, (int)off, 0, 0);
     }
 };
-constexpr int64_t kOobMaxBytes = 0x7FFFFF00;
 
 // NLL of up to 64 latched steps: every lane evaluates its increment, inclusive prefix sum across the wave, one
 // coalesced store; returns the new running total (wave-uniform).

@@ -632,11 +632,7 @@ __global__ void __launch_bounds__(64) cdsgps4_coop_kernel(SmootherIO io, ModelAr
     }
 }
 
-// The collapsed quadrature needs the caller's CGP_SIGMA_STANDARD assertion, groups, and one group per lane of a half wave.
-inline bool collapsed_ok(const ModelArgs& ma) {
-    return (ma.sg.flags & CGP_SIGMA_STANDARD) && ma.sg.group_start && ma.sg.n_groups >= 1 && ma.sg.n_groups <= 32;
-}
-
+// (the collapsed quadrature where the set allows it: collapsed_ok, cgp_route.hpp)
 template <class DM>
 inline int launch_sgp4_coop(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;

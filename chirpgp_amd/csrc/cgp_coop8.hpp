@@ -437,21 +437,15 @@ __global__ void __launch_bounds__(64) ekf8_coop_kernel(FilterIO io, ModelArgs ma
 template <int NH>
 inline int launch_ekf8_coop(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
-    if (io.T * ((2 * NH + 2) * (2 * NH + 2) * 8) > kOobMaxBytes) return CGP_E_UNSUPPORTED;        // output windows (OobWindow)
+    if (!coop8_rows_fit(2 * NH + 2, io.T)) return CGP_E_UNSUPPORTED;        // output windows (OobWindow)
     hipLaunchKernelGGL((ekf8_coop_kernel<NH>), dim3((unsigned)io.B), dim3(64), 0, stream, io, ma);
     return hip_rc(hipGetLastError());
-}
-
-// The collapsed quadrature of the kernel above needs the caller's CGP_SIGMA_STANDARD assertion, groups, and at most one
-// group per (DPP row, block) pair.
-inline bool coop8_sigma_ok(const ModelArgs& ma) {
-    return (ma.sg.flags & CGP_SIGMA_STANDARD) && ma.sg.group_start && ma.sg.n_groups >= 1 && ma.sg.n_groups <= 16;
 }
 
 template <int NH>
 inline int launch_sgp8_coop(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
-    if (io.T * ((2 * NH + 2) * (2 * NH + 2) * 8) > kOobMaxBytes) return CGP_E_UNSUPPORTED;        // output windows (OobWindow)
+    if (!coop8_rows_fit(2 * NH + 2, io.T)) return CGP_E_UNSUPPORTED;        // output windows (OobWindow)
     const bool axial = (ma.sg.flags & CGP_SIGMA_AXIAL) != 0;
     const size_t lds = sigma_lds_bytes(ma, 2 * NH + 2);
     if (io.segs > 1) {                                                              // time-split: one wavefront per (trial, segment)
@@ -516,6 +510,7 @@ inline int walk_segments(const SmootherIO& io, int blocks_per_cu) {
 // ---- one wavefront per trial: records (G, Pp, mp) in quarters of 16, the tile's filtering rows (Pf, mf) parked beside them
 constexpr int kRowDoubles = 45;                   // Pf (packed lower, 36) | mf (8) | one zero; odd: conflict-free lane stride
 constexpr int kRowmf = 36, kRowZero = 44;
+static_assert(kCoop8SmootherLdsBytes == sizeof(double) * (16 * kElemDoubles + 64 * kRowDoubles), "coop8_smoother_ok (cgp_route.hpp) budgets the records and rows of coop8_smoother_kernel");
 struct Elem8WalkOperands { double gA0, gA1, gB0, gB1, gM, Ppv, mpc, Pfv, mfr; };
 
 // SEL (cgp_smoother_select): the lanes that hold the selected component's smoothed mean and variance leave them in LDS step by step;
@@ -799,10 +794,12 @@ __global__ void __launch_bounds__(64) coop8_split_kernel(SmootherIO io, ModelArg
     }
 }
 
-template <class Elem>
-inline hipError_t launch_coop8_smoother(const SmootherIO& io_in, const ModelArgs& ma, hipStream_t stream) {
-    if (io_in.B <= 0 || io_in.T <= 0) return hipSuccess;
-    if (io_in.T * Elem::D * Elem::D * 8 > kOobMaxBytes) return hipErrorInvalidValue;      // 2 GiB buffer windows (callers check coop8_smoother_ok)
+// The launcher of the cooperative walks (here and cgp_walk4.hpp): one wavefront per trial with kWhole, or the time-split form -- kCompose
+// leaves every segment's map (`map_doubles` each) in the context's per-stream workspace, kApply walks the segments.  The *Sel kernels
+// write the selected outputs (cgp_smoother_select) as well.
+using WalkKernel = void (*)(SmootherIO, ModelArgs);
+template <class Elem, WalkKernel kWhole, WalkKernel kWholeSel, WalkKernel kCompose, WalkKernel kApply, WalkKernel kApplySel>
+inline hipError_t launch_walk_smoother(const SmootherIO& io_in, const ModelArgs& ma, hipStream_t stream, int map_doubles) {
     const size_t dyn = Elem::USES_SIGMA ? sigma_lds_bytes(ma, Elem::D) : 0;
     // workgroups of the split kernel a CU holds (registers, LDS): asked once per kernel and dynamic-LDS size, then remembered
     static std::atomic<long long> occ_cache{-1};                           // (dyn << 8) | per_cu
@@ -811,15 +808,15 @@ inline hipError_t launch_coop8_smoother(const SmootherIO& io_in, const ModelArgs
         const long long seen = occ_cache.load(std::memory_order_relaxed);
         if (seen >= 0 && (size_t)(seen >> 8) == dyn) per_cu = (int)(seen & 0xFF);
         else {
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, coop8_split_kernel<Elem, kWalkApply>, 64, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 4; }
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kApply, 64, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 4; }
             occ_cache.store(((long long)dyn << 8) | (per_cu & 0xFF), std::memory_order_relaxed);
         }
     }
     const int segs = walk_segments(io_in, per_cu);
     const bool sel = io_in.sel.comp >= 0;
+    const WalkKernel whole_kernel = sel ? kWholeSel : kWhole, apply_kernel = sel ? kApplySel : kApply;
     auto whole = [&]() {
-        if (sel) hipLaunchKernelGGL((coop8_smoother_kernel<Elem, true>), dim3((unsigned)io_in.B), dim3(64), dyn, stream, io_in, ma);
-        else hipLaunchKernelGGL((coop8_smoother_kernel<Elem>), dim3((unsigned)io_in.B), dim3(64), dyn, stream, io_in, ma);
+        hipLaunchKernelGGL(whole_kernel, dim3((unsigned)io_in.B), dim3(64), dyn, stream, io_in, ma);
         return hipGetLastError();
     };
     if (segs <= 1) return whole();
@@ -829,16 +826,21 @@ inline hipError_t launch_coop8_smoother(const SmootherIO& io_in, const ModelArgs
     const int64_t tiles = (io.T - 1 + 63) / 64;
     io.tiles_per_seg = (int)((tiles + io.segs - 1) / io.segs);
     io.segs = (int)((tiles + io.tiles_per_seg - 1) / io.tiles_per_seg);           // no empty segments
-    void* ws = ctx_workspace(io.host_ctx, stream, sizeof(double) * kMap8Doubles * (size_t)io.B * io.segs);
-    hipError_t e;
+    void* ws = ctx_workspace(io.host_ctx, stream, sizeof(double) * map_doubles * (size_t)io.B * io.segs);
     if (!ws) return whole();             // no workspace (allocation failed, pinned too small, growth inside a graph capture): the one-wave-per-trial form needs none
     io.ws = (double*)ws;
     const unsigned grid = (unsigned)(io.B * io.segs);
-    hipLaunchKernelGGL((coop8_split_kernel<Elem, kWalkCompose>), dim3(grid), dim3(64), dyn, stream, io, ma);
-    if (sel) hipLaunchKernelGGL((coop8_split_kernel<Elem, kWalkApply, true>), dim3(grid), dim3(64), dyn, stream, io, ma);
-    else hipLaunchKernelGGL((coop8_split_kernel<Elem, kWalkApply>), dim3(grid), dim3(64), dyn, stream, io, ma);
-    e = hipGetLastError();
-    return e;
+    hipLaunchKernelGGL(kCompose, dim3(grid), dim3(64), dyn, stream, io, ma);
+    hipLaunchKernelGGL(apply_kernel, dim3(grid), dim3(64), dyn, stream, io, ma);
+    return hipGetLastError();
+}
+
+template <class Elem>
+inline hipError_t launch_coop8_smoother(const SmootherIO& io, const ModelArgs& ma, hipStream_t stream) {
+    if (io.B <= 0 || io.T <= 0) return hipSuccess;
+    if (!coop8_smoother_ok(Elem::D, io.T, ma)) return hipErrorInvalidValue;      // 2 GiB buffer windows, LDS
+    return launch_walk_smoother<Elem, coop8_smoother_kernel<Elem, false>, coop8_smoother_kernel<Elem, true>, coop8_split_kernel<Elem, kWalkCompose, false>,
+                                coop8_split_kernel<Elem, kWalkApply, false>, coop8_split_kernel<Elem, kWalkApply, true>>(io, ma, stream, kMap8Doubles);
 }
 
 }  // namespace cgp

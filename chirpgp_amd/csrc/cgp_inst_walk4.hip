@@ -4,7 +4,6 @@
 #include "cgp_walk4.hpp"
 #include "cgp_dispatch.hpp"
 namespace cgp {
-bool walk4_smoother_fits(int64_t T, const ModelArgs& ma) { return walk4_smoother_ok(T, ma); }
 int dispatch_smoother_walk4_linear(int method, const SmootherIO& io, const ModelArgs& ma, hipStream_t st) {
     if (method == CGP_S_EKS) return hip_rc(launch_walk4_smoother<EksElement<LinearDisc<4>>>(io, ma, st));
     if (method == CGP_S_SGP) return hip_rc(launch_walk4_smoother<SgpsElement<LinearDisc<4>>>(io, ma, st));

@@ -712,59 +712,45 @@ inline hipError_t launch_smoother(const SmootherIO& io, const ModelArgs& ma, hip
     return hipGetLastError();
 }
 
-// Dispatch tables implemented one per translation unit (cgp_inst_*.hip) so that they compile in parallel.
-// `key` is d for the linear models and n_harm for the harmonic / KPT ones.  Return CGP_E_UNSUPPORTED if the
-// combination is not compiled in, CGP_E_HIP on a launch error.
+// Dispatch tables implemented one per translation unit (cgp_inst_*.hip) so that they compile in parallel: one entry per kernel family
+// of cgp_route.hpp, which decides among them.  `key` is d for the linear models and n_harm for the harmonic / KPT ones.  Return
+// CGP_E_UNSUPPORTED if the combination is not compiled in (or the launcher's guard refuses it), CGP_E_HIP on a launch error.
 int dispatch_filter_disc_linear(int method, int key, bool wave, const FilterIO&, const ModelArgs&, hipStream_t);
-int dispatch_filter_kf4_mfma(const FilterIO&, const ModelArgs&, hipStream_t);      // kf at d = 4 on the matrix cores (cgp_mfma4.hpp)
 int dispatch_filter_disc_harm(int method, int key, bool wave, const FilterIO&, const ModelArgs&, hipStream_t);
 int dispatch_filter_sde_linear(int method, int key, bool wave, const FilterIO&, const ModelArgs&, hipStream_t);
 int dispatch_filter_sde_harm(int method, int key, bool wave, const FilterIO&, const ModelArgs&, hipStream_t);
 int dispatch_filter_kpt(int key, bool wave, const FilterIO&, const ModelArgs&, hipStream_t);
-int dispatch_filter_coop4(const FilterIO&, const ModelArgs&, hipStream_t);
-int dispatch_filter_mfma4(const FilterIO&, const ModelArgs&, hipStream_t);
+int dispatch_filter_kpt8(int key, const FilterIO&, const ModelArgs&, hipStream_t);       // the tile-layout / matrix-core kernels (cgp_kpt8.hpp)
+int dispatch_filter_kf4_mfma(const FilterIO&, const ModelArgs&, hipStream_t);            // kf at d = 4 on the matrix cores (cgp_mfma4.hpp)
+int dispatch_filter_mfma4(const FilterIO&, const ModelArgs&, hipStream_t);               // ekf, d = 4: one trial or one segment per wavefront
+int launch_ekf4_mfma_x4(const FilterIO&, const ModelArgs&, hipStream_t);                 // ... four trials per wavefront
+int dispatch_filter_coop4(const FilterIO&, const ModelArgs&, hipStream_t);               // ... on DPP rows (cgp_coop4.hpp)
 int dispatch_filter_mfma4_sgp(const FilterIO&, const ModelArgs&, hipStream_t);
-int dispatch_filter_mfma4_cdsgp(const FilterIO&, const ModelArgs&, hipStream_t);
-int dispatch_smoother_mfma4_cdsgp(const SmootherIO&, const ModelArgs&, hipStream_t);
-int dispatch_filter_mfma4_cdekf(const FilterIO&, const ModelArgs&, hipStream_t);
-int dispatch_smoother_mfma4_cdeks(const SmootherIO&, const ModelArgs&, hipStream_t);
-// the matrix-core EKF addresses a trial's outputs through 2 GiB buffer windows (cgp_mfma4.hpp)
-inline bool ekf4_mfma_fits(const FilterIO& io) { return io.T * 128 <= 0x7FFFFF00ll; }
 int dispatch_filter_coop4_sgp(const FilterIO&, const ModelArgs&, hipStream_t);
-// d = 4, one lane per trial, large batches (cgp_lane4.hpp).  The launches it takes: dense or shared records whose rows start on
-// 16-byte boundaries (its LDS-DMA moves 16-byte pieces), an even number of steps, output windows of 64 trials within the 2 GiB a
-// raw buffer addresses, no time-split segments.
-inline bool lane4_filter_fits(const FilterIO& io) {
-    return io.segs <= 1 && io.T >= 2 && io.T % 2 == 0 && io.ys_stride % 2 == 0 && ((uintptr_t)io.ys & 15) == 0 && io.T * 128 * 64 <= 0x7FFFFF00ll;
-}
-int dispatch_filter_lane4(int method, const FilterIO&, const ModelArgs&, hipStream_t);
-// ... and its smoothers (eks on the chirp / La Scala LCD models, cd_eks on the chirp SDE): 16-byte aligned inputs (LDS-DMA), output windows
-// of 64 trials within 2 GiB
-inline bool lane4_smoother_fits(const SmootherIO& io) {
-    return io.T >= 2 && io.T * 128 * 64 <= 0x7FFFFF00ll && ((uintptr_t)io.mfs & 15) == 0 && ((uintptr_t)io.Pfs & 15) == 0;
-}
-int dispatch_smoother_lane4(int method, int model_id, const SmootherIO&, const ModelArgs&, hipStream_t);
-// d = 6 / 8 harmonic models in the 8 x 8 tile layout (cgp_coop8.hpp)
-bool coop8_filter_sgp_ok(int n_harm, int64_t T, const ModelArgs&);
-bool walk4_smoother_fits(int64_t T, const ModelArgs&);
-int dispatch_smoother_walk4_linear(int method, const SmootherIO&, const ModelArgs&, hipStream_t);
-int dispatch_smoother_walk4_harm(int method, const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_filter_lane4(int method, const FilterIO&, const ModelArgs&, hipStream_t);   // d = 4, one lane per trial, large batches (cgp_lane4.hpp)
+int dispatch_filter_coop8_ekf(int n_harm, const FilterIO&, const ModelArgs&, hipStream_t);      // d = 6 / 8 in the 8 x 8 tile layout (cgp_coop8.hpp)
 int dispatch_filter_coop8_sgp(int n_harm, const FilterIO&, const ModelArgs&, hipStream_t);
-int dispatch_filter_coop8_ekf(int n_harm, const FilterIO&, const ModelArgs&, hipStream_t);
-bool coop8_smoother_ok(int d, int64_t T, const ModelArgs&);
-bool coop8_smoother_harm_ok(int method, const ModelArgs&);
-int dispatch_smoother_coop8_linear(int method, int d, const SmootherIO&, const ModelArgs&, hipStream_t);
-int dispatch_smoother_coop8_harm(int method, int n_harm, const SmootherIO&, const ModelArgs&, hipStream_t);
-int dispatch_filter_coop4_cdsgp(const FilterIO&, const ModelArgs&, hipStream_t);
-int dispatch_smoother_coop4_cdsgp(const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_filter_mfma4_cdekf(const FilterIO&, const ModelArgs&, hipStream_t);
 int dispatch_filter_coop4_cdekf(const FilterIO&, const ModelArgs&, hipStream_t);
-int dispatch_smoother_coop4_cdeks(const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_filter_mfma4_cdsgp(const FilterIO&, const ModelArgs&, hipStream_t);
+int dispatch_filter_coop4_cdsgp(const FilterIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_disc_linear(int method, int key, bool wave, const SmootherIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_disc_harm(int method, int key, bool wave, const SmootherIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_sde_linear(int method, int key, bool wave, const SmootherIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_sde_harm(int method, int key, bool wave, const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_walk4_linear(int method, const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_walk4_harm(int method, const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_coop8_linear(int method, int d, const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_coop8_harm(int method, int n_harm, const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_lane4(int method, int model_id, const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_mfma4_cdsgp(const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_coop4_cdsgp(const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_mfma4_cdeks(const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_coop4_cdeks(const SmootherIO&, const ModelArgs&, hipStream_t);
 
 inline int hip_rc(hipError_t e) { return e == hipSuccess ? CGP_OK : CGP_E_HIP; }
 #endif                         // __HIPCC_RTC__
 
 }  // namespace cgp
+
+#include "cgp_route.hpp"       // which of them a call runs, and the admission predicates their launchers guard with

@@ -207,7 +207,7 @@ __global__ void __launch_bounds__(64) kpt4_mfma_kernel(FilterIO io, ModelArgs ma
 template <int NH>
 inline int launch_kpt8_coop(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
-    if (io.T * ((NH + 2) * (NH + 2) * 8) > kOobMaxBytes) return CGP_E_UNSUPPORTED;               // output windows (OobWindow)
+    if (!kpt8_fits(NH, io.T)) return CGP_E_UNSUPPORTED;               // output windows (OobWindow)
     if constexpr (NH <= 2) hipLaunchKernelGGL(kpt4_mfma_kernel<NH>, dim3((unsigned)io.B), dim3(64), 0, stream, io, ma);
     else hipLaunchKernelGGL(kpt8_coop_kernel<NH>, dim3((unsigned)io.B), dim3(64), 0, stream, io, ma);
     return hip_rc(hipGetLastError());

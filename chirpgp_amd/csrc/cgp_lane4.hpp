@@ -317,6 +317,7 @@ inline int lane4_period(int64_t T) {
 template <class Pred, class Meas>
 inline hipError_t launch_lane4_filter(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return hipSuccess;
+    if (!lane4_filter_fits(io)) return hipErrorInvalidValue;
     const int period = lane4_period(io.T);
     const int64_t groups = (io.B + 64 * period - 1) / (64 * period);
     const size_t dyn = Pred::USES_SIGMA ? sigma_lds_bytes(ma, Pred::D) : 0;
@@ -580,6 +581,7 @@ inline int lane4_smoother_period(int64_t T) {
 template <class Step>
 inline hipError_t launch_lane4_smoother(const SmootherIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return hipSuccess;
+    if (!lane4_smoother_fits(io)) return hipErrorInvalidValue;
     // covariance rows requested one step ahead (default) or, cgp_debug_set(CGP_DBG_LANE_BUFFERS, 3), two: measured at 262 144 x 500 on MI355X, no
     // gain -- full rows 8.2 -> 8.2 ms, the marginal alone 4.91 -> 4.86, E[g] alone 8.95 -> 8.85: the prefetch depth is not what limits the kernel
     const bool three = io.lane_buffers == 3;

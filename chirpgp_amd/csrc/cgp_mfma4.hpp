@@ -734,7 +734,7 @@ __global__ void __launch_bounds__(64) kf4_mfma_kernel(FilterIO io, ModelArgs ma)
 }
 inline int launch_kf4_mfma(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
-    if (io.T * 128 > kOobMaxBytes) return CGP_E_UNSUPPORTED;
+    if (!mfma4_rows_fit(io.T)) return CGP_E_UNSUPPORTED;
     hipLaunchKernelGGL(kf4_mfma_kernel, dim3((unsigned)io.B), dim3(64), 0, stream, io, ma);
     return hip_rc(hipGetLastError());
 }
@@ -753,8 +753,7 @@ __global__ void __launch_bounds__(64) ekf4_mfma_kernel(FilterIO io, ModelArgs ma
 
 // (round 5) the four-trials-per-wavefront kernel lives in a translation unit of its own (cgp_inst_ekf4_x4.hip): the one-trial kernel's
 // unit is compiled without machine-level loop-invariant code motion (Makefile), which costs this one 14 %
-inline bool ekf4_mfma_x4_fits(const FilterIO& io) { return io.T * 512 <= kOobMaxBytes; }
-int launch_ekf4_mfma_x4(const FilterIO& io, const ModelArgs& ma, hipStream_t stream);
+// (launch_ekf4_mfma_x4, declared in cgp_kernels.hpp)
 
 #ifdef CGP_EKF4_X4_KERNELS
 // ---------------------------------------------------------------------------------------------- four trials per wave
@@ -895,6 +894,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, DENS
 
 // 4 T x 128 bytes of covariance rows must fit the 2 GiB window of a wave
 inline int launch_ekf4_mfma_x4_impl(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
+    if (io.B <= 0 || io.T <= 0) return CGP_OK;
+    if (!ekf4_mfma_x4_fits(io)) return CGP_E_UNSUPPORTED;
     if (io.B > 4096) hipLaunchKernelGGL(ekf4_mfma_x4_kernel<true>, dim3((unsigned)((io.B + 3) / 4)), dim3(64), 0, stream, io, ma);
     else hipLaunchKernelGGL(ekf4_mfma_x4_kernel<false>, dim3((unsigned)((io.B + 3) / 4)), dim3(64), 0, stream, io, ma);
     return hip_rc(hipGetLastError());
@@ -905,15 +906,10 @@ inline int launch_ekf4_mfma_x4_impl(const FilterIO& io, const ModelArgs& ma, hip
 inline int launch_ekf4_mfma(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
     // the kernels address a trial's covariance rows through a 32-bit byte offset into a 2 GiB buffer window: a record too
-    // long for it is refused HERE, next to the kernels that need it (the dispatcher routes such records to the DPP kernel)
-    if (io.T * 128 > kOobMaxBytes) return CGP_E_UNSUPPORTED;
-    // beyond one wave per SIMD the four MFMA blocks carry four trials (CGP_ONE_TRIAL_PER_WAVE keeps one, for tests)
-    if (io.segs > 1)           // time-split with burn-in: one wavefront per (trial, segment)
-        hipLaunchKernelGGL(ekf4_mfma_kernel, dim3((unsigned)(io.B * io.segs)), dim3(64), 0, stream, io, ma);
-    else if ((io.B > 1024 || (io.flags & CGP_FOUR_TRIALS_PER_WAVE)) && ekf4_mfma_x4_fits(io) && !(io.flags & CGP_ONE_TRIAL_PER_WAVE))
-        return launch_ekf4_mfma_x4(io, ma, stream);
-    else
-        hipLaunchKernelGGL(ekf4_mfma_kernel, dim3((unsigned)io.B), dim3(64), 0, stream, io, ma);
+    // long for it is refused HERE, next to the kernels that need it (cgp_route.hpp sends such records to the DPP kernel)
+    if (!ekf4_mfma_fits(io)) return CGP_E_UNSUPPORTED;
+    // one wavefront per trial or, time-split with burn-in, per (trial, segment)
+    hipLaunchKernelGGL(ekf4_mfma_kernel, dim3((unsigned)(io.B * (io.segs > 1 ? io.segs : 1))), dim3(64), 0, stream, io, ma);
     return hip_rc(hipGetLastError());
 }
 

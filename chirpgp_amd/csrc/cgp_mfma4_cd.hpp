@@ -406,13 +406,13 @@ __global__ void __launch_bounds__(64) cdeks4_mfma_kernel(SmootherIO io, ModelArg
 
 inline int launch_cdekf4_mfma(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
-    if (io.T * 128 > kOobMaxBytes) return CGP_E_UNSUPPORTED;
+    if (!mfma4_rows_fit(io.T)) return CGP_E_UNSUPPORTED;
     hipLaunchKernelGGL(cdekf4_mfma_kernel, dim3((unsigned)io.B), dim3(64), 0, stream, io, ma);
     return hip_rc(hipGetLastError());
 }
 inline int launch_cdeks4_mfma(const SmootherIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
-    if (io.T * 128 > kOobMaxBytes) return CGP_E_UNSUPPORTED;
+    if (!mfma4_rows_fit(io.T)) return CGP_E_UNSUPPORTED;
     if (io.bsegs > 1) {
         if (io.B * io.bsegs > 0x7fffffffLL) return CGP_E_UNSUPPORTED;
         hipLaunchKernelGGL(cdeks4_mfma_kernel<true>, dim3((unsigned)(io.B * io.bsegs)), dim3(64), 0, stream, io, ma);
@@ -426,7 +426,7 @@ inline int launch_cdeks4_mfma(const SmootherIO& io, const ModelArgs& ma, hipStre
 template <class SM>
 inline int launch_cdsgp4_mfma(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
-    if (!sgp4_mfma_fits(io, ma)) return CGP_E_UNSUPPORTED;
+    if (!sgp4_mfma_fits(io.T, ma)) return CGP_E_UNSUPPORTED;
     const bool two = ma.sg.n_groups > 16;
     if (io.segs > 1) {                                                              // time-split: one wavefront per (trial, segment)
         const unsigned grid = (unsigned)(io.B * io.segs);
@@ -439,7 +439,7 @@ inline int launch_cdsgp4_mfma(const FilterIO& io, const ModelArgs& ma, hipStream
 template <class SM>
 inline int launch_cdsgps4_mfma(const SmootherIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
-    if (!collapsed_ok(ma) || io.T * 128 > kOobMaxBytes) return CGP_E_UNSUPPORTED;
+    if (!sgp4_mfma_fits(io.T, ma)) return CGP_E_UNSUPPORTED;
     if (io.bsegs > 1) {                                                             // time-split with burn-in: one wavefront per (trial, segment)
         const unsigned grid = (unsigned)(io.B * io.bsegs);
         if (ma.sg.n_groups > 16) hipLaunchKernelGGL((cdsgps4_mfma_kernel<SM, true, true>), dim3(grid), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);

@@ -259,13 +259,10 @@ __global__ void __launch_bounds__(64) sgp4_mfma_kernel(FilterIO io, ModelArgs ma
 }
 
 // The matrix-core kernel takes collapsible sets of at most 32 groups whose output windows fit a raw buffer.
-inline bool sgp4_mfma_fits(const FilterIO& io, const ModelArgs& ma) {
-    return collapsed_ok(ma) && io.T * 128 <= kOobMaxBytes;
-}
 template <class DM>
 inline int launch_sgp4_mfma(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
-    if (!sgp4_mfma_fits(io, ma)) return CGP_E_UNSUPPORTED;
+    if (!sgp4_mfma_fits(io.T, ma)) return CGP_E_UNSUPPORTED;
     const bool two = ma.sg.n_groups > 16;
     if (io.segs > 1) {                                                              // time-split: one wavefront per (trial, segment)
         const unsigned grid = (unsigned)(io.B * io.segs);

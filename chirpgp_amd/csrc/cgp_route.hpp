@@ -1,0 +1,341 @@
+// cgp_route.hpp -- which kernel a cgp_filter / cgp_smoother call runs.  Host code without a HIP call or a device access: the C-ABI
+// (cgp_api.hip) asks route_filter / route_smoother before it enqueues anything, and a host program can ask them too
+// (tests/route_probe.hip).  Each kernel's admission predicate is stated once, here, and serves the route functions and the guard of
+// the kernel's launcher alike.  Included by cgp_kernels.hpp, behind the types it needs.
+#pragma once
+#include "cgp_kernels.hpp"
+#ifndef __HIPCC_RTC__          // host code (the run-time-compiled models include these headers)
+
+namespace cgp {
+
+// ---- admission: what each specialised kernel can address -------------------------------------------------------------------------
+// Outputs leave through raw-buffer windows (cgp_coop4.hpp: OobWindow) of at most 2 GiB less the last line: whatever one workgroup
+// addresses through one window -- `bytes_per_step` for each of T steps -- has to fit.
+constexpr int64_t kOobMaxBytes = 0x7FFFFF00;
+inline bool oob_fits(int64_t T, int64_t bytes_per_step) { return T * bytes_per_step <= kOobMaxBytes; }
+
+// d = 4 on the matrix cores (cgp_mfma4*.hpp): one trial's covariance rows a window, four trials' in the four-trials-per-wavefront EKF
+inline bool mfma4_rows_fit(int64_t T) { return oob_fits(T, 128); }
+inline bool ekf4_mfma_fits(const FilterIO& io) { return mfma4_rows_fit(io.T); }
+inline bool ekf4_mfma_x4_fits(const FilterIO& io) { return oob_fits(io.T, 512); }
+// The collapsed quadrature of the d = 4 sigma-point kernels needs the caller's CGP_SIGMA_STANDARD assertion, groups, and one group per
+// lane of a half wave; the matrix-core kernels (cgp_mfma4_sigma.hpp, cgp_mfma4_cd.hpp) are built for it alone.
+inline bool collapsed_ok(const ModelArgs& ma) {
+    return (ma.sg.flags & CGP_SIGMA_STANDARD) && ma.sg.group_start && ma.sg.n_groups >= 1 && ma.sg.n_groups <= 32;
+}
+inline bool sgp4_mfma_fits(int64_t T, const ModelArgs& ma) { return collapsed_ok(ma) && mfma4_rows_fit(T); }
+
+// d = 6 / 8 in the 8 x 8 tile layout (cgp_coop8.hpp) and ekf_for_kpt (cgp_kpt8.hpp): one trial's d x d rows a window.  The
+// sigma-point filter's collapsed quadrature: the standard-set assertion, groups, at most one group per (DPP row, block) pair.
+inline bool coop8_rows_fit(int d, int64_t T) { return oob_fits(T, (int64_t)d * d * 8); }
+inline bool coop8_sigma_ok(const ModelArgs& ma) {
+    return (ma.sg.flags & CGP_SIGMA_STANDARD) && ma.sg.group_start && ma.sg.n_groups >= 1 && ma.sg.n_groups <= 16;
+}
+inline bool coop8_filter_sgp_ok(int n_harm, int64_t T, const ModelArgs& ma) {
+    return (n_harm == 2 || n_harm == 3) && coop8_sigma_ok(ma) && coop8_rows_fit(2 * n_harm + 2, T);
+}
+inline bool kpt8_fits(int n_harm, int64_t T) { return coop8_rows_fit(n_harm + 2, T); }
+// The cooperative smoother keeps 16 step records and the tile's 64 filtering rows in 36.9 KB of static LDS (the split kernel:
+// 32 records, 27.9 KB); with the staged sigma-point set beside it a workgroup must stay within 40 KB so that four of them
+// (one per SIMD) share a CU's 160 KB (every cubature rule fits; larger sets take the lane-scan kernel).
+constexpr size_t kCoop8SmootherLdsBytes = sizeof(double) * (16 * 109 + 64 * 45);      // cgp_coop8.hpp: 16 kElemDoubles + 64 kRowDoubles
+inline bool coop8_smoother_ok(int d, int64_t T, const ModelArgs& ma) {
+    return d >= 5 && d <= 8 && coop8_rows_fit(d, T) && sigma_lds_bytes(ma, d) + kCoop8SmootherLdsBytes + 64 <= 40 * 1024;
+}
+// the sigma-point elements of the harmonic models are compiled in their collapsed form only: other sets take the lane-scan kernel
+inline bool coop8_smoother_harm_ok(int method, const ModelArgs& ma) {
+    return method == CGP_S_EKS || (method == CGP_S_SGP && (ma.sg.flags & CGP_SIGMA_STANDARD) && ma.sg.group_start);
+}
+// The d = 4 walk (cgp_walk4.hpp): one workgroup holds 64 records (18 944 B) beside the staged sigma-point set; at least four of them
+// have to share a CU's 160 KB.
+constexpr size_t kWalk4LdsBytes = sizeof(double) * 64 * 37;                             // cgp_walk4.hpp: 64 kWalkRec
+inline bool walk4_smoother_ok(int64_t T, const ModelArgs& ma) {
+    return mfma4_rows_fit(T) && sigma_lds_bytes(ma, 4) + kWalk4LdsBytes + 64 <= 40 * 1024;
+}
+
+// d = 4, one lane per trial, large batches (cgp_lane4.hpp).  The launches it takes: dense or shared records whose rows start on
+// 16-byte boundaries (its LDS-DMA moves 16-byte pieces), an even number of steps, output windows of 64 trials within the 2 GiB a
+// raw buffer addresses, no time-split segments ...
+inline bool lane4_filter_fits(const FilterIO& io) {
+    return io.segs <= 1 && io.T >= 2 && io.T % 2 == 0 && io.ys_stride % 2 == 0 && ((uintptr_t)io.ys & 15) == 0 && oob_fits(io.T, 128 * 64);
+}
+// ... for its sigma-point filter a set that fits beside the kernel's static LDS (cgp_steps.hpp) ...
+inline bool lane4_sgp_fits(const ModelArgs& ma) { return sigma_lds_bytes(ma, 4) <= (size_t)kLane4SigLdsMaxBytes; }
+// ... and its smoothers (eks on the chirp / La Scala LCD models, cd_eks on the chirp SDE): 16-byte aligned inputs (LDS-DMA), output
+// windows of 64 trials within 2 GiB
+inline bool lane4_smoother_fits(const SmootherIO& io) {
+    return io.T >= 2 && oob_fits(io.T, 128 * 64) && ((uintptr_t)io.mfs & 15) == 0 && ((uintptr_t)io.Pfs & 15) == 0;
+}
+
+// ---- launch shape ------------------------------------------------------------------------------------------------------------------
+// One wavefront per trial is the latency-optimal shape while the batch is about the number of
+// SIMDs (1024): a step then costs its dependent-instruction chain once.  One lane per trial costs more per step but
+// carries 64 trials per wave, so it wins as soon as enough wavefronts would have to share a SIMD -- how many depends on how
+// much faster the lane-cooperative (matrix-core) kernel's step is than the one-lane step.  Crossovers measured on MI355X in
+// round 3 (bench.py --batch B --flags 2 | 4; wave-per-trial time grows linearly with B beyond 1024, the lane-per-trial time is
+// flat until B ~ 64 K), in trials per SIMD:
+//     EKF, chirp / La Scala d = 4 (MFMA, four trials per wave above 1024)   1.25 ms vs 2.58 at 8 K, 2.29 vs 2.65 at 16 K, 3.33 vs 2.89 at 24 K   -> 20
+//     EKF, 2 / 3 harmonics d = 6 / 8 (tile layout)                          0.93 vs 1.81 at 4 K, 1.73 vs 1.82 at 8 K, 3.29 vs 1.88 at 16 K        -> 8
+//     sigma-point filter, d = 4 (MFMA sums)                                 1.38 vs 8.17 at 4 K, 5.12 vs 8.18 at 16 K, 6.2 vs 5.1 at 32 K         -> 24
+//     sigma-point filter, d = 6 / 8 (tile layout)                           2.52 vs 6.95 at 4 K, 9.58 vs 6.99 at 16 K                             -> 11
+//     cd_ekf / cd_eks, d = 4 (MFMA)                                         1.41 vs 1.38 / 1.38 vs 1.90 at 4 K, 4.95 vs 1.40 / 4.89 vs 2.07 at 16 K -> 4 / 5
+//     cd_sgp filter / smoother, d = 4 (MFMA)                                2.3 vs 28.6 at 4 K, 9.2 vs 28.7 at 16 K                               -> 48
+//     discrete smoothers on the cooperative walks (d = 4 .. 8)              never slower than one lane per trial: 0.36 vs 9.98 ms (sigma-point d = 4,
+//                                                                           4 K), 2.77 vs 18.4 (EKS d = 8, 16 K), 9.4 vs 10.6 (EKS d = 4, 256 K)   -> always
+//     everything on the generic kernels                                     as measured in round 1: 2.5 (EKF-type), 8 (sigma-point), 16 (affine scan)
+// Round 5, where the large-batch lane kernel of cgp_lane4.hpp is what one lane per trial runs: it wins from 9 / 9 trials per SIMD on
+// (tools/lane_crossover.sh, profiles/r05_lane_crossover.txt: EKF 0.49 against 0.59 ms at 8192 x 500 and 0.71 against 0.59 at 10 240 --
+// CRLB records, i.e. with the four-trials-per-wavefront kernel on its branch-free wide step --, GH-3 4.3 against 5.0 ms at 8192 x 500
+// and 6.5 against 5.0 at 12 288, after the lane kernel's fan stopped running twice on records outside the lean regime; the generic
+// lane kernel it replaces there kept the round-3 limits of 20 / 24).  Smoothers: eks on the d = 4 chirp models beyond 24 trials per
+// SIMD -- 1.21 against 1.48 ms at 32 768 x 500, 8.0 against 10.6 ms at 262 144 x 500, the walk ahead below: 0.70 against 0.93 ms at
+// 16 384; profiles/r05_lane_smoothers.txt -- and cd_eks from 3: 1.74 against 2.48 ms at 4096 x 500.
+struct ShapeLimit { int num, den; };                      // one wavefront per trial while B * den < num * SIMDs; num < 0: always
+constexpr ShapeLimit kWaveAlways{-1, 1};
+inline bool choose_wave(int num_cus, int64_t B, uint32_t flags, ShapeLimit limit, const cgp_sigma* sg) {
+    // the wave-per-trial shapes stage the sigma-point set in LDS; a set that does not fit runs one lane per trial
+    if (sg && SigmaSet::stage_bytes(sg->s, sg->d, sg->n_groups, sg->group_start != nullptr) > (size_t)kSigLdsMaxBytes) return false;
+    if (flags & CGP_WAVE_PER_TRIAL) return true;
+    if (flags & CGP_THREAD_PER_TRIAL) return false;
+    if (limit.num < 0) return true;
+    const int64_t simds = (int64_t)num_cus * 4;
+    return B * limit.den < (int64_t)limit.num * simds;
+}
+// What a call would run with one wavefront per trial, and up to how many trials per SIMD that beats what it would run with one lane
+// per trial: `limit` against a generic lane kernel, `limit_lane4` against the large-batch kernels of cgp_lane4.hpp.
+template <class Route> struct WaveCandidate {
+    Route route;
+    ShapeLimit limit, limit_lane4;
+    void crossover(int trials_per_simd, int against_lane4) { limit = {trials_per_simd, 1}; limit_lane4 = {against_lane4, 1}; }
+};
+
+// ---- filters -----------------------------------------------------------------------------------------------------------------------
+enum class FilterRoute {
+    kGenericWave, kGenericLane,                                // filter_kernel of cgp_kernels.hpp, by model family and method
+    kKf4Mfma,                                                  // kf at d = 4: the matrix-core EKF step with the constant Jacobian F
+    kEkf4Mfma, kEkf4MfmaSeg, kEkf4MfmaX4, kEkf4Coop,           // ekf, d = 4: one trial, one segment or four trials a wavefront; DPP rows
+    kSgp4Mfma, kSgp4Coop, kLane4Ekf, kLane4Sgp,                // sgp_filter, d = 4; the large-batch lane kernels
+    kEkf8Coop, kSgp8Coop,                                      // 2 / 3 harmonics in the tile layout
+    kCdEkf4Mfma, kCdEkf4Coop, kCdSgp4Mfma, kCdSgp4Coop,        // continuous-discrete, d = 4
+    kKpt8Coop, kGenericKpt                                     // ekf_for_kpt: tile layout / matrix cores, or filter_kernel in either shape
+};
+// the kernels that know the segments of a time-split launch (kEkf4Mfma: as kEkf4MfmaSeg)
+inline bool knows_segments(FilterRoute r) {
+    return r == FilterRoute::kEkf4Mfma || r == FilterRoute::kSgp4Mfma || r == FilterRoute::kSgp8Coop || r == FilterRoute::kCdSgp4Mfma;
+}
+struct FilterQuery {
+    int method;
+    const cgp_model* model;          // checked (check_model)
+    const cgp_sigma* sigma;          // or NULL
+    const FilterIO* io;              // filled but for the segments
+    const ModelArgs* ma;
+    uint32_t flags;
+    int64_t segments;                // requested (cgp_filter_time_split); 1: none
+    int num_cus;
+};
+struct FilterDecision {
+    int rc = CGP_OK;                 // or the refusal and its message
+    const char* message = nullptr;
+    FilterRoute route = FilterRoute::kGenericWave;
+    bool wave = true;
+    uint32_t flags = 0;              // the call's, with CGP_WAVE_PER_TRIAL where the segments force it
+    int segs = 1;                    // effective: without the empty ones
+    int64_t seg_len = 0;
+};
+
+inline WaveCandidate<FilterRoute> filter_wave_candidate(const FilterQuery& q) {
+    const cgp_model& m = *q.model;
+    const int64_t T = q.io->T;
+    const bool sig = q.method == CGP_F_SGP || q.method == CGP_F_CD_SGP;
+    const ShapeLimit generic = sig ? ShapeLimit{8, 1} : ShapeLimit{5, 2};
+    WaveCandidate<FilterRoute> c{FilterRoute::kGenericWave, generic, generic};
+    const bool spec = !(q.flags & CGP_GENERIC_KERNEL), mfma = !(q.flags & CGP_DPP_KERNEL);
+    // Kept as found: a crossover belongs to the (method, model) family and the flags, not to the kernel the family ends up with -- a record
+    // too long for a matrix-core or tile-layout kernel's windows, or a set its quadrature does not take, runs the DPP or generic kernel
+    // under the specialised kernel's limit (d = 6 / 8: {8, 1} and {11, 1} on the generic kernel), CGP_DPP_KERNEL and
+    // CGP_ONE_TRIAL_PER_WAVE fall back to the generic limits, and kf at d = 4 never left them.
+    switch (m.model_id) {
+    case CGP_M_LINEAR:
+        if (q.method == CGP_F_EKF && m.d == 4 && spec && mfma && mfma4_rows_fit(T)) c.route = FilterRoute::kKf4Mfma;
+        break;
+    case CGP_M_HARMONIC_LCD:
+    case CGP_M_LASCALA_LCD: {
+        const bool chirp4 = spec && m.n_harm == 1;
+        const bool harm8 = spec && m.model_id == CGP_M_HARMONIC_LCD && (m.n_harm == 2 || m.n_harm == 3);
+        if (q.method == CGP_F_EKF && chirp4) {
+            c.route = (mfma && ekf4_mfma_fits(*q.io)) ? FilterRoute::kEkf4Mfma : FilterRoute::kEkf4Coop;
+            if (mfma && !(q.flags & CGP_ONE_TRIAL_PER_WAVE)) c.crossover(20, 9);
+        } else if (q.method == CGP_F_SGP && chirp4) {
+            c.route = (mfma && sgp4_mfma_fits(T, *q.ma)) ? FilterRoute::kSgp4Mfma : FilterRoute::kSgp4Coop;
+            if (mfma) c.crossover(24, 9);
+        } else if (q.method == CGP_F_EKF && harm8) {
+            if (coop8_rows_fit(m.d, T)) c.route = FilterRoute::kEkf8Coop;
+            c.crossover(8, 8);
+        } else if (q.method == CGP_F_SGP && harm8) {
+            if (coop8_filter_sgp_ok(m.n_harm, T, *q.ma)) c.route = FilterRoute::kSgp8Coop;
+            c.crossover(11, 11);
+        }
+        break;
+    }
+    case CGP_M_HARMONIC_SDE: {
+        const bool sde4 = spec && m.n_harm == 1;
+        if (q.method == CGP_F_CD_SGP && sde4) {
+            c.route = (mfma && sgp4_mfma_fits(T, *q.ma)) ? FilterRoute::kCdSgp4Mfma : FilterRoute::kCdSgp4Coop;
+            if (mfma) c.crossover(48, 48);
+        } else if (q.method == CGP_F_CD_EKF && sde4) {
+            c.route = (mfma && mfma4_rows_fit(T)) ? FilterRoute::kCdEkf4Mfma : FilterRoute::kCdEkf4Coop;
+            if (mfma) c.crossover(4, 4);
+        }
+        break;
+    }
+    case CGP_M_KPT:
+        c.route = (spec && kpt8_fits(m.n_harm, T)) ? FilterRoute::kKpt8Coop : FilterRoute::kGenericKpt;
+        break;
+    default: break;
+    }
+    return c;
+}
+inline FilterRoute filter_lane_candidate(const FilterQuery& q, int segs) {
+    const cgp_model& m = *q.model;
+    if (m.model_id == CGP_M_KPT) return FilterRoute::kGenericKpt;
+    const bool lcd = m.model_id == CGP_M_HARMONIC_LCD || m.model_id == CGP_M_LASCALA_LCD;
+    if (lcd && m.n_harm == 1 && !(q.flags & CGP_GENERIC_KERNEL) && segs <= 1 && lane4_filter_fits(*q.io)) {
+        if (q.method == CGP_F_EKF) return FilterRoute::kLane4Ekf;
+        if (q.method == CGP_F_SGP && lane4_sgp_fits(*q.ma)) return FilterRoute::kLane4Sgp;
+    }
+    return FilterRoute::kGenericLane;
+}
+inline FilterDecision route_filter(const FilterQuery& q) {
+    FilterDecision d;
+    d.flags = q.flags;
+    auto refuse = [&d](const char* message) { d.rc = CGP_E_UNSUPPORTED; d.message = message; return d; };
+    const bool sig = q.method == CGP_F_SGP || q.method == CGP_F_CD_SGP;
+    const int64_t B = q.io->B, T = q.io->T;
+    const WaveCandidate<FilterRoute> wave = filter_wave_candidate(q);
+    // ---- time-split with burn-in (cgp_filter_time_split): segments of whole 64-step chunks, one wavefront each
+    if (q.segments > 1) {
+        // (kept as found: admission goes by the REQUESTED segments -- a record too short to split is refused all the same where the
+        // kernel knows no segments -- and CGP_DPP_KERNEL refuses the split on the 2- / 3-harmonic model too, whose kernel has no DPP
+        // variant to ask for)
+        if (!knows_segments(wave.route) || (q.flags & (CGP_DPP_KERNEL | CGP_THREAD_PER_TRIAL | CGP_FOUR_TRIALS_PER_WAVE)))
+            return refuse("time-split filters are built for ekf / sgp_filter / cd_sgp_filter on the d = 4 chirp and La Scala models "
+                          "and sgp_filter on the 2- / 3-harmonic model (matrix-core and tile-layout kernels, standard sigma sets)");
+        d.seg_len = ((T + q.segments - 1) / q.segments + 63) / 64 * 64;
+        const int64_t segs = (T + d.seg_len - 1) / d.seg_len;              // without the empty ones
+        if (segs > 1) {
+            // (a set too large for the LDS stage runs one lane per trial whatever the flags say -- choose_wave -- and those kernels
+            // know no segments: refuse instead of reading records nobody wrote)
+            if (sig && SigmaSet::stage_bytes(q.sigma->s, q.sigma->d, q.sigma->n_groups, q.sigma->group_start != nullptr) > (size_t)kSigLdsMaxBytes)
+                return refuse("time-split filters need a sigma-point set that fits the LDS stage of the one-wavefront-per-trial kernels");
+            d.segs = (int)segs;
+            d.flags |= CGP_WAVE_PER_TRIAL;
+        }
+    }
+    const FilterRoute lane = filter_lane_candidate(q, d.segs);
+    const bool lane4 = lane == FilterRoute::kLane4Ekf || lane == FilterRoute::kLane4Sgp;
+    d.wave = choose_wave(q.num_cus, B, d.flags, lane4 ? wave.limit_lane4 : wave.limit, sig ? q.sigma : nullptr);
+    // (kept as found: unreachable -- the segments set CGP_WAVE_PER_TRIAL, and the one thing that overrides it was refused above)
+    if (d.segs > 1 && !d.wave) return refuse("time-split filters run one wavefront per trial only");
+    d.route = d.wave ? wave.route : lane;
+    if (d.route == FilterRoute::kEkf4Mfma) {
+        // beyond one wave per SIMD the four MFMA blocks carry four trials (CGP_ONE_TRIAL_PER_WAVE keeps one, for tests).  Kept as found:
+        // "one wave per SIMD" is the literal 1024, whatever num_cus says.
+        if (d.segs > 1) d.route = FilterRoute::kEkf4MfmaSeg;
+        else if ((B > 1024 || (q.flags & CGP_FOUR_TRIALS_PER_WAVE)) && ekf4_mfma_x4_fits(*q.io) && !(q.flags & CGP_ONE_TRIAL_PER_WAVE))
+            d.route = FilterRoute::kEkf4MfmaX4;
+    }
+    return d;
+}
+
+// ---- smoothers ---------------------------------------------------------------------------------------------------------------------
+enum class SmootherRoute {
+    kCoop8Linear, kWalk4Linear, kDiscLinear,                   // rts: tile layout (5 <= d <= 8), the d = 4 walk, the generic kernels
+    kCoop8Harm, kWalk4Harm, kLane4, kDiscHarm,                 // eks / sgp_smoother on the chirp family; kLane4 also cd_eks on the chirp SDE
+    kSdeLinear, kCdSgp4Mfma, kCdSgp4Coop, kCdEks4Mfma, kCdEks4Coop, kSdeHarm, kNone
+};
+// selected outputs (cgp_smoother_select) are written by the kernel itself where it is one of the d = 4 walks / lane kernels or the
+// tile-layout kernels (mss / Pss then optional); any other kernel writes the full rows and a gather launch reads the marginal back
+inline bool writes_selection(SmootherRoute r) {
+    return r == SmootherRoute::kWalk4Linear || r == SmootherRoute::kWalk4Harm || r == SmootherRoute::kLane4 || r == SmootherRoute::kCoop8Linear ||
+           r == SmootherRoute::kCoop8Harm;
+}
+// the kernels that know the segments of a time-split launch with burn-in (cgp_smoother_time_split)
+inline bool knows_segments(SmootherRoute r) { return r == SmootherRoute::kCdSgp4Mfma || r == SmootherRoute::kCdEks4Mfma; }
+struct SmootherQuery {
+    int method;
+    const cgp_model* model;          // checked (check_model)
+    const cgp_sigma* sigma;          // or NULL
+    const SmootherIO* io;
+    const ModelArgs* ma;
+    uint32_t flags;
+    int num_cus;
+};
+struct SmootherDecision { SmootherRoute route; bool wave; };
+
+inline WaveCandidate<SmootherRoute> smoother_wave_candidate(const SmootherQuery& q) {
+    const cgp_model& m = *q.model;
+    const ModelArgs& ma = *q.ma;
+    const int64_t T = q.io->T;
+    const bool sig = q.method == CGP_S_SGP || q.method == CGP_S_CD_SGP;
+    const bool affine = (q.method == CGP_S_EKS || q.method == CGP_S_SGP) && !(q.flags & CGP_SEQUENTIAL_SCAN);
+    const ShapeLimit generic = affine ? ShapeLimit{16, 1} : (sig ? ShapeLimit{8, 1} : ShapeLimit{5, 2});
+    WaveCandidate<SmootherRoute> c{SmootherRoute::kNone, generic, generic};
+    const bool spec = !(q.flags & CGP_GENERIC_KERNEL), mfma = !(q.flags & CGP_DPP_KERNEL);
+    auto walk = [&c](SmootherRoute r, ShapeLimit against_lane4) { c.route = r; c.limit = kWaveAlways; c.limit_lane4 = against_lane4; };
+    switch (m.model_id) {
+    case CGP_M_LINEAR:
+        c.route = SmootherRoute::kDiscLinear;
+        // 5 <= d <= 8: maps built per lane, applied cooperatively in the tile layout (cgp_coop8.hpp)
+        if (affine && spec && coop8_smoother_ok(m.d, T, ma)) walk(SmootherRoute::kCoop8Linear, kWaveAlways);
+        // d = 4: gains per lane, the recursion walked on the matrix cores (cgp_walk4.hpp)
+        else if (affine && spec && m.d == 4 && walk4_smoother_ok(T, ma)) walk(SmootherRoute::kWalk4Linear, kWaveAlways);
+        break;
+    case CGP_M_HARMONIC_LCD:
+    case CGP_M_LASCALA_LCD:
+        c.route = SmootherRoute::kDiscHarm;
+        if (affine && spec && m.n_harm >= 2 && coop8_smoother_ok(m.d, T, ma) && coop8_smoother_harm_ok(q.method, ma)) walk(SmootherRoute::kCoop8Harm, kWaveAlways);
+        else if (affine && spec && m.n_harm == 1 && walk4_smoother_ok(T, ma)) walk(SmootherRoute::kWalk4Harm, ShapeLimit{24, 1});
+        break;
+    case CGP_M_LINEAR_SDE: c.route = SmootherRoute::kSdeLinear; break;
+    case CGP_M_HARMONIC_SDE: {
+        // (kept as found, as for the filters: the crossovers go with the family and CGP_DPP_KERNEL, not with the kernel)
+        const bool sde4 = spec && m.n_harm == 1;
+        c.route = SmootherRoute::kSdeHarm;
+        if (q.method == CGP_S_CD_SGP && sde4) {
+            c.route = (mfma && sgp4_mfma_fits(T, ma)) ? SmootherRoute::kCdSgp4Mfma : SmootherRoute::kCdSgp4Coop;
+            if (mfma) c.crossover(48, 48);
+        } else if (q.method == CGP_S_CD_EKS && sde4) {
+            c.route = (mfma && mfma4_rows_fit(T)) ? SmootherRoute::kCdEks4Mfma : SmootherRoute::kCdEks4Coop;
+            if (mfma) c.crossover(5, 3);
+        }
+        break;
+    }
+    default: break;
+    }
+    return c;
+}
+inline SmootherRoute smoother_lane_candidate(const SmootherQuery& q) {
+    const cgp_model& m = *q.model;
+    const bool lane4 = m.n_harm == 1 && !(q.flags & CGP_GENERIC_KERNEL) && lane4_smoother_fits(*q.io);
+    switch (m.model_id) {
+    case CGP_M_LINEAR: return SmootherRoute::kDiscLinear;
+    case CGP_M_HARMONIC_LCD:
+    case CGP_M_LASCALA_LCD: return (q.method == CGP_S_EKS && lane4) ? SmootherRoute::kLane4 : SmootherRoute::kDiscHarm;
+    case CGP_M_LINEAR_SDE: return SmootherRoute::kSdeLinear;
+    case CGP_M_HARMONIC_SDE: return (q.method == CGP_S_CD_EKS && lane4) ? SmootherRoute::kLane4 : SmootherRoute::kSdeHarm;
+    default: return SmootherRoute::kNone;
+    }
+}
+inline SmootherDecision route_smoother(const SmootherQuery& q) {
+    const bool sig = q.method == CGP_S_SGP || q.method == CGP_S_CD_SGP;
+    const WaveCandidate<SmootherRoute> wave = smoother_wave_candidate(q);
+    const SmootherRoute lane = smoother_lane_candidate(q);
+    const ShapeLimit limit = lane == SmootherRoute::kLane4 ? wave.limit_lane4 : wave.limit;
+    SmootherDecision d;
+    d.wave = choose_wave(q.num_cus, q.io->B, q.flags, limit, sig ? q.sigma : nullptr);
+    d.route = d.wave ? wave.route : lane;
+    return d;
+}
+
+}  // namespace cgp
+#endif                         // __HIPCC_RTC__

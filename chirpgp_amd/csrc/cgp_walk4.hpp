@@ -42,6 +42,7 @@ namespace cgp {
 constexpr int kWalkRec = 37;                      // G 16 (row-major) | C 16 (full) | c 4 | pad: odd, conflict-free lane stride
 constexpr int kWalkG = 0, kWalkC = 16, kWalkc = 32;
 constexpr int kWalkAhead = 2;                     // quads between an operand's LDS read and its use
+static_assert(kWalk4LdsBytes == sizeof(double) * 64 * kWalkRec, "walk4_smoother_ok (cgp_route.hpp) budgets the records of walk4_smoother_kernel");
 constexpr int kWalkMapDoubles = 40;               // a segment's composed map in the workspace: A 16 | C 16 | c 4 | pad
 struct Walk4Operands { double g, C, c; };
 
@@ -239,50 +240,13 @@ __global__ void __launch_bounds__(64) walk4_smoother_kernel(SmootherIO io, Model
     }
 }
 
-// One workgroup holds 64 records (18 944 B) beside the staged sigma-point set; at least four of them have to share a CU's 160 KB.
-inline bool walk4_smoother_ok(int64_t T, const ModelArgs& ma) {
-    return T * 128 <= kOobMaxBytes && sigma_lds_bytes(ma, 4) + sizeof(double) * 64 * kWalkRec + 64 <= 40 * 1024;
-}
 template <class Elem>
-inline hipError_t launch_walk4_smoother(const SmootherIO& io_in, const ModelArgs& ma, hipStream_t stream) {
-    if (io_in.B <= 0 || io_in.T <= 0) return hipSuccess;
-    if (!walk4_smoother_ok(io_in.T, ma)) return hipErrorInvalidValue;
-    const size_t dyn = Elem::USES_SIGMA ? sigma_lds_bytes(ma, 4) : 0;
-    // workgroups of the split kernel a CU holds (registers, LDS): asked once per kernel and dynamic-LDS size, then remembered
-    static std::atomic<long long> occ_cache{-1};                           // (dyn << 8) | per_cu
-    int per_cu = 0;
-    if (io_in.segs != 1) {
-        const long long seen = occ_cache.load(std::memory_order_relaxed);
-        if (seen >= 0 && (size_t)(seen >> 8) == dyn) per_cu = (int)(seen & 0xFF);
-        else {
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, walk4_smoother_kernel<Elem, kWalkApply>, 64, dyn) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 4; }
-            occ_cache.store(((long long)dyn << 8) | (per_cu & 0xFF), std::memory_order_relaxed);
-        }
-    }
-    const int segs = walk_segments(io_in, per_cu);
-    const bool sel = io_in.sel.comp >= 0;
-    auto whole = [&]() {
-        if (sel) hipLaunchKernelGGL((walk4_smoother_kernel<Elem, kWalkWhole, true>), dim3((unsigned)io_in.B), dim3(64), dyn, stream, io_in, ma);
-        else hipLaunchKernelGGL((walk4_smoother_kernel<Elem, kWalkWhole>), dim3((unsigned)io_in.B), dim3(64), dyn, stream, io_in, ma);
-        return hipGetLastError();
-    };
-    if (segs <= 1) return whole();
-    // time-split: two passes with the segments' maps in the context's per-stream workspace (nothing the caller sees)
-    SmootherIO io = io_in;
-    io.segs = segs;
-    const int64_t tiles = (io.T - 1 + 63) / 64;
-    io.tiles_per_seg = (int)((tiles + io.segs - 1) / io.segs);
-    io.segs = (int)((tiles + io.tiles_per_seg - 1) / io.tiles_per_seg);           // no empty segments
-    void* ws = ctx_workspace(io.host_ctx, stream, sizeof(double) * kWalkMapDoubles * (size_t)io.B * io.segs);
-    hipError_t e;
-    if (!ws) return whole();             // no workspace (allocation failed, pinned too small, growth inside a graph capture): the one-wave-per-trial form needs none
-    io.ws = (double*)ws;
-    const unsigned grid = (unsigned)(io.B * io.segs);
-    hipLaunchKernelGGL((walk4_smoother_kernel<Elem, kWalkCompose>), dim3(grid), dim3(64), dyn, stream, io, ma);
-    if (sel) hipLaunchKernelGGL((walk4_smoother_kernel<Elem, kWalkApply, true>), dim3(grid), dim3(64), dyn, stream, io, ma);
-    else hipLaunchKernelGGL((walk4_smoother_kernel<Elem, kWalkApply>), dim3(grid), dim3(64), dyn, stream, io, ma);
-    e = hipGetLastError();
-    return e;
+inline hipError_t launch_walk4_smoother(const SmootherIO& io, const ModelArgs& ma, hipStream_t stream) {
+    if (io.B <= 0 || io.T <= 0) return hipSuccess;
+    if (!walk4_smoother_ok(io.T, ma)) return hipErrorInvalidValue;
+    return launch_walk_smoother<Elem, walk4_smoother_kernel<Elem, kWalkWhole, false>, walk4_smoother_kernel<Elem, kWalkWhole, true>,
+                                walk4_smoother_kernel<Elem, kWalkCompose, false>, walk4_smoother_kernel<Elem, kWalkApply, false>,
+                                walk4_smoother_kernel<Elem, kWalkApply, true>>(io, ma, stream, kWalkMapDoubles);
 }
 
 }  // namespace cgp
