@@ -56,7 +56,8 @@ template <int N> CGP_DEV Dual<N> exp(const Dual<N>& a) { const double e = ::exp(
 template <int N> CGP_DEV Dual<N> log(const Dual<N>& a) { return chain(a, ::log(a.v), 1.0 / a.v); }
 template <int N> CGP_DEV Dual<N> sqrt(const Dual<N>& a) { const double r = ::sqrt(a.v); return chain(a, r, 0.5 / r); }
 template <int N> CGP_DEV Dual<N> tanh(const Dual<N>& a) { const double t = ::tanh(a.v); return chain(a, t, 1.0 - t * t); }
-template <int N> CGP_DEV Dual<N> pow(const Dual<N>& a, double e) { const double p = ::pow(a.v, e - 1.0); return chain(a, p * a.v, e * p); }
+// (the value as the double instantiation computes it, so that both agree at a.v = 0; d/dx x^0 = 0 everywhere, as jax.grad has it)
+template <int N> CGP_DEV Dual<N> pow(const Dual<N>& a, double e) { return chain(a, ::pow(a.v, e), e == 0.0 ? 0.0 : e * ::pow(a.v, e - 1.0)); }
 // the reference's positive bijection g(x) = log(exp(x) + 1) (models.py:50, the naive form) and its derivative
 CGP_DEV double softplus(double x) { return ::log(::exp(x) + 1.0); }
 template <int N> CGP_DEV Dual<N> softplus(const Dual<N>& a) { const double e = ::exp(a.v), z = e + 1.0; return chain(a, ::log(z), e / z); }

@@ -239,8 +239,8 @@ def custom_cond_m_cov(source, d, params, host=None):
     """Descriptor of a discrete model the library does not enumerate -- what the reference takes as any traceable ``cond_m_cov(u, dt)``
     (filters_smoothers.py:222-264, 317-349, 446-531): usable with ``ekf``, ``eks``, ``sgp_filter`` and ``sgp_smoother`` (the covariance is
     evaluated at every sigma point, as the reference's ``_sgp_prediction`` does).  ``source`` is HIP device code defining, for a generic scalar
-    type T (double, or the dual numbers the kernel differentiates with: sin, cos, exp, log, sqrt, tanh, pow(x, const) and softplus are
-    overloaded),
+    type T (double, or the dual numbers the kernel differentiates with: + - * / with either operand a double, unary minus, += -= *=,
+    sin, cos, exp, log, sqrt, tanh, pow(x, const) -- pow(0, 0) = 1 with derivative 0 -- and softplus are overloaded),
 
         template <class T> __device__ void cond_mean(const T* u, const double* p, double dt, T* mean);
         __device__ void cond_cov(const double* u, const double* p, double dt, double* cov);      // cov: [d][d] row-major, symmetric
