@@ -120,17 +120,6 @@ struct SmoothSel {
 //      log1p by six terms of its series (truncation t^7 / 7 < 1e-19): ~25 instructions a node;
 //   2. any |x| < 700: the branch-free full-accuracy softplus of cgp_fastmath.hpp (softplus_pair_any), ~80 a node;
 //   3. otherwise (overflow, inf, NaN) and for the other integrands: the library functions, as cgp_gaussian_expectation_fn evaluates them.
-CGP_DEV double exp_neg_lean_lit(double x) {
-    const double nx = -x;
-    const double k = __builtin_rint(nx * kLog2e);
-    double r = fma(-k, kLn2Hi, nx);
-    r = fma(-k, kLn2Lo, r);
-    const double r2 = r * r;
-    const double a0 = fma(kExpLean[1], r, kExpLean[0]), a1 = fma(kExpLean[3], r, kExpLean[2]);
-    const double a2 = fma(kExpLean[5], r, kExpLean[4]), a3 = fma(kExpLean[7], r, kExpLean[6]);
-    const double r4 = r2 * r2;
-    return __builtin_amdgcn_ldexp(fma(fma(a3, r2, a2), r4, fma(a1, r2, a0)), (int)k);
-}
 CGP_DEV double gh_expectation(int func, double m, double s, const double* __restrict__ xi, const double* __restrict__ w, int order) {
     double fast = 0.0;
     bool have = false;
@@ -146,8 +135,8 @@ CGP_DEV double gh_expectation(int func, double m, double s, const double* __rest
             for (int p = 0; p < order; p++) {
                 const double x = fma(s, xi[p], m);
                 const double t = exp_neg_lean_lit(x);
-                double q = fma(t, -1.0 / 6.0, 1.0 / 5.0);                      // log1p(t) / t = 1 - t/2 + t^2/3 - t^3/4 + t^4/5 - t^5/6
-                q = fma(q, t, -1.0 / 4.0); q = fma(q, t, 1.0 / 3.0); q = fma(q, t, -0.5); q = fma(q, t, 1.0);
+                double q = kLog1pSeries[0];                                    // log1p(t) / t = 1 - t/2 + t^2/3 - t^3/4 + t^4/5 - t^5/6
+                CGP_UNROLL for (int i = 1; i < 6; i++) q = fma(q, t, kLog1pSeries[i]);
                 acc = fma(w[p], fma(q, t, x), acc);
             }
             fast = acc;
@@ -165,6 +154,8 @@ CGP_DEV double gh_expectation(int func, double m, double s, const double* __rest
         have = tier1 || tier2;
         if (__builtin_amdgcn_ballot_w64(!have) == 0) return fast;
     }
+    // (the integrand switch of gaussian_expectation_kernel, cgp_api.hip, written out again: called as a shared function from here, by value
+    // or as the whole loop, this function comes out with other branches and registers -- cgp_api and cgp_inst_walk4 differed)
     double acc = 0.0;
     for (int p = 0; p < order; p++) {
         const double x = fma(s, xi[p], m);

@@ -99,7 +99,7 @@ __global__ void __launch_bounds__(64) lane4_filter_kernel(FilterIO io, ModelArgs
     pred.setup(ma, trial);
     if constexpr (Pred::USES_SIGMA) pred.sg.stage(dyn_lds(), lane, 64, D);       // (SgpPredictLane: the fan reads the set from LDS)
     pred.large_batch();                                  // small-angle sin / cos where every lane's angle allows (cgp_fastmath.hpp)
-    // (the per-lane softplus stays the naive form here: the wide common-regime form -- cgp_models.hpp: softplus_pair_wide -- pays only
+    // (the per-lane softplus stays the naive form here: the wide common-regime form -- cgp_fastmath.hpp: softplus_pair_wide -- pays only
     // while every lane's frequency state is >= 1.5, and the CRLB job's is a zero-mean GP: its fallback ran in every wavefront, +23 %
     // vector instructions, measured)
     Vec<D> H, mf;

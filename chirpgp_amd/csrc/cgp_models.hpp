@@ -15,108 +15,9 @@
 
 namespace cgp {
 
-// softplus log(exp(x) + 1) (models.py:50) and its derivative exp(x) / (exp(x) + 1), per lane, for the latency-bound kernels.
-// Common regime, 1.5 <= x < 700 (frequencies above 1.7 Hz):  x + t q(t)  and  1 / (1 + t)  with t = exp(-x) <= 0.223 and
-// q = log1p(t) / t, both by the LEAN degree-7 polynomials of cgp_fastmath.hpp (relative error 7e-12 on the softplus,
-// 1.2e-11 on the derivative: these kernels' results sat eight orders inside the 1e-5 gate) -- 23 instructions instead of
-// the 63 of exp + full log.  If ANY active lane is outside that regime (or NaN) the wavefront also evaluates the
-// reference's naive form, whose overflow behaviour (inf, NaN) is the reference's, and those lanes take it: one
-// wave-uniform branch, not taken in the common case.
-CGP_DEV double exp_neg_lean_lane(double x) {
-    const double nx = -x;
-    const double k = __builtin_rint(nx * kLog2e);
-    double r = fma(-k, kLn2Hi, nx);
-    r = fma(-k, kLn2Lo, r);
-    const double r2 = r * r;
-    const double a0 = horner(kExpLean[1], r, kExpLean[0]), a1 = horner(kExpLean[3], r, kExpLean[2]);
-    const double a2 = horner(kExpLean[5], r, kExpLean[4]), a3 = horner(kExpLean[7], r, kExpLean[6]);
-    const double r4 = r2 * r2;
-    return __builtin_amdgcn_ldexp(horner(horner(a3, r2, a2), r4, horner(a1, r2, a0)), (int)k);
-}
-CGP_DEV double log1p_over_t_lean(double t) {
-    const double t2 = t * t;
-    const double a0 = horner(kLog1pOverTLean[1], t, kLog1pOverTLean[0]), a1 = horner(kLog1pOverTLean[3], t, kLog1pOverTLean[2]);
-    const double a2 = horner(kLog1pOverTLean[5], t, kLog1pOverTLean[4]), a3 = horner(kLog1pOverTLean[7], t, kLog1pOverTLean[6]);
-    const double t4 = t2 * t2;
-    return horner(horner(a3, t2, a2), t4, horner(a1, t2, a0));
-}
 // the three forms of a sigma-point fan's softplus -> sin / cos chain in the one-wavefront kernels (precompute / precompute_spec /
 // precompute_any below): spec first; if a lane is outside its regime, any; checked as the last resort
 constexpr int kFanChecked = 0, kFanSpec = 1, kFanAny = 2;
-CGP_DEV bool softplus_lane_common(double x) { return x >= 1.5 && x < 700.0; }
-// The lean softplus on BOTH sides (round 5; the sigma-point fans, which need no derivative): with t = exp(-|x|) <= 0.223 for |x| >= 1.5,
-//     softplus(x) = max(x, 0) + log1p(t) = max(x, 0) + t q(t)
-// -- for x <= -1.5 the same polynomials in the same t-range as for x >= 1.5, one v_max_f64 off the chain.  Records the filter has lost sit at
-// a NEGATIVE frequency state most of the time (tools/state_histogram.py): their fans stay in the lean tier.
-CGP_DEV bool softplus_lane_lean2(double x) { return fabs(x) >= 1.5 && fabs(x) < 700.0; }
-CGP_DEV void softplus_pair_wide(double x, double& sp, double& dsp) {
-    const double t = exp_neg_lean_lane(x);
-    sp = fma(log1p_over_t_lean(t), t, x);
-    dsp = rcp_nr1(1.0 + t);
-    const bool common = softplus_lane_common(x);
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!common) != 0, 0)) {
-        const double e = fast_exp(x);
-        const double z = e + 1.0;
-        const double sp_n = fast_log_ge1(z), dsp_n = e * rcp_nr(z);     // inf * NaN = NaN where the reference has inf / inf = NaN
-        sp = common ? sp : sp_n;
-        dsp = common ? dsp : dsp_n;
-    }
-}
-CGP_DEV double softplus_wide(double x) {
-    const double t = exp_neg_lean_lane(x);
-    double sp = fma(log1p_over_t_lean(t), t, x);
-    const bool common = softplus_lane_common(x);
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!common) != 0, 0)) {
-        const double sp_n = fast_log_ge1(fast_exp(x) + 1.0);
-        sp = common ? sp : sp_n;
-    }
-    return sp;
-}
-// The naive form as is: fewer live registers than the pair above (no second path, no 16 polynomial coefficients), which
-// is what counts in the one-lane-per-trial kernels -- they live on occupancy, and the wide form costs them a wave per SIMD
-// (measured: lane-per-trial EKS 2.3 -> 4.6 ms at B = 65536).
-CGP_DEV void softplus_pair(double x, double& sp, double& dsp) {
-    const double e = fast_exp(x);
-    const double z = e + 1.0;
-    sp = fast_log_ge1(z);
-    dsp = e * rcp_nr(z);            // inf * NaN = NaN where the reference has inf / inf = NaN
-}
-CGP_DEV double softplus(double x) { return fast_log_ge1(fast_exp(x) + 1.0); }
-// The naive form for the large-batch lane kernels (cgp_lane4.hpp), which are bound by their vector instruction count: exp and log without
-// their overflow / underflow / inf selects and with the direct exponent extraction (cgp_fastmath.hpp: fast_log_ge1_finite) -- the same
-// values for x < 700 (an ulp in the log where the mantissa interval's ends are met), 12 instructions less; if ANY lane is at or beyond
-// 700 (or NaN) the wavefront also evaluates softplus_pair and those lanes take it, overflow behaviour and all.
-CGP_DEV double softplus_batch(double x) {
-    double sp = fast_log_ge1_finite(fast_exp_core(x) + 1.0);
-    const bool regular = x < 700.0;
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!regular) != 0, 0)) {
-        const double sp_n = softplus(x);
-        sp = regular ? sp : sp_n;
-    }
-    return sp;
-}
-CGP_DEV void softplus_pair_batch(double x, double& sp, double& dsp) {
-    const double e = fast_exp_core(x);
-    const double z = e + 1.0;
-    sp = fast_log_ge1_finite(z);
-    dsp = e * rcp_nr(z);
-    const bool regular = x < 700.0;
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!regular) != 0, 0)) {
-        double sp_n, dsp_n;
-        softplus_pair(x, sp_n, dsp_n);
-        sp = regular ? sp : sp_n;
-        dsp = regular ? dsp : dsp_n;
-    }
-}
-// `uniform` = the argument is the same in all lanes of the wavefront (a wave-per-trial kernel evaluating the model at the
-// trial's mean): one scalar branch then picks the cheap large-x form (cgp_fastmath.hpp).  `wide` = the kernel is latency-
-// rather than occupancy-bound (one wavefront per trial, time-parallel smoother): take the wide common-regime form.
-CGP_DEV void softplus_pair_sel(bool uniform, bool wide, double x, double& sp, double& dsp) {
-    if (uniform) softplus_pair_uniform(x, sp, dsp);
-    else if (wide) softplus_pair_wide(x, sp, dsp);
-    else softplus_pair(x, sp, dsp);
-}
-CGP_DEV double softplus_sel(bool wide, double x) { return wide ? softplus_wide(x) : softplus(x); }
 
 // Closed-form Matern-3/2 discretisation, models.py:61-73.
 CGP_DEV void m32_solution(double ell, double sigma, double dt, double (&M)[4], double (&S)[3]) {
