@@ -158,6 +158,57 @@ template <class DM> CGP_DEV double lane_sigma_entry(const DM& model, int i, int 
 // Whether a trial's measurement vector is the unit vector e_1, as in every chirp / La Scala builder of the reference (models.py:118)
 CGP_DEV bool h_is_e1(const double* __restrict__ Hp) { return Hp[0] == 0.0 && Hp[1] == 1.0 && Hp[2] == 0.0 && Hp[3] == 0.0; }
 
+// Outputs of a filter in the cooperative layout: lanes 0..15 store Pf[t] as one coalesced row, lane 0 the mean.
+struct Coop4FilterOut {
+    double* __restrict__ mfs; double* __restrict__ Pfs; double* __restrict__ nll;
+    bool nll_final, want_nll;
+    CGP_DEV void init(const FilterIO& io, int64_t trial) {
+        const int64_t T = io.T;
+        mfs = io.mfs ? io.mfs + trial * T * 4 : nullptr;
+        Pfs = io.Pfs ? io.Pfs + trial * T * 16 : nullptr;
+        nll_final = (io.flags & CGP_NLL_FINAL_ONLY) != 0;
+        nll = (io.nll && !nll_final) ? io.nll + trial * T : nullptr;
+        want_nll = io.nll != nullptr;
+    }
+    CGP_DEV void store(int64_t t, int lane, double P, const Vec<4>& u) const {
+        if (Pfs && lane < 16) Pfs[t * 16 + lane] = P;
+        if (mfs && lane == 0) {
+            *reinterpret_cast<double2*>(mfs + t * 4) = make_double2(u.v[0], u.v[1]);
+            *reinterpret_cast<double2*>(mfs + t * 4 + 2) = make_double2(u.v[2], u.v[3]);
+        }
+    }
+};
+
+// THE forward loop of the cooperative filters: the record in chunks of 64 measurements (one per lane, handed to the steps by v_readlane), the
+// update, the stores, and the NLL latch -- lane `slot` keeps (S, innovation) of its step, a chunk's increments are summed by nll_flush_wave.
+// predict(u, P, f, Pp) is what a kernel keeps to itself: the predicted mean (replicated) and the lane's entry of the predicted covariance.
+// The kernels load (meas, m0, P0) themselves, where they always did: the order of those loads among a kernel's own decides its registers.
+// ekf4_coop_kernel below keeps its own copy of this loop: on the shared one its filter measured 1.4 % slower (docs/EXPERIMENTS.md 5k).
+template <class Predict>
+CGP_DEV void coop4_filter_walk(const FilterIO& io, int64_t trial, int lane, const Coop4Meas& meas, Vec<4> u, double P, Predict predict) {
+    const int64_t T = io.T;
+    const double* __restrict__ ys = io.record(trial);
+    Coop4FilterOut out;
+    out.init(io, trial);
+    double cum = 0.0, S_l = 1.0, innov_l = 0.0;
+    for (int64_t t0 = 0; t0 < T; t0 += 64) {
+        double ychunk = (t0 + lane < T) ? ys[t0 + lane] : 0.0;
+        asm volatile("" : "+v"(ychunk));
+        const int nsteps = (T - t0 < 64) ? (int)(T - t0) : 64;
+        for (int slot = 0; slot < nsteps; slot++) {
+            const double y = readlane_f64(ychunk, slot);
+            Vec<4> f; double Pp;
+            predict(u, P, f, Pp);
+            double S, innov;                                             // filters_smoothers.py:55-68
+            coop4_update(meas, Pp, f.v[0], f.v[1], f.v[2], f.v[3], y, P, u.v[0], u.v[1], u.v[2], u.v[3], S, innov);
+            if (lane == slot) { S_l = S; innov_l = innov; }
+            out.store(t0 + slot, lane, P, u);
+        }
+        if (out.want_nll) cum = nll_flush_wave(S_l, innov_l, lane, nsteps, cum, out.nll ? out.nll + t0 : nullptr);
+    }
+    if (lane == 0 && io.nll && out.nll_final) io.nll[trial] = cum;
+}
+
 // ---- the d = 4 matrix-core kernels (cgp_mfma4*.hpp; lane = 16 r + 4 b + q holds P[r][q], the four blocks b are replicas): what goes on
 // around their steps.  The store calls stay in the kernels: they differ on purpose.
 // Outputs of a filter.  Rows leave through buffer windows: the per-lane byte offset is a CONSTANT (block 0 stores the 16 entries of Pf,
@@ -208,6 +259,25 @@ template <class Rhs> CGP_DEV void rk4_lane(double dt, double& m, double& P, Rhs 
     }
     m = m + (dt * am) * kSixth;
     P = P + (dt * aP) * kSixth;
+}
+
+// The same on the cooperative (DPP) layout's replicated mean and the lane's covariance entry; rhs(m, P, km, kP).  It keeps those kernels' own
+// arithmetic -- (dt k) half and a true "/ 6.0" -- which differs from rk4_lane's in the last bit: the two are not to be merged.
+template <class Rhs> CGP_DEV void coop4_rk4(double dt, Vec<4>& m, double& P, Rhs rhs) {
+    Vec<4> tm = m, am, km;
+    double tP = P, aP = 0.0, kP;
+    CGP_UNROLL for (int i = 0; i < 4; i++) am.v[i] = 0.0;
+#pragma unroll 1
+    for (int stage = 0; stage < 4; stage++) {
+        rhs(tm, tP, km, kP);
+        const double wgt = (stage == 0 || stage == 3) ? 1.0 : 2.0;
+        const double half = (stage == 2) ? 1.0 : 0.5;
+        CGP_UNROLL for (int i = 0; i < 4; i++) { am.v[i] = fma(wgt, km.v[i], am.v[i]); tm.v[i] = m.v[i] + (dt * km.v[i]) * half; }
+        aP = fma(wgt, kP, aP);
+        tP = P + (dt * kP) * half;
+    }
+    CGP_UNROLL for (int i = 0; i < 4; i++) m.v[i] = m.v[i] + (dt * am.v[i]) / 6.0;
+    P = P + (dt * aP) / 6.0;
 }
 
 // The chunks of workgroup (trial, seg) of a time-split smoother launch (SmootherIO::bsegs): [j_first, j_last] walked, [j_own, j_last] stored;

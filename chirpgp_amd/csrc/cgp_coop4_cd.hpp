@@ -96,46 +96,17 @@ __global__ void __launch_bounds__(64) cdekf4_coop_kernel(FilterIO io, ModelArgs 
     const double dt = ma.dt;
 
     const double* __restrict__ m0p = io.m0 + trial * io.m0_stride;
-    Vec<4> u;
-    u.v[0] = m0p[0]; u.v[1] = m0p[1]; u.v[2] = m0p[2]; u.v[3] = m0p[3];
-    double P = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, li, lj);
-    const int64_t T = io.T;
-    const double* __restrict__ ys = io.record(trial);
-    Coop4FilterOut out;
-    out.init(io, trial);
-
-    double cum = 0.0, S_l = 1.0, innov_l = 0.0;
-    for (int64_t t0 = 0; t0 < T; t0 += 64) {
-        double ychunk = (t0 + lane < T) ? ys[t0 + lane] : 0.0;
-        asm volatile("" : "+v"(ychunk));
-        const int nsteps = (T - t0 < 64) ? (int)(T - t0) : 64;
-        for (int slot = 0; slot < nsteps; slot++) {
-            const double y = readlane_f64(ychunk, slot);
-            Vec<4> tm = u, am, km;
-            double tP = P, aP = 0.0;
-            CGP_UNROLL for (int i = 0; i < 4; i++) am.v[i] = 0.0;
-#pragma unroll 1
-            for (int stage = 0; stage < 4; stage++) {
-                double Jr[4], Jc[4];
-                jac.eval(fm, tm, km, Jr, Jc);
-                const double kP = coop4_lyapunov(Jr, Jc, tP, gam);                   // J P + P J^T + gamma
-                const double wgt = (stage == 0 || stage == 3) ? 1.0 : 2.0;
-                const double half = (stage == 2) ? 1.0 : 0.5;
-                CGP_UNROLL for (int i = 0; i < 4; i++) { am.v[i] = fma(wgt, km.v[i], am.v[i]); tm.v[i] = u.v[i] + (dt * km.v[i]) * half; }
-                aP = fma(wgt, kP, aP);
-                tP = P + (dt * kP) * half;
-            }
-            const double f0 = u.v[0] + (dt * am.v[0]) / 6.0, f1 = u.v[1] + (dt * am.v[1]) / 6.0;
-            const double f2 = u.v[2] + (dt * am.v[2]) / 6.0, f3 = u.v[3] + (dt * am.v[3]) / 6.0;
-            const double Pp = P + (dt * aP) / 6.0;
-            double S, innov;
-            coop4_update(meas, Pp, f0, f1, f2, f3, y, P, u.v[0], u.v[1], u.v[2], u.v[3], S, innov);
-            if (lane == slot) { S_l = S; innov_l = innov; }
-            out.store(t0 + slot, lane, P, u.v[0], u.v[1], u.v[2], u.v[3]);
-        }
-        if (out.want_nll) cum = nll_flush_wave(S_l, innov_l, lane, nsteps, cum, out.nll ? out.nll + t0 : nullptr);
-    }
-    if (lane == 0 && io.nll && out.nll_final) io.nll[trial] = cum;
+    Vec<4> mean0;
+    mean0.v[0] = m0p[0]; mean0.v[1] = m0p[1]; mean0.v[2] = m0p[2]; mean0.v[3] = m0p[3];
+    const double cov0 = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, li, lj);
+    coop4_filter_walk(io, trial, lane, meas, mean0, cov0, [&](const Vec<4>& u, double P, Vec<4>& f, double& Pp) {
+        f = u; Pp = P;
+        coop4_rk4(dt, f, Pp, [&](const Vec<4>& tm, double tP, Vec<4>& km, double& kP) {
+            double Jr[4], Jc[4];
+            jac.eval(fm, tm, km, Jr, Jc);
+            kP = coop4_lyapunov(Jr, Jc, tP, gam);                                // J P + P J^T + gamma
+        });
+    });
 }
 
 __global__ void __launch_bounds__(64) cdeks4_coop_kernel(SmootherIO io, ModelArgs ma) {
@@ -155,59 +126,13 @@ __global__ void __launch_bounds__(64) cdeks4_coop_kernel(SmootherIO io, ModelArg
     load_sym<4>(ma.gamma + trial * ma.gamma_stride, gamma);
     const double gam = coop4_load_sym_entry(ma.gamma + trial * ma.gamma_stride, li, lj);
     const double dt = -ma.dt;
-    const int lr1 = dpp_i32<kRowRor4>(li), lr2 = dpp_i32<kRowRor8>(li), lr3 = dpp_i32<kRowRor12>(li);
 
-    const int64_t T = io.T;
-    const double* __restrict__ mfs = io.mfs + trial * T * 4;
-    const double* __restrict__ Pfs = io.Pfs + trial * T * 16;
-    double* __restrict__ mss = io.mss + trial * T * 4;
-    double* __restrict__ Pss = io.Pss + trial * T * 16;
-
-    Vec<4> ms;
-    load_vec<4>(mfs + (T - 1) * 4, ms);
-    double Ps = coop4_load_sym_entry(Pfs + (T - 1) * 16, li, lj);
-    if (lane < 16) Pss[(T - 1) * 16 + lane] = Pfs[(T - 1) * 16 + lane];      // filters_smoothers.py:140-142, verbatim copy
-    if (lane < 4) mss[(T - 1) * 4 + lane] = mfs[(T - 1) * 4 + lane];
-
-    for (int64_t t_hi = T - 2; t_hi >= 0; t_hi -= 64) {
-    const int nsteps = t_hi + 1 < 64 ? (int)(t_hi + 1) : 64;
-    coop4_chunk_gains(gbuf, lane, nsteps, t_hi, mfs, Pfs, gamma);      // Pf^{-1} gamma of the chunk's steps, one step per lane
-    for (int slot = 0; slot < nsteps; slot++) {
-        const int64_t t = t_hi - slot;
-        const double* gl = gbuf + slot * kGainPitch;
-        Mat<4> PG; Vec<4> mf;                                            // constant over the 4 stages
-        coop4_read_gain(gl, PG, mf);
-        // A = J + G^T: the lane's A[i][l_r] = J[i][l_r] + G[l_r][i] and A[j][l] = J[j][l] + G[l][j]
-        const double gr[4] = {gl[li * 4 + li], gl[lr1 * 4 + li], gl[lr2 * 4 + li], gl[lr3 * 4 + li]};
-        const double gc[4] = {gl[0 * 4 + lj], gl[1 * 4 + lj], gl[2 * 4 + lj], gl[3 * 4 + lj]};
-
-        Vec<4> tm = ms, am, km;
-        double tP = Ps, aP = 0.0;
-        CGP_UNROLL for (int i = 0; i < 4; i++) am.v[i] = 0.0;
-#pragma unroll 1
-        for (int stage = 0; stage < 4; stage++) {
-            double Jr[4], Jc[4];
-            jac.eval(fm, tm, km, Jr, Jc);
-            CGP_UNROLL for (int i = 0; i < 4; i++) {
-                double s = km.v[i];
-                CGP_UNROLL for (int k = 0; k < 4; k++) s = fma(PG.a[k][i], tm.v[k] - mf.v[k], s);
-                km.v[i] = s;                                                 // a(m) + gamma Pf^{-1} (m - mf)
-            }
-            CGP_UNROLL for (int r = 0; r < 4; r++) { Jr[r] += gr[r]; Jc[r] += gc[r]; }
-            const double kP = coop4_lyapunov(Jr, Jc, tP, -gam);              // A P + P A^T - gamma
-            const double wgt = (stage == 0 || stage == 3) ? 1.0 : 2.0;
-            const double half = (stage == 2) ? 1.0 : 0.5;
-            CGP_UNROLL for (int i = 0; i < 4; i++) { am.v[i] = fma(wgt, km.v[i], am.v[i]); tm.v[i] = ms.v[i] + (dt * km.v[i]) * half; }
-            aP = fma(wgt, kP, aP);
-            tP = Ps + (dt * kP) * half;
-        }
-        CGP_UNROLL for (int i = 0; i < 4; i++) ms.v[i] = ms.v[i] + (dt * am.v[i]) / 6.0;
-        Ps = Ps + (dt * aP) / 6.0;
-        if (lane < 16) Pss[t * 16 + lane] = Ps;
-        if (lane == 0) store_vec<4>(mss + t * 4, ms);
-    }
-    wave_lds_fence();
-    }
+    coop4_smoother_walk(io, trial, lane, gamma, dt, gbuf, [&](const Vec<4>& tm, double tP, const double (&gr)[4], const double (&gc)[4], Vec<4>& km, double& kP) {
+        double Jr[4], Jc[4];
+        jac.eval(fm, tm, km, Jr, Jc);
+        CGP_UNROLL for (int r = 0; r < 4; r++) { Jr[r] += gr[r]; Jc[r] += gc[r]; }   // A = J + G^T: A[i][l_r] = J[i][l_r] + G[l_r][i], A[j][l] = J[j][l] + G[l][j]
+        kP = coop4_lyapunov(Jr, Jc, tP, -gam);                                       // A P + P A^T - gamma
+    });
 }
 
 inline int launch_cdekf4_coop(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {

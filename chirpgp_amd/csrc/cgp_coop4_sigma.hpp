@@ -127,26 +127,6 @@ struct CollapsedPoint {
         }
     }
 };
-// Shared prologue of the filter kernels: outputs, measurement chunking and NLL latch live in the kernels themselves.
-struct Coop4FilterOut {
-    double* __restrict__ mfs; double* __restrict__ Pfs; double* __restrict__ nll;
-    bool nll_final, want_nll;
-    CGP_DEV void init(const FilterIO& io, int64_t trial) {
-        const int64_t T = io.T;
-        mfs = io.mfs ? io.mfs + trial * T * 4 : nullptr;
-        Pfs = io.Pfs ? io.Pfs + trial * T * 16 : nullptr;
-        nll_final = (io.flags & CGP_NLL_FINAL_ONLY) != 0;
-        nll = (io.nll && !nll_final) ? io.nll + trial * T : nullptr;
-        want_nll = io.nll != nullptr;
-    }
-    CGP_DEV void store(int64_t t, int lane, double P, double u0, double u1, double u2, double u3) const {
-        if (Pfs && lane < 16) Pfs[t * 16 + lane] = P;
-        if (mfs && lane == 0) {
-            *reinterpret_cast<double2*>(mfs + t * 4) = make_double2(u0, u1);
-            *reinterpret_cast<double2*>(mfs + t * 4 + 2) = make_double2(u2, u3);
-        }
-    }
-};
 
 // ------------------------------------------------------------------------------------------------ sgp_filter, d = 4
 // COLLAPSED (CGP_SIGMA_STANDARD sets with at most 32 groups): the quadrature of cgp_steps.hpp:sgp4_prediction_collapsed
@@ -172,12 +152,9 @@ __global__ void __launch_bounds__(64) sgp4_coop_kernel(FilterIO io, ModelArgs ma
     const int s2_idx = 5 + Sym<4>::idx(li, lj);         // this lane's entry among the totals: [wsum, mean x4, second moment x10]
 
     const double* __restrict__ m0p = io.m0 + trial * io.m0_stride;
-    double u0 = m0p[0], u1 = m0p[1], u2 = m0p[2], u3 = m0p[3];
-    double P = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, li, lj);
-    const int64_t T = io.T;
-    const double* __restrict__ ys = io.record(trial);
-    Coop4FilterOut out;
-    out.init(io, trial);
+    Vec<4> mean0;
+    mean0.v[0] = m0p[0]; mean0.v[1] = m0p[1]; mean0.v[2] = m0p[2]; mean0.v[3] = m0p[3];
+    const double cov0 = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, li, lj);
     const int ng = sg.groups();
     LanePoints pts;
     CollapsedPoint cpt;
@@ -192,61 +169,52 @@ __global__ void __launch_bounds__(64) sgp4_coop_kernel(FilterIO io, ModelArgs ma
     const double v22c = (li == 2 && lj == 2) ? 1.0 : 0.0, v33c = (li == 3 && lj == 3) ? 1.0 : 0.0;
     const double v32c = (both_lin && li != lj) ? 1.0 : 0.0;
 
-    double cum = 0.0, S_l = 1.0, innov_l = 0.0;
-    for (int64_t t0 = 0; t0 < T; t0 += 64) {
-        double ychunk = (t0 + lane < T) ? ys[t0 + lane] : 0.0;
-        asm volatile("" : "+v"(ychunk));
-        const int nsteps = (T - t0 < 64) ? (int)(T - t0) : 64;
-        for (int slot = 0; slot < nsteps; slot++) {
-            const double y = readlane_f64(ychunk, slot);
-            // ---- sigma-point prediction (filters_smoothers.py:88-121)
-            Sym<4> Pr, L; Vec<4> inv, m;
-            coop4_gather(P, Pr);
-            m.v[0] = u0; m.v[1] = u1; m.v[2] = u2; m.v[3] = u3;
-            cholesky<4>(Pr, L, inv);
-            if constexpr (COLLAPSED) {
-                const double d0 = L(0, 0) * cpt.xi0;
-                const double d1 = fma(L(1, 1), cpt.xi1, L(1, 0) * cpt.xi0);
-                const double d2 = fma(L(2, 2), cpt.xi2, fma(L(2, 1), cpt.xi1, L(2, 0) * cpt.xi0));
-                const double d3 = fma(L(3, 2), cpt.xi2, fma(L(3, 1), cpt.xi1, L(3, 0) * cpt.xi0));
-                const double h0 = u0 + d0, h1 = u1 + d1;
-                typename DM::Pre pre;
-                model.precompute(u2 + d2, pre);      // one group per lane: an anchored rotation would only add the anchor to the chain
-                const double g0 = pre.c[0] * h0 - pre.s[0] * h1, g1 = pre.s[0] * h0 + pre.c[0] * h1;
-                const double w0 = cpt.W * g0, w1 = cpt.W * g1;
-                double* tot = red + kRedChunk * kRedLd;
-                red[0 * kRedLd + lane] = w0; red[1 * kRedLd + lane] = w1;
-                red[2 * kRedLd + lane] = w0 * g0; red[3 * kRedLd + lane] = w1 * g0; red[4 * kRedLd + lane] = w1 * g1;
-                red[5 * kRedLd + lane] = w0 * d2; red[6 * kRedLd + lane] = w1 * d2;
-                red[7 * kRedLd + lane] = w0 * d3; red[8 * kRedLd + lane] = w1 * d3;
-                wave_lds_fence();
-                {
-                    const int r = lane >> 1, h = lane & 1;
-                    const double2* row = reinterpret_cast<const double2*>(red + r * kRedLd + h * 16);
-                    double sum = 0.0;
-                    if (r < 9) sum = row_sum16(row);
-                    sum += dpp_f64<kQuadSwap1>(sum);
-                    if (h == 0 && r < 9) tot[r] = sum;
-                }
-                wave_lds_fence();
-                const double poison = L(0, 0) - L(0, 0);
-                const double M0 = model.M[0], M1 = model.M[1], M2 = model.M[2], M3 = model.M[3];
-                const double f0 = tot[0], f1 = tot[1];
-                const double f2 = fma(M0, u2, M1 * u3) + poison, f3 = fma(M2, u2, M3 * u3) + poison;
-                const double t20 = fma(M0, Pr(2, 2), M1 * Pr(3, 2)), t21 = fma(M0, Pr(3, 2), M1 * Pr(3, 3));
-                const double t30 = fma(M2, Pr(2, 2), M3 * Pr(3, 2)), t31 = fma(M2, Pr(3, 2), M3 * Pr(3, 3));
-                const double V22 = fma(t20, M0, t21 * M1), V32 = fma(t30, M0, t31 * M1), V33 = fma(t30, M2, t31 * M3);
-                const double nl = tot[idx_s] - tot[li < 2 ? li : 0] * tot[lj < 2 ? lj : 0];
-                const double mixed = fma(cm0, tot[idx_x2], cm1 * tot[idx_x3]);
-                const double lin = fma(v22c, V22, fma(v32c, V32, v33c * V33));
-                const double Pp = ((both_nl ? nl : (both_lin ? lin : mixed)) + Sig) + poison;
-                wave_lds_fence();
-                double S, innov;
-                coop4_update(meas, Pp, f0, f1, f2, f3, y, P, u0, u1, u2, u3, S, innov);
-                if (lane == slot) { S_l = S; innov_l = innov; }
-                out.store(t0 + slot, lane, P, u0, u1, u2, u3);
-                continue;
+    // ---- sigma-point prediction (filters_smoothers.py:88-121)
+    coop4_filter_walk(io, trial, lane, meas, mean0, cov0, [&](const Vec<4>& m, double P, Vec<4>& mp, double& Pp) {
+        Sym<4> Pr, L; Vec<4> inv;
+        coop4_gather(P, Pr);
+        cholesky<4>(Pr, L, inv);
+        if constexpr (COLLAPSED) {
+            const double u0 = m.v[0], u1 = m.v[1], u2 = m.v[2], u3 = m.v[3];
+            const double d0 = L(0, 0) * cpt.xi0;
+            const double d1 = fma(L(1, 1), cpt.xi1, L(1, 0) * cpt.xi0);
+            const double d2 = fma(L(2, 2), cpt.xi2, fma(L(2, 1), cpt.xi1, L(2, 0) * cpt.xi0));
+            const double d3 = fma(L(3, 2), cpt.xi2, fma(L(3, 1), cpt.xi1, L(3, 0) * cpt.xi0));
+            const double h0 = u0 + d0, h1 = u1 + d1;
+            typename DM::Pre pre;
+            model.precompute(u2 + d2, pre);      // one group per lane: an anchored rotation would only add the anchor to the chain
+            const double g0 = pre.c[0] * h0 - pre.s[0] * h1, g1 = pre.s[0] * h0 + pre.c[0] * h1;
+            const double w0 = cpt.W * g0, w1 = cpt.W * g1;
+            double* tot = red + kRedChunk * kRedLd;
+            red[0 * kRedLd + lane] = w0; red[1 * kRedLd + lane] = w1;
+            red[2 * kRedLd + lane] = w0 * g0; red[3 * kRedLd + lane] = w1 * g0; red[4 * kRedLd + lane] = w1 * g1;
+            red[5 * kRedLd + lane] = w0 * d2; red[6 * kRedLd + lane] = w1 * d2;
+            red[7 * kRedLd + lane] = w0 * d3; red[8 * kRedLd + lane] = w1 * d3;
+            wave_lds_fence();
+            {
+                const int r = lane >> 1, h = lane & 1;
+                const double2* row = reinterpret_cast<const double2*>(red + r * kRedLd + h * 16);
+                double sum = 0.0;
+                if (r < 9) sum = row_sum16(row);
+                sum += dpp_f64<kQuadSwap1>(sum);
+                if (h == 0 && r < 9) tot[r] = sum;
             }
+            wave_lds_fence();
+            const double poison = L(0, 0) - L(0, 0);
+            const double M0 = model.M[0], M1 = model.M[1], M2 = model.M[2], M3 = model.M[3];
+            const double f0 = tot[0], f1 = tot[1];
+            const double f2 = fma(M0, u2, M1 * u3) + poison, f3 = fma(M2, u2, M3 * u3) + poison;
+            const double t20 = fma(M0, Pr(2, 2), M1 * Pr(3, 2)), t21 = fma(M0, Pr(3, 2), M1 * Pr(3, 3));
+            const double t30 = fma(M2, Pr(2, 2), M3 * Pr(3, 2)), t31 = fma(M2, Pr(3, 2), M3 * Pr(3, 3));
+            const double V22 = fma(t20, M0, t21 * M1), V32 = fma(t30, M0, t31 * M1), V33 = fma(t30, M2, t31 * M3);
+            const double nl = tot[idx_s] - tot[li < 2 ? li : 0] * tot[lj < 2 ? lj : 0];
+            const double mixed = fma(cm0, tot[idx_x2], cm1 * tot[idx_x3]);
+            const double lin = fma(v22c, V22, fma(v32c, V32, v33c * V33));
+            const double lin_or_mixed = both_lin ? lin : mixed;                 // (two selects of values at hand: nested in one expression the
+            Pp = ((both_nl ? nl : lin_or_mixed) + Sig) + poison;                // choice can come out as a branch around the LDS reads, 7 % of a step)
+            mp.v[0] = f0; mp.v[1] = f1; mp.v[2] = f2; mp.v[3] = f3;
+            wave_lds_fence();
+        } else {
             double acc[15];
             CGP_UNROLL for (int k = 0; k < 15; k++) acc[k] = 0.0;
             if (pts.ok) {
@@ -292,18 +260,11 @@ __global__ void __launch_bounds__(64) sgp4_coop_kernel(FilterIO io, ModelArgs ma
             }
             const double* tot = coop_reduce_to_lds<15>(acc, red, lane, ng <= 32);
             const double wsum = tot[0];
-            const double f0 = tot[1], f1 = tot[2], f2 = tot[3], f3 = tot[4];
+            mp.v[0] = tot[1]; mp.v[1] = tot[2]; mp.v[2] = tot[3]; mp.v[3] = tot[4];
             // Pp = E[f f^T + Sigma] - mp mp^T, this lane's entry
-            const double Pp = fma(wsum, Sig, tot[s2_idx]) - tot[1 + li] * tot[1 + lj];
-            // ---- update
-            double S, innov;
-            coop4_update(meas, Pp, f0, f1, f2, f3, y, P, u0, u1, u2, u3, S, innov);
-            if (lane == slot) { S_l = S; innov_l = innov; }
-            out.store(t0 + slot, lane, P, u0, u1, u2, u3);
+            Pp = fma(wsum, Sig, tot[s2_idx]) - tot[1 + li] * tot[1 + lj];
         }
-        if (out.want_nll) cum = nll_flush_wave(S_l, innov_l, lane, nsteps, cum, out.nll ? out.nll + t0 : nullptr);
-    }
-    if (lane == 0 && io.nll && out.nll_final) io.nll[trial] = cum;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ cd sigma-point moment ODE
@@ -457,13 +418,9 @@ __global__ void __launch_bounds__(64) cdsgp4_coop_kernel(FilterIO io, ModelArgs 
     const int cij_idx = 4 + li * 4 + lj, cji_idx = 4 + lj * 4 + li;
 
     const double* __restrict__ m0p = io.m0 + trial * io.m0_stride;
-    Vec<4> u;
-    u.v[0] = m0p[0]; u.v[1] = m0p[1]; u.v[2] = m0p[2]; u.v[3] = m0p[3];
-    double P = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, li, lj);
-    const int64_t T = io.T;
-    const double* __restrict__ ys = io.record(trial);
-    Coop4FilterOut out;
-    out.init(io, trial);
+    Vec<4> mean0;
+    mean0.v[0] = m0p[0]; mean0.v[1] = m0p[1]; mean0.v[2] = m0p[2]; mean0.v[3] = m0p[3];
+    const double cov0 = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, li, lj);
     const int ng = sg.groups();
     LanePoints pts;
     CollapsedPoint cpt;
@@ -471,39 +428,13 @@ __global__ void __launch_bounds__(64) cdsgp4_coop_kernel(FilterIO io, ModelArgs 
     if constexpr (COLLAPSED) { cpt.load(sg, lane); role.init(li, lj, model.gam); }
     else pts.load(sg, lane);
 
-    double cum = 0.0, S_l = 1.0, innov_l = 0.0;
-    for (int64_t t0 = 0; t0 < T; t0 += 64) {
-        double ychunk = (t0 + lane < T) ? ys[t0 + lane] : 0.0;
-        asm volatile("" : "+v"(ychunk));
-        const int nsteps = (T - t0 < 64) ? (int)(T - t0) : 64;
-        for (int slot = 0; slot < nsteps; slot++) {
-            const double y = readlane_f64(ychunk, slot);
-            // ---- RK4 on (m, P) (quadratures.py:34-54), same operation order as cgp_steps.hpp:rk4_m_cov
-            Vec<4> tm = u, am, km;
-            double tP = P, aP = 0.0, kP;
-            CGP_UNROLL for (int i = 0; i < 4; i++) am.v[i] = 0.0;
-#pragma unroll 1
-            for (int stage = 0; stage < 4; stage++) {
-                if constexpr (COLLAPSED) coop4_cd_sgp_rhs_collapsed<SM>(model, cpt, role, red, lane, gam, tm, tP, km, kP);
-                else coop4_cd_sgp_rhs<SM>(model, sg, pts, ng, red, lane, cij_idx, cji_idx, gam, tm, tP, km, kP);
-                const double wgt = (stage == 0 || stage == 3) ? 1.0 : 2.0;
-                const double half = (stage == 2) ? 1.0 : 0.5;
-                CGP_UNROLL for (int i = 0; i < 4; i++) { am.v[i] = fma(wgt, km.v[i], am.v[i]); tm.v[i] = u.v[i] + (dt * km.v[i]) * half; }
-                aP = fma(wgt, kP, aP);
-                tP = P + (dt * kP) * half;
-            }
-            const double f0 = u.v[0] + (dt * am.v[0]) / 6.0, f1 = u.v[1] + (dt * am.v[1]) / 6.0;
-            const double f2 = u.v[2] + (dt * am.v[2]) / 6.0, f3 = u.v[3] + (dt * am.v[3]) / 6.0;
-            const double Pp = P + (dt * aP) / 6.0;
-            // ---- update
-            double S, innov;
-            coop4_update(meas, Pp, f0, f1, f2, f3, y, P, u.v[0], u.v[1], u.v[2], u.v[3], S, innov);
-            if (lane == slot) { S_l = S; innov_l = innov; }
-            out.store(t0 + slot, lane, P, u.v[0], u.v[1], u.v[2], u.v[3]);
-        }
-        if (out.want_nll) cum = nll_flush_wave(S_l, innov_l, lane, nsteps, cum, out.nll ? out.nll + t0 : nullptr);
-    }
-    if (lane == 0 && io.nll && out.nll_final) io.nll[trial] = cum;
+    coop4_filter_walk(io, trial, lane, meas, mean0, cov0, [&](const Vec<4>& u, double P, Vec<4>& f, double& Pp) {
+        f = u; Pp = P;
+        coop4_rk4(dt, f, Pp, [&](const Vec<4>& tm, double tP, Vec<4>& km, double& kP) {
+            if constexpr (COLLAPSED) coop4_cd_sgp_rhs_collapsed<SM>(model, cpt, role, red, lane, gam, tm, tP, km, kP);
+            else coop4_cd_sgp_rhs<SM>(model, sg, pts, ng, red, lane, cij_idx, cji_idx, gam, tm, tP, km, kP);
+        });
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ backward gains, a chunk at a time
@@ -538,6 +469,52 @@ CGP_DEV void coop4_read_gain(const double* g, Mat<4>& PG, Vec<4>& mf) {
     mf.v[0] = a.x; mf.v[1] = a.y; mf.v[2] = b.x; mf.v[3] = b.y;
 }
 
+// THE backward loop of the cooperative continuous-discrete smoothers: row T - 1 copied (filters_smoothers.py:140-142, verbatim), then chunks
+// of 64 steps -- their gains, and per step the RK4 step from t + 1 to t (dt < 0) and the stores.  rhs(m, P, gr, gc, km, kP) is what a kernel
+// keeps to itself: its drift km and covariance rate kP, for which it gets the lane's entries of G = Pf^{-1} gamma (constant over the four
+// stages) -- gr[r] = G[l_r][i] of the rows l_r the DPP row rotations deliver (discovered by rotating the row index itself), gc[l] = G[l][j];
+// the loop adds the mean's G^T (m - mf).
+template <class Rhs>
+CGP_DEV void coop4_smoother_walk(const SmootherIO& io, int64_t trial, int lane, const Sym<4>& gamma, double dt, double* gbuf, Rhs rhs) {
+    const int li = (lane >> 2) & 3, lj = lane & 3;
+    const int lr1 = dpp_i32<kRowRor4>(li), lr2 = dpp_i32<kRowRor8>(li), lr3 = dpp_i32<kRowRor12>(li);
+    const int64_t T = io.T;
+    const double* __restrict__ mfs = io.mfs + trial * T * 4;
+    const double* __restrict__ Pfs = io.Pfs + trial * T * 16;
+    double* __restrict__ mss = io.mss + trial * T * 4;
+    double* __restrict__ Pss = io.Pss + trial * T * 16;
+
+    Vec<4> ms;
+    load_vec<4>(mfs + (T - 1) * 4, ms);
+    double Ps = coop4_load_sym_entry(Pfs + (T - 1) * 16, li, lj);
+    if (lane < 16) Pss[(T - 1) * 16 + lane] = Pfs[(T - 1) * 16 + lane];
+    if (lane < 4) mss[(T - 1) * 4 + lane] = mfs[(T - 1) * 4 + lane];
+
+    for (int64_t t_hi = T - 2; t_hi >= 0; t_hi -= 64) {
+        const int nsteps = t_hi + 1 < 64 ? (int)(t_hi + 1) : 64;
+        coop4_chunk_gains(gbuf, lane, nsteps, t_hi, mfs, Pfs, gamma);
+        for (int slot = 0; slot < nsteps; slot++) {
+            const int64_t t = t_hi - slot;
+            const double* gl = gbuf + slot * kGainPitch;
+            Mat<4> PG; Vec<4> mf;
+            coop4_read_gain(gl, PG, mf);
+            const double gr[4] = {gl[li * 4 + li], gl[lr1 * 4 + li], gl[lr2 * 4 + li], gl[lr3 * 4 + li]};
+            const double gc[4] = {gl[0 * 4 + lj], gl[1 * 4 + lj], gl[2 * 4 + lj], gl[3 * 4 + lj]};
+            coop4_rk4(dt, ms, Ps, [&](const Vec<4>& tm, double tP, Vec<4>& km, double& kP) {
+                rhs(tm, tP, gr, gc, km, kP);
+                CGP_UNROLL for (int i = 0; i < 4; i++) {
+                    double s = km.v[i];
+                    CGP_UNROLL for (int k = 0; k < 4; k++) s = fma(PG.a[k][i], tm.v[k] - mf.v[k], s);
+                    km.v[i] = s;
+                }
+            });
+            if (lane < 16) Pss[t * 16 + lane] = Ps;
+            if (lane == 0) store_vec<4>(mss + t * 4, ms);
+        }
+        wave_lds_fence();
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ cd_sgp_smoother, d = 4
 // Backward RK4 with  dm = _m + G^T (m - mf),  dP = _P + G^T P + P G - 2 gamma,  G = Pf^{-1} gamma  (filters_smoothers.py:615-621).
 // G is constant over the four stages (hoisted, as in cgp_steps.hpp); its entries reach the lanes through LDS:
@@ -563,8 +540,6 @@ __global__ void __launch_bounds__(64) cdsgps4_coop_kernel(SmootherIO io, ModelAr
     const double gam = coop4_load_sym_entry(ma.gamma + trial * ma.gamma_stride, li, lj);
     const double dt = -ma.dt;
     const int cij_idx = 4 + li * 4 + lj, cji_idx = 4 + lj * 4 + li;
-    // source rows of the three row rotations, discovered by rotating the row index itself
-    const int lr1 = dpp_i32<kRowRor4>(li), lr2 = dpp_i32<kRowRor8>(li), lr3 = dpp_i32<kRowRor12>(li);
     const int ng = sg.groups();
     LanePoints pts;
     CollapsedPoint cpt;
@@ -572,64 +547,20 @@ __global__ void __launch_bounds__(64) cdsgps4_coop_kernel(SmootherIO io, ModelAr
     if constexpr (COLLAPSED) { cpt.load(sg, lane); role.init(li, lj, model.gam); }
     else pts.load(sg, lane);
 
-    const int64_t T = io.T;
-    const double* __restrict__ mfs = io.mfs + trial * T * 4;
-    const double* __restrict__ Pfs = io.Pfs + trial * T * 16;
-    double* __restrict__ mss = io.mss + trial * T * 4;
-    double* __restrict__ Pss = io.Pss + trial * T * 16;
-
-    Vec<4> ms;
-    load_vec<4>(mfs + (T - 1) * 4, ms);
-    double Ps = coop4_load_sym_entry(Pfs + (T - 1) * 16, li, lj);
-    if (lane < 16) Pss[(T - 1) * 16 + lane] = Pfs[(T - 1) * 16 + lane];      // filters_smoothers.py:140-142, verbatim copy
-    if (lane < 4) mss[(T - 1) * 4 + lane] = mfs[(T - 1) * 4 + lane];
-
-    for (int64_t t_hi = T - 2; t_hi >= 0; t_hi -= 64) {
-    const int nsteps = t_hi + 1 < 64 ? (int)(t_hi + 1) : 64;
-    coop4_chunk_gains(gbuf, lane, nsteps, t_hi, mfs, Pfs, gamma);
-    for (int slot = 0; slot < nsteps; slot++) {
-        const int64_t t = t_hi - slot;
-        const double* gl = gbuf + slot * kGainPitch;
-        Mat<4> PG; Vec<4> mf;
-        coop4_read_gain(gl, PG, mf);
-        const double gr0 = gl[li * 4 + li], gr1 = gl[lr1 * 4 + li], gr2 = gl[lr2 * 4 + li], gr3 = gl[lr3 * 4 + li];
-        const double gc0 = gl[0 * 4 + lj], gc1 = gl[1 * 4 + lj], gc2 = gl[2 * 4 + lj], gc3 = gl[3 * 4 + lj];
-
-        Vec<4> tm = ms, am, km;
-        double tP = Ps, aP = 0.0, kP;
-        CGP_UNROLL for (int i = 0; i < 4; i++) am.v[i] = 0.0;
-#pragma unroll 1
-        for (int stage = 0; stage < 4; stage++) {
-            // (_m, _P), _P includes + gamma
-            if constexpr (COLLAPSED) coop4_cd_sgp_rhs_collapsed<SM>(model, cpt, role, red, lane, gam, tm, tP, km, kP);
-            else coop4_cd_sgp_rhs<SM>(model, sg, pts, ng, red, lane, cij_idx, cji_idx, gam, tm, tP, km, kP);
-            CGP_UNROLL for (int i = 0; i < 4; i++) {
-                double s = km.v[i];
-                CGP_UNROLL for (int k = 0; k < 4; k++) s = fma(PG.a[k][i], tm.v[k] - mf.v[k], s);
-                km.v[i] = s;                                                                        // _m + G^T (m - mf)
-            }
-            double tij = gr0 * tP;                                                                  // (G^T P)[i][j]
-            tij = fma(gr1, dpp_f64<kRowRor4>(tP), tij);
-            tij = fma(gr2, dpp_f64<kRowRor8>(tP), tij);
-            tij = fma(gr3, dpp_f64<kRowRor12>(tP), tij);
-            double tji = gc0 * dpp_f64<kQuadBcast0>(tP);                                            // (P G)[i][j] = (G^T P)[j][i]
-            tji = fma(gc1, dpp_f64<kQuadBcast1>(tP), tji);
-            tji = fma(gc2, dpp_f64<kQuadBcast2>(tP), tji);
-            tji = fma(gc3, dpp_f64<kQuadBcast3>(tP), tji);
-            kP = (kP + (tij + tji)) - 2.0 * gam;
-            const double wgt = (stage == 0 || stage == 3) ? 1.0 : 2.0;
-            const double half = (stage == 2) ? 1.0 : 0.5;
-            CGP_UNROLL for (int i = 0; i < 4; i++) { am.v[i] = fma(wgt, km.v[i], am.v[i]); tm.v[i] = ms.v[i] + (dt * km.v[i]) * half; }
-            aP = fma(wgt, kP, aP);
-            tP = Ps + (dt * kP) * half;
-        }
-        CGP_UNROLL for (int i = 0; i < 4; i++) ms.v[i] = ms.v[i] + (dt * am.v[i]) / 6.0;
-        Ps = Ps + (dt * aP) / 6.0;
-        if (lane < 16) Pss[t * 16 + lane] = Ps;
-        if (lane == 0) store_vec<4>(mss + t * 4, ms);
-    }
-    wave_lds_fence();
-    }
+    coop4_smoother_walk(io, trial, lane, gamma, dt, gbuf, [&](const Vec<4>& tm, double tP, const double (&gr)[4], const double (&gc)[4], Vec<4>& km, double& kP) {
+        // (_m, _P), _P includes + gamma
+        if constexpr (COLLAPSED) coop4_cd_sgp_rhs_collapsed<SM>(model, cpt, role, red, lane, gam, tm, tP, km, kP);
+        else coop4_cd_sgp_rhs<SM>(model, sg, pts, ng, red, lane, cij_idx, cji_idx, gam, tm, tP, km, kP);
+        double tij = gr[0] * tP;                                                                // (G^T P)[i][j]
+        tij = fma(gr[1], dpp_f64<kRowRor4>(tP), tij);
+        tij = fma(gr[2], dpp_f64<kRowRor8>(tP), tij);
+        tij = fma(gr[3], dpp_f64<kRowRor12>(tP), tij);
+        double tji = gc[0] * dpp_f64<kQuadBcast0>(tP);                                          // (P G)[i][j] = (G^T P)[j][i]
+        tji = fma(gc[1], dpp_f64<kQuadBcast1>(tP), tji);
+        tji = fma(gc[2], dpp_f64<kQuadBcast2>(tP), tji);
+        tji = fma(gc[3], dpp_f64<kQuadBcast3>(tP), tji);
+        kP = (kP + (tij + tji)) - 2.0 * gam;
+    });
 }
 
 // (the collapsed quadrature where the set allows it: collapsed_ok, cgp_route.hpp)

@@ -193,13 +193,49 @@ __global__ void __launch_bounds__(64) cdsgp4_mfma_kernel(FilterIO io, ModelArgs 
     } else out.store_nll_total(io, trial, lane, cum);
 }
 
+// THE backward loop of the continuous-discrete smoothers in this layout, for the (trial, segment) that `sio` decoded: per chunk of 64 steps
+// the gains G = Pf^{-1} gamma, lane-parallel (cgp_coop4_sigma.hpp:coop4_chunk_gains), read back from LDS one entry per lane (Gd = G[r][q], and
+// mf in column form); per step RK4 from t + 1 to t (dt < 0) on rhs(m, P, Gd, mf, km, kP) -- a kernel's own -- and the stores.
+// SPLIT (round 6; cgp_smoother_time_split): one wavefront per (trial, segment) -- see SmootherIO::bsegs.  Chunk j covers the rows
+// T - 2 - 64 j - 63 .. T - 2 - 64 j; segment s owns the chunks [s cps, (s + 1) cps) and starts burn_chunks chunks earlier in its walk
+// (later in time) from the FILTERING row there; the burn-in chunks store through a zero-byte window.
+template <bool SPLIT, class Rhs>
+CGP_DEV void cd4_mfma_smoother_walk(const SmootherIO& io, Tile4SmootherIO& sio, int lane, const Sym<4>& gamma, double dt, double* gbuf, Rhs rhs) {
+    const int r = lane >> 4, q = lane & 3;
+    if (!sio.template init<SPLIT>(io, lane)) return;
+    const int64_t T = io.T;
+    const double* __restrict__ mfs = sio.mfs;
+    const double* __restrict__ Pfs = sio.Pfs;
+    const SmootherSpan sp = sio.sp;
+    double ms = mfs[sp.t_start * 4 + q];                                 // the mean in column form
+    double Ps = coop4_load_sym_entry(Pfs + sp.t_start * 16, r, q);
+
+    for (int64_t j = sp.j_first; j <= sp.j_last; j++) {
+        const int64_t t_hi = T - 2 - 64 * j;
+        const bool own = j >= sp.j_own;
+        if constexpr (SPLIT) { if (j == sp.j_own) sio.junction_store(io, lane, ms, Ps); }
+        const OobWindow& oP = sio.P_window(own);
+        const OobWindow& om = sio.m_window(own);
+        const int nsteps = t_hi + 1 < 64 ? (int)(t_hi + 1) : 64;
+        coop4_chunk_gains(gbuf, lane, nsteps, t_hi, mfs, Pfs, gamma);
+        for (int slot = 0; slot < nsteps; slot++) {
+            const unsigned t = (unsigned)(t_hi - slot);
+            const double* gl = gbuf + slot * kGainPitch;
+            const double Gd = gl[r * 4 + q];
+            const double mf = gl[16 + q];
+            rk4_lane(dt, ms, Ps, [&](double tm, double tP, double& km, double& kP) { rhs(tm, tP, Gd, mf, km, kP); });
+            oP.store(Ps, t * 128u + sio.offP);
+            om.store(ms, t * 32u + sio.offm);
+        }
+        wave_lds_fence();
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ cd_sgp_smoother, d = 4
 // Backward RK4 with  dm = _m + G^T (m - mf),  dP = _P + G^T P + P G - 2 gamma,  G = Pf^{-1} gamma  (filters_smoothers.py:615-621).
 // G is constant over the four stages and computed a chunk of 64 steps at a time, lane-parallel (cgp_coop4_sigma.hpp:
 // coop4_chunk_gains); the walk reads it back from LDS one entry per lane, and mf in column form.
-// SPLIT (round 6; cgp_smoother_time_split): one wavefront per (trial, segment) -- see SmootherIO::bsegs.  Chunk j covers the rows
-// T - 2 - 64 j - 63 .. T - 2 - 64 j; segment s owns the chunks [s cps, (s + 1) cps) and starts burn_chunks chunks earlier in its walk
-// (later in time) from the FILTERING row there; the burn-in chunks store through a zero-byte window.
+// SPLIT: cd4_mfma_smoother_walk.
 template <class SM, bool TWO, bool SPLIT = false>
 __global__ void __launch_bounds__(64) cdsgps4_mfma_kernel(SmootherIO io, ModelArgs ma) {
     static_assert(SM::D == 4, "d = 4 kernel");
@@ -224,41 +260,13 @@ __global__ void __launch_bounds__(64) cdsgps4_mfma_kernel(SmootherIO io, ModelAr
     K.init(r, q, grp.W, model.lam, model.gam, coop4_load_sym_entry(ma.gamma + trial * ma.gamma_stride, r, q));
     SoftplusRegs R;
     R.init();
-    const double dt = -ma.dt;
-
-    if (!sio.template init<SPLIT>(io, lane)) return;
-    const int64_t T = io.T;
-    const double* __restrict__ mfs = sio.mfs;
-    const double* __restrict__ Pfs = sio.Pfs;
-    const SmootherSpan sp = sio.sp;
-    double ms = mfs[sp.t_start * 4 + q];                                 // the mean in column form
-    double Ps = coop4_load_sym_entry(Pfs + sp.t_start * 16, r, q);
-
-    for (int64_t j = sp.j_first; j <= sp.j_last; j++) {
-        const int64_t t_hi = T - 2 - 64 * j;
-        const bool own = j >= sp.j_own;
-        if constexpr (SPLIT) { if (j == sp.j_own) sio.junction_store(io, lane, ms, Ps); }
-        const OobWindow& oP = sio.P_window(own);
-        const OobWindow& om = sio.m_window(own);
-        const int nsteps = t_hi + 1 < 64 ? (int)(t_hi + 1) : 64;
-        coop4_chunk_gains(gbuf, lane, nsteps, t_hi, mfs, Pfs, gamma);
-        for (int slot = 0; slot < nsteps; slot++) {
-            const unsigned t = (unsigned)(t_hi - slot);
-            const double* gl = gbuf + slot * kGainPitch;
-            const double Gd = gl[r * 4 + q];                             // G[r][q]: A operand G[k][r'], B operand G[k][q']
-            const double mf = gl[16 + q];
-            rk4_lane(dt, ms, Ps, [&](double tm, double tP, double& km, double& kP) {
-                cd4_mfma_rhs<TWO>(model, R, K, grp, tm, tP, km, kP);    // (_m, _P), _P includes + gamma
-                const double drow = mfma4x4(tm - mf, K.ident, 0.0);     // m - mf from column to row form: [r][q] <- [q][r]
-                km = mfma4x4(drow, Gd, km);                             // _m + G^T (m - mf): sum_k (m - mf)[k] G[k][q]
-                const double sym = mfma4x4(Gd, tP, mfma4x4(tP, Gd, 0.0));                           // G^T P + P G (P symmetric)
-                kP = (kP + sym) - 2.0 * K.gam;
-            });
-            oP.store(Ps, t * 128u + sio.offP);
-            om.store(ms, t * 32u + sio.offm);
-        }
-        wave_lds_fence();
-    }
+    cd4_mfma_smoother_walk<SPLIT>(io, sio, lane, gamma, -ma.dt, gbuf, [&](double tm, double tP, double Gd, double mf, double& km, double& kP) {
+        cd4_mfma_rhs<TWO>(model, R, K, grp, tm, tP, km, kP);            // (_m, _P), _P includes + gamma
+        const double drow = mfma4x4(tm - mf, K.ident, 0.0);             // m - mf from column to row form: [r][q] <- [q][r]
+        km = mfma4x4(drow, Gd, km);                                     // _m + G^T (m - mf): sum_k (m - mf)[k] G[k][q]   (A operand G[k][r'], B operand G[k][q'])
+        const double sym = mfma4x4(Gd, tP, mfma4x4(tP, Gd, 0.0));       // G^T P + P G (P symmetric)
+        kP = (kP + sym) - 2.0 * K.gam;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ cd_ekf / cd_eks, d = 4
@@ -366,42 +374,15 @@ __global__ void __launch_bounds__(64) cdeks4_mfma_kernel(SmootherIO io, ModelArg
     R.init();
     Sym<4> gamma;
     load_sym<4>(ma.gamma + trial * ma.gamma_stride, gamma);
-    const double dt = -ma.dt, fs = model.fs;
-
-    if (!sio.template init<SPLIT>(io, lane)) return;
-    const int64_t T = io.T;
-    const double* __restrict__ mfs = sio.mfs;
-    const double* __restrict__ Pfs = sio.Pfs;
-    const SmootherSpan sp = sio.sp;
-    double ms = mfs[sp.t_start * 4 + q];
-    double Ps = coop4_load_sym_entry(Pfs + sp.t_start * 16, r, q);
-
-    for (int64_t j = sp.j_first; j <= sp.j_last; j++) {
-        const int64_t t_hi = T - 2 - 64 * j;
-        const bool own = j >= sp.j_own;
-        if constexpr (SPLIT) { if (j == sp.j_own) sio.junction_store(io, lane, ms, Ps); }
-        const OobWindow& oP = sio.P_window(own);
-        const OobWindow& om = sio.m_window(own);
-        const int nsteps = t_hi + 1 < 64 ? (int)(t_hi + 1) : 64;
-        coop4_chunk_gains(gbuf, lane, nsteps, t_hi, mfs, Pfs, gamma);  // Pf^{-1} gamma of the chunk's steps, one step per lane
-        for (int slot = 0; slot < nsteps; slot++) {
-            const unsigned t = (unsigned)(t_hi - slot);
-            const double* gl = gbuf + slot * kGainPitch;
-            const double Gd = gl[r * 4 + q];                             // G[r][q] = (G^T)[q][r]: the lane's entry of A^T - J^T
-            const double mf = gl[16 + q];
-            rk4_lane(dt, ms, Ps, [&](double tm, double tP, double& km, double& kP) {
-                double JT;
-                cd4_ekf_eval(R, K, Jc, fs, tm, km, JT);
-                const double drow = mfma4x4(tm - mf, K.ident, 0.0);     // m - mf from column to row form
-                km = mfma4x4(drow, Gd, km);                             // a(m) + G^T (m - mf)
-                const double AP = mfma4x4(JT + Gd, tP, 0.0);            // sum_k A[r][k] P[k][q], A = J + G^T
-                kP = mfma4x4(AP, K.ident, AP - K.gam);                  // (A P)^T + A P - gamma
-            });
-            oP.store(Ps, t * 128u + sio.offP);
-            om.store(ms, t * 32u + sio.offm);
-        }
-        wave_lds_fence();
-    }
+    const double fs = model.fs;
+    cd4_mfma_smoother_walk<SPLIT>(io, sio, lane, gamma, -ma.dt, gbuf, [&](double tm, double tP, double Gd, double mf, double& km, double& kP) {
+        double JT;
+        cd4_ekf_eval(R, K, Jc, fs, tm, km, JT);
+        const double drow = mfma4x4(tm - mf, K.ident, 0.0);             // m - mf from column to row form
+        km = mfma4x4(drow, Gd, km);                                     // a(m) + G^T (m - mf)
+        const double AP = mfma4x4(JT + Gd, tP, 0.0);                    // sum_k A[r][k] P[k][q], A = J + G^T: G[r][q] = (G^T)[q][r] is the lane's entry of A^T - J^T
+        kP = mfma4x4(AP, K.ident, AP - K.gam);                          // (A P)^T + A P - gamma
+    });
 }
 
 inline int launch_cdekf4_mfma(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {

@@ -617,10 +617,22 @@ def test_nan_in_the_d4_sigma_point_kernels(kw):
 
 @pytest.mark.parametrize('T', [1, 2, 63, 64, 65, 129])
 def test_ragged_lengths_cd_sigma_point(T):
-    """The 64-step chunks of the matrix-core cd_sgp filter (measurements, NLL latch) and smoother (backward gains)."""
+    """The 64-step chunks of the wave-per-trial continuous-discrete kernels at d = 4, matrix-core (cgp_mfma4_cd.hpp) and DPP (cgp_coop4*.hpp)
+    layout: the forward loops (measurements, NLL latch) and the backward loops (gains) that the kernels of a layout share."""
     c = cs.chirp_case(T=T, seed=37)
-    only = ('cd_sgp_filter', 'cd_sgp_smoother')
-    bk.compare(bk.run_pairs('hip', c, hip_kw=WAVE, only=only), bk.run_pairs('port', c, only=only), RTOL, f'cd T={T}')
+    only = ('cd_sgp_filter', 'cd_sgp_smoother', 'cd_ekf', 'cd_eks')
+    want = bk.run_pairs('port', c, only=only)
+    for name, kw in (('wave', WAVE), ('wave_dpp', WAVE_DPP)):
+        bk.compare(bk.run_pairs('hip', c, hip_kw=kw, only=only), want, RTOL, f'cd T={T} {name}')
+
+
+def test_ragged_length_dpp_literal_sigma_point():
+    """One step past a chunk with Gauss-Hermite order 4: its 64 groups take the DPP kernels that sum over every point (not collapsed)."""
+    from chirpgp_amd.quadratures import SigmaPoints
+    c = cs.chirp_case(T=65, seed=37)
+    c.sgps = SigmaPoints.gauss_hermite(4, 4)
+    only = ('sgp_filter', 'sgp_smoother', 'cd_sgp_filter', 'cd_sgp_smoother')
+    bk.compare(bk.run_pairs('hip', c, hip_kw=WAVE_DPP, only=only), bk.run_pairs('port', c, only=only), RTOL, 'gh4 T=65')
 
 
 # ------------------------------------------------------------------ BASELINE config C1
