@@ -776,7 +776,8 @@ def gaussian_expectation(ms, chol_Ps, xi, w, func=FN_SOFTPLUS):
 
 
 def debug_math(op, x):
-    """In-kernel elementary functions on the device (test hook): returns (out0, out1) as NumPy arrays."""
+    """In-kernel elementary functions on the device (test hook): returns (out0, out1) as NumPy arrays.  The two-argument ops
+    (DEBUG_MATH_PAIR_OPS) take x as (n, 2) pairs and return n results."""
     torch = _torch()
     xd = dev(x).reshape(-1)
     with torch.cuda.device(xd.device):
@@ -784,7 +785,11 @@ def debug_math(op, x):
         o0, o1 = torch.empty_like(xd), torch.empty_like(xd)
         rc = load_library().cgp_debug_math(ctx, int(op), _ptr(xd), xd.numel(), _ptr(o0), _ptr(o1), _stream())
         _check(ctx, rc, 'cgp_debug_math')
-        return o0.cpu().numpy(), o1.cpu().numpy()
+        keep = xd.numel() // 2 if int(op) in DEBUG_MATH_PAIR_OPS else xd.numel()
+        return o0[:keep].cpu().numpy(), o1[:keep].cpu().numpy()
+
+
+DEBUG_MATH_PAIR_OPS = (22, 23, 25)
 
 
 def _init_struct(H, Xi, m0, P0, d, B, keep):

@@ -102,10 +102,17 @@ __global__ void __launch_bounds__(256) smooth_select_kernel(const double* __rest
         sel_write(sel, ghrule, i, mss[i * d + sel.comp], Pss[i * d * d + sel.comp * (d + 1)]);
 }
 
+// Scales of the debug ops that evaluate a form with its scales folded into the coefficients (ops 14 / 15): neither is a power of two, so a
+// coefficient that missed its scale shows.  The test divides them out again (tests/fastmath_points.py holds the same two numbers).
+constexpr double kDebugScale = 0.0439822971502571, kDebugDscale = 2.7;
+
 __global__ void __launch_bounds__(256) debug_math_kernel(int op, const double* __restrict__ x, int64_t n,
                                                          double* __restrict__ o0, double* __restrict__ o1) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const double v = x[i];
+    const bool pairs = op == 22 || op == 23 || op == 25;                 // two-argument ops: (x[2 i], x[2 i + 1]) -> o0[i], o1[i]
+    const int64_t count = pairs ? n / 2 : n;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+        const double v = pairs ? x[2 * i] : x[i];
+        const double v2 = pairs ? x[2 * i + 1] : 0.0;
         double a = 0.0, b = 0.0;
         switch (op) {
         case 0: a = fast_exp(v); break;
@@ -116,6 +123,53 @@ __global__ void __launch_bounds__(256) debug_math_kernel(int op, const double* _
         case 9: a = rcp_nr1(v); break;
         case 10: { bool ok; softplus_pair_any(v, a, b, ok); if (!ok) { a = __builtin_nan(""); b = a; } break; }      // (not ok -> NaN: the caller's fallback)
         case 11: softplus_pair_mid(v, a, b); break;                                                                   // (valid for |v| <= 2)
+        // 12 - 15: the softplus of the speculative EKF step as ekf4_mfma_step_spec1 (cgp_mfma4.hpp) writes it, per regime, with th = 0 and kja = 1
+        case 12: {                                                                                                    // COMMON, 1.5 <= v < 700
+            SpecRegs R; R.init();
+            const double t = exp_neg_lean1(R, v);
+            const double lin = fma(1.0, v, -0.0);
+            double qa;
+            softplus_tail_lean(R, t, qa, b);
+            a = fma(qa, t, lin);
+            break;
+        }
+        case 13: {                                                                                                    // LOW, -700 < v <= -1.5
+            SpecRegs R; R.init();
+            const double kja = 1.0, th = 0.0;
+            const double t = exp_neg_lean1(R, -v);                                                                    // t = exp(v)
+            const double lin = -th;
+            double qa, dsp;
+            softplus_tail_lean(R, t, qa, dsp);
+            a = fma(qa, t, lin);
+            b = (kja * t) * dsp;
+            break;
+        }
+        case 14: {                                                                                                    // HIGH, 5 <= v < 700: kDebugScale x, kDebugDscale x
+            SpecRegs R; R.init();
+            SpecRegsHigh RH; RH.init(kDebugScale, kDebugDscale);
+            const double t = exp_neg_high(R, RH, v);
+            const double lin = fma(kDebugScale, v, -0.0);
+            double qa;
+            softplus_tail_high(RH, t, qa, b);
+            a = fma(qa, t, lin);
+            break;
+        }
+        case 15: {                                                                                                    // MID, |v| <= 2: kDebugScale x, kDebugDscale x
+            SpecRegsMid M; M.init(kDebugScale, kDebugDscale);
+            double ga, hj;
+            softplus_mid_polys(M, v, ga, hj);
+            a = ga + fma(0.5 * kDebugScale, v, -0.0);
+            b = fma(v, hj, 0.5 * kDebugDscale);
+            break;
+        }
+        case 18: a = fast_log_ge1_finite(v); break;
+        case 19: a = softplus_batch(v); break;
+        case 20: softplus_pair_batch(v, a, b); break;
+        case 21: fast_sincos_small(v, a, b); break;
+        case 22: a = div_nr(v, v2); break;
+        case 23: a = div_nr1(v, v2); break;
+        case 24: sqrt_rsqrt(v, a, b); break;
+        case 25: a = nll_increment(v, v2); break;
         default: softplus_pair(v, a, b); break;
         }
         o0[i] = a;
@@ -126,11 +180,15 @@ __global__ void __launch_bounds__(256) debug_math_kernel(int op, const double* _
 // The wave-uniform variants: one input element per wavefront (all 64 lanes evaluate the same argument).
 __global__ void __launch_bounds__(64) debug_math_uniform_kernel(int op, const double* __restrict__ x, int64_t n,
                                                                 double* __restrict__ o0, double* __restrict__ o1) {
+    FastMathRegs F;
+    if (op == 16 || op == 17) F.init();
     for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
         const double v = x[i];
         double a, b;
         if (op == 5) softplus_pair_uniform(v, a, b);
         else if (op == 8) { SpecRegs R; R.init(); double q; const double t = exp_neg_lean(R, v); softplus_tail_lean(R, t, q, b); a = fma(q, t, v); }
+        else if (op == 16) softplus_pair_uniform(F, v, a, b);
+        else if (op == 17) fast_sincos_uniform(F, v, a, b);
         else fast_sincos_uniform(v, a, b);
         if (threadIdx.x == 0) { o0[i] = a; if (o1) o1[i] = b; }
     }
@@ -599,13 +657,14 @@ int cgp_squared_error_sums(cgp_ctx* ctx, const double* a, const double* r, int64
 
 int cgp_debug_math(cgp_ctx* ctx, int op, const double* x, int64_t n, double* out0, double* out1, void* stream) {
     if (!ctx) return CGP_E_ARG;
-    if (n < 0 || op < 0 || op > 11) return fail(ctx, CGP_E_ARG, "bad op or n");
+    if (n < 0 || op < 0 || op > 25) return fail(ctx, CGP_E_ARG, "bad op or n");
+    if ((op == 22 || op == 23 || op == 25) && (n & 1)) return fail(ctx, CGP_E_ARG, "a two-argument op takes an even number of inputs");
     if (n == 0) return CGP_OK;
     if (!x || !out0) return fail(ctx, CGP_E_ARG, "NULL pointer");
     DeviceScope on_device(ctx->device);
     if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
     const int64_t blocks = (n + 255) / 256;
-    if (op == 5 || op == 6 || op == 8) hipLaunchKernelGGL(debug_math_uniform_kernel, dim3((unsigned)(n < 4096 ? n : 4096)), dim3(64), 0, (hipStream_t)stream, op, x, n, out0, out1);
+    if (op == 5 || op == 6 || op == 8 || op == 16 || op == 17) hipLaunchKernelGGL(debug_math_uniform_kernel, dim3((unsigned)(n < 4096 ? n : 4096)), dim3(64), 0, (hipStream_t)stream, op, x, n, out0, out1);
     else hipLaunchKernelGGL(debug_math_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, (hipStream_t)stream, op, x, n, out0, out1);
     return hipGetLastError() == hipSuccess ? CGP_OK : fail(ctx, CGP_E_HIP, "kernel launch failed");
 }

@@ -6,7 +6,8 @@
 // so the library calls alone cost ~1000 of the ~3700 cycles of a v1 EKF step.  The versions below are branch-free
 // (one rarely taken fallback in sincos), have no denormal / errno / special-case paths beyond what the reference's
 // arithmetic can produce (+inf from exp overflow, NaN), and are accurate to a few ulp -- far inside the 1e-5 gate
-// and checked against a 200-bit reference in tests/test_gpu_fastmath.py.
+// and checked against a 200-bit reference: the tables on the CPU (tests/test_fastmath_tables.py), every form a kernel runs on the GPU, at
+// random (tests/test_gpu_fastmath.py) and at its hard points (tests/test_gpu_fastmath_edges.py; docs/KERNELS.md has the measured table).
 //
 // Constants were generated with mpmath at 200 bits (tools/gen_math_constants.py).
 #pragma once
@@ -139,7 +140,8 @@ CGP_DEV double exp_poly(double r) {
 }
 
 // exp(x) without the overflow / underflow / NaN handling, for arguments known to lie in (-700, 700):
-// x = k ln2 + r, Taylor of degree 13 on |r| <= ln2 / 2 (truncation 4e-18), v_ldexp_f64.
+// x = k ln2 + r, Taylor of degree 13 on |r| <= ln2 / 2 (truncation 5.2e-18 of the value: r^14 / 14! = 4e-18 against exp(r) >= 0.707),
+// v_ldexp_f64 (one rounding where the result is subnormal: x < -708.4).
 CGP_DEV double fast_exp_core(double x) {
     double k;
     const double r = exp_reduce(MathLit{}, x, k);
@@ -268,7 +270,8 @@ CGP_DEV double log_from_s(double s, double k) {
     return fma(k, kLn2Hi, lm);
 }
 
-// log(z) for z in [1, +inf] (the softplus argument exp(x) + 1): z = 2^k m, m in [sqrt(1/2), sqrt(2)), s = (m - 1) / (m + 1).
+// log(z) for z in [1, +inf] (the softplus argument exp(x) + 1) -- and for every positive NORMAL z below 1 (the uniforms of cgp_rng.hpp, the
+// 2 pi S of nll_increment; both tested, tests/test_gpu_fastmath_edges.py): z = 2^k m, m in [sqrt(1/2), sqrt(2)), s = (m - 1) / (m + 1).
 CGP_DEV double fast_log_ge1(double z) {
     double m = __builtin_amdgcn_frexp_mant(z);            // [0.5, 1)
     int e = __builtin_amdgcn_frexp_exp(z);
@@ -281,7 +284,8 @@ CGP_DEV double fast_log_ge1(double z) {
     return (z == __builtin_inf()) ? z : y;
 }
 
-// fast_log_ge1 for a FINITE z >= 1 with the exponent taken so that the mantissa lands in [sqrt(1/2), sqrt(2)) directly: k = exponent of
+// fast_log_ge1 for a finite z in [1, 2^1023 sqrt(2)) (beyond, z sqrt(2) overflows: NaN; its callers pass exp(x) + 1, x < 700) with the
+// exponent taken so that the mantissa lands in [sqrt(1/2), sqrt(2)) directly: k = exponent of
 // z sqrt(2), m = z 2^-k (exact) -- five instructions where frexp + the compare-and-select adjustment of fast_log_ge1 take nine.  (The
 // rounding of z sqrt(2) can leave m an ulp outside the interval at its ends: the series does not care.)
 CGP_DEV double fast_log_ge1_finite(double z) {
@@ -324,13 +328,12 @@ CGP_DEV void quadrant(int q, double s0, double c0, double& sn, double& cs) {
 constexpr double kSinTaylor[8] = {-1.0 / 355687428096000.0, 1.0 / 1307674368000.0, -1.0 / 6227020800.0, 1.0 / 39916800.0, -1.0 / 362880.0, 1.0 / 5040.0,
                                   -1.0 / 120.0, 1.0 / 6.0};                  // -1/17! ... 1/3! (sign folded below)
 constexpr double kCosTaylor[7] = {1.0 / 20922789888000.0, -1.0 / 87178291200.0, 1.0 / 479001600.0, -1.0 / 3628800.0, 1.0 / 40320.0, -1.0 / 720.0, 1.0 / 24.0};
-// ... as two independent Horner chains, the series FROM_S / FROM_C terms shorter
-template <int FROM_S = 0, int FROM_C = 0>
+// ... as two independent Horner chains
 CGP_DEV void sincos_horner(double r, double& s0, double& c0) {
     const double r2 = r * r;
-    double ps = kSinTaylor[FROM_S], pc = kCosTaylor[FROM_C];
-    CGP_UNROLL for (int i = FROM_S + 1; i < 8; i++) ps = horner_c(ps, r2, kSinTaylor[i]);
-    CGP_UNROLL for (int i = FROM_C + 1; i < 7; i++) pc = horner_c(pc, r2, kCosTaylor[i]);
+    double ps = kSinTaylor[0], pc = kCosTaylor[0];
+    CGP_UNROLL for (int i = 1; i < 8; i++) ps = horner_c(ps, r2, kSinTaylor[i]);
+    CGP_UNROLL for (int i = 1; i < 7; i++) pc = horner_c(pc, r2, kCosTaylor[i]);
     s0 = fma(-(r * r2), ps, r);                       // r - r^3 (1/3! - r^2/5! + ...)
     c0 = fma(r2 * r2, pc, fma(-0.5, r2, 1.0));        // 1 - r^2/2 + r^4 (1/4! - ...)
 }
@@ -381,12 +384,12 @@ CGP_DEV void fast_sincos(double x, double& sn, double& cs) {
 
 // fast_sincos for kernels whose angles are small throughout (one lane per trial at dt = 0.01: the rotation angle is dt 2 pi g(u) ~ 0.06 g):
 // if every active lane's |x| <= pi / 4 the Cody-Waite reduction is the identity (n = 0, r = x, no swap, no sign flip) and is skipped -- the
-// same bits, ~ 18 instructions less; one wave-uniform branch, otherwise fast_sincos as is (NaN and inf take that way).
-// ... and while every lane's |x| <= 1/4 (a frequency below 4 Hz at that step) the series end four terms earlier: sin to x^11, cos to x^12
-// (truncation 2.4e-18 / 4e-20), five instructions less.
-CGP_DEV void sincos_quarter(double r, double& s0, double& c0) { sincos_horner<3, 2>(r, s0, c0); }       // from 1/11!, 1/12!
+// same bits, ~ 18 instructions less; one wave-uniform branch, otherwise fast_sincos as is (NaN and inf take that way).  So a lane's value
+// does not depend on the lanes it shares a wavefront with.
+// (Until the edge tests there was a third tier: while every lane's |x| <= 1/4 the series ended four terms earlier -- sin to x^11, cos to x^12,
+// truncation 2.4e-18 / 4e-20, five instructions less.  That is NOT the same bits: about one lane in 64 came out an ulp away from what
+// it gets beside a lane above 1/4, i.e. a trial's rows depended on the batch it was launched in.  Taken out; docs/EXPERIMENTS.md has the timing.)
 CGP_DEV void fast_sincos_small(double x, double& sn, double& cs) {
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!(fabs(x) <= 0.25)) == 0, 1)) { sincos_quarter(x, sn, cs); return; }
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(!(fabs(x) <= kPiOver4)) == 0, 1)) { sincos_reduced(x, sn, cs); return; }
     fast_sincos(x, sn, cs);
 }

@@ -119,7 +119,9 @@ struct SmoothSel {
 //      exponential by the degree-7 near-minimax polynomial of the speculative EKF step (5.5e-11 of t, i.e. 2e-14 of the softplus) and
 //      log1p by six terms of its series (truncation t^7 / 7 < 1e-19): ~25 instructions a node;
 //   2. any |x| < 700: the branch-free full-accuracy softplus of cgp_fastmath.hpp (softplus_pair_any), ~80 a node;
-//   3. otherwise (overflow, inf, NaN) and for the other integrands: the library functions, as cgp_gaussian_expectation_fn evaluates them.
+//   3. otherwise (overflow, inf, NaN) and for the other integrands: the library functions, as cgp_gaussian_expectation_fn evaluates them --
+//      but log1p(e^x) at the nodes below 0, where the naive 1 + e^x rounds the softplus away (0 instead of e^x from x = -37 down: a fan that
+//      reaches -700 jumped from the second tier's 1e-304 to 0).
 CGP_DEV double gh_expectation(int func, double m, double s, const double* __restrict__ xi, const double* __restrict__ w, int order) {
     double fast = 0.0;
     bool have = false;
@@ -160,7 +162,7 @@ CGP_DEV double gh_expectation(int func, double m, double s, const double* __rest
     for (int p = 0; p < order; p++) {
         const double x = fma(s, xi[p], m);
         double f;
-        if (func == CGP_FN_SOFTPLUS) f = log(exp(x) + 1.0);                 // models.py:50, the naive form as is
+        if (func == CGP_FN_SOFTPLUS) { const double e = exp(x); f = x < 0.0 ? log1p(e) : log(e + 1.0); }   // models.py:50, the naive form (overflow, NaN as is)
         else if (func == CGP_FN_EXP) f = exp(x);
         else if (func == CGP_FN_SQUARE) f = x * x;
         else f = x;

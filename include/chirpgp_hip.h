@@ -403,11 +403,19 @@ int cgp_add_noise(cgp_ctx* ctx, const double* clean, int64_t clean_stride, const
 int cgp_debug_philox(cgp_ctx* ctx, const uint32_t* ctr, const uint32_t* key, int64_t n, uint32_t* out, void* stream);
 
 /* Test hook: evaluates one of the engine's in-kernel float64 elementary functions (csrc/cgp_fastmath.hpp) on n inputs.
- * op: 0 exp, 1 log on [1, inf] (softplus argument), 2 sincos (out0 = sin, out1 = cos), 3 reciprocal,
+ * op: 0 exp, 1 log of a positive normal argument, 2 sincos (out0 = sin, out1 = cos), 3 reciprocal,
  *     4 softplus pair (out0 = log(exp(x) + 1), out1 = its derivative), 5 / 6 the wave-uniform variants of 4 / 2,
  *     7 the per-lane softplus pair in its wide common-regime form (with the naive fallback), 8 the speculative step's
  *     lean softplus pair (valid for 1.5 <= x < 700 only; ~1e-11), 9 reciprocal with one Newton step, 10 the branch-free softplus pair
  *     for any |x| < 700 (NaN where it reports "not valid"), 11 the polynomial softplus pair of the MID regime (valid for |x| <= 2).
+ *     12 - 15 the softplus of the matrix-core EKF's speculative step as that step writes it (one-constant exp reduction): 12 COMMON
+ *     (1.5 <= x < 700), 13 LOW (-700 < x <= -1.5: t = exp(x), t q(t), t / (1 + t)), 14 HIGH (5 <= x < 700) and 15 MID (|x| <= 2), the last
+ *     two with fixed scales folded into their coefficients: out0 = 0.0439822971502571 x the softplus, out1 = 2.7 x its derivative;
+ *     16 / 17 the wave-uniform pair / sincos with the coefficients pinned in registers (the cooperative kernels' forms);
+ *     18 log on [1, 2^1023 sqrt 2) by direct exponent extraction, 19 / 20 the lane kernels' softplus / softplus pair, 21 sincos for
+ *     small angles (a wave-uniform ballot), 24 square root and reciprocal root (out0, out1), and the two-argument ops, which
+ *     read x as n / 2 consecutive pairs and write n / 2 results (n even): 22 / 23 x[2 i] / x[2 i + 1] from the two-step / one-step
+ *     reciprocal, 25 nll_increment(S = x[2 i], innov = x[2 i + 1]).
  *     out1 may be NULL for one-output ops. */
 int cgp_debug_math(cgp_ctx* ctx, int op, const double* x, int64_t n, double* out0, double* out1, void* stream);
 
