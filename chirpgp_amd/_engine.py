@@ -18,7 +18,7 @@ S_EKS, S_SGP, S_CD_EKS, S_CD_SGP = range(4)
 M_LINEAR, M_HARMONIC_LCD, M_LASCALA_LCD, M_LINEAR_SDE, M_HARMONIC_SDE, M_KPT = range(6)
 NLL_FINAL_ONLY, WAVE_PER_TRIAL, THREAD_PER_TRIAL, SEQUENTIAL_SCAN, GENERIC_KERNEL, SIM_FIXED_X0 = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 LITERAL_SIGMA_SUM, DPP_KERNEL, FOUR_TRIALS_PER_WAVE, ONE_TRIAL_PER_WAVE = 0x40, 0x80, 0x200, 0x400
-TIME_SPLIT, NO_TIME_SPLIT = 0x800, 0x1000
+TIME_SPLIT, NO_TIME_SPLIT, SKIP_MISSING = 0x800, 0x1000, 0x2000
 SIGMA_STANDARD = 0x1
 SIGMA_AXIAL = 0x2
 MAX_D = 12            # include/chirpgp_hip.h: CGP_MAX_D (9 .. 12: the harmonic LCD model with 4 or 5 harmonics)
@@ -415,8 +415,17 @@ def _record_addressing(R, trials_per_record, record_index):
     return rep, idx_h, (R if idx_h is None else int(idx_h.size)) * rep
 
 
+def _missing_flag(missing):
+    """``missing`` of the filters -> flag bits: None / 'propagate' (the reference: a NaN measurement poisons the state) or 'skip'."""
+    if missing is None or missing == 'propagate':
+        return 0
+    if missing == 'skip':
+        return SKIP_MISSING
+    raise ValueError(f"missing must be None, 'propagate' or 'skip', not {missing!r}")
+
+
 def run_filter(method, spec, sgps, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=False, flags=0, want=(True, True, True),
-               trials_per_record=None, record_index=None, time_split=None, split_tol=None, return_junction_error=False):
+               trials_per_record=None, record_index=None, time_split=None, split_tol=None, return_junction_error=False, missing=None):
     """cgp_filter with NumPy / torch marshalling.  ys (T,) or (B, T) -> (mfs, Pfs, nll) with matching leading axes.
 
     Shared records (include/chirpgp_hip.h, cgp_filter): with ``trials_per_record = k`` every record of ys -- (T,) or (R, T) --
@@ -428,7 +437,14 @@ def run_filter(method, spec, sgps, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=
     wavefronts per trial for batches that leave most SIMDs idle.  With ``return_junction_error=True`` the per-trial junction mismatch
     of THIS call comes back as a fourth output (device tensor [B]; None if the results are the sequential filter's); it is also
     left, per calling thread, in ``_engine.last_junction_error``.  With ``split_tol`` the call checks it (one device
-    synchronisation) and falls back to the sequential filter if any junction is further off."""
+    synchronisation) and falls back to the sequential filter if any junction is further off.
+
+    ``missing='skip'`` (include/chirpgp_hip.h, CGP_SKIP_MISSING): a NaN measurement is a missing sample -- the prediction is that step's
+    filtering result and its NLL increment is exactly 0 -- instead of the reference's poison (None / 'propagate').  Not with
+    ``time_split``."""
+    gaps = _missing_flag(missing)
+    if gaps and time_split is not None:
+        raise ValueError("missing='skip' does not go with time_split: a burn-in that starts inside a gap has no junction to compare")
     junction = None
     torch = _torch()
     like_numpy = not _is_torch(ys)
@@ -455,7 +471,7 @@ def run_filter(method, spec, sgps, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=
         mfs = torch.empty((B, T, d), **opts) if want[0] else None
         Pfs = torch.empty((B, T, d, d), **opts) if want[1] else None
         nll = (torch.empty((B,) if nll_final_only else (B, T), **opts)) if want[2] else None
-        fl = int(flags) | (NLL_FINAL_ONLY if nll_final_only else 0)
+        fl = int(flags) | (NLL_FINAL_ONLY if nll_final_only else 0) | gaps
         lib, st = load_library(), _stream()
         if time_split is not None:
             segments, burn_in = (int(v) for v in time_split)
@@ -512,9 +528,10 @@ def release_custom_models():
     return n
 
 
-def run_filter_custom(spec, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=False, want=(True, True, True), flags=0, sgps=None):
+def run_filter_custom(spec, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=False, want=(True, True, True), flags=0, sgps=None, missing=None):
     """ekf / cd_ekf -- with `sgps`: sgp_filter / cd_sgp_filter -- on a model compiled at run time (cgp_filter_custom): the generic
-    one-lane-per-trial kernel instantiated on the caller's source.  ys (T,) or (B, T)."""
+    one-lane-per-trial kernel instantiated on the caller's source.  ys (T,) or (B, T).  ``missing`` as in run_filter."""
+    gaps = _missing_flag(missing)
     torch = _torch()
     like_numpy = not _is_torch(ys)
     ys_d = dev(ys)
@@ -534,7 +551,7 @@ def run_filter_custom(spec, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=False, 
         mfs = torch.empty((B, T, d), **opts) if want[0] else None
         Pfs = torch.empty((B, T, d, d), **opts) if want[1] else None
         nll = (torch.empty((B,) if nll_final_only else (B, T), **opts)) if want[2] else None
-        fl = int(flags) | (NLL_FINAL_ONLY if nll_final_only else 0)
+        fl = int(flags) | (NLL_FINAL_ONLY if nll_final_only else 0) | gaps
         rc = _timed('filter', lambda: load_library().cgp_filter_custom(ctx, handle, C.byref(sig) if sig is not None else None, _ptr(params), pstride, _ptr(g), gstride, C.byref(init), float(dt),
                                                                        _ptr(ys_d), T, 1, None, B, T, _ptr(mfs), _ptr(Pfs), _ptr(nll), fl, _stream()))
         _check(ctx, rc, 'cgp_filter_custom')

@@ -422,18 +422,18 @@ static int filter_impl(cgp_ctx* ctx, int method, const cgp_model* model, const c
         break;
     case FilterRoute::kKf4Mfma:     rc = dispatch_filter_kf4_mfma(io, ma, st); break;
     case FilterRoute::kEkf4Mfma:
-    case FilterRoute::kEkf4MfmaSeg: rc = dispatch_filter_mfma4(io, ma, st); break;
+    case FilterRoute::kEkf4MfmaSeg: rc = route.gaps ? dispatch_filter_mfma4_gaps(io, ma, st) : dispatch_filter_mfma4(io, ma, st); break;
     case FilterRoute::kEkf4MfmaX4:  rc = launch_ekf4_mfma_x4(io, ma, st); break;
     case FilterRoute::kEkf4Coop:    rc = dispatch_filter_coop4(io, ma, st); break;
-    case FilterRoute::kSgp4Mfma:    rc = dispatch_filter_mfma4_sgp(io, ma, st); break;
+    case FilterRoute::kSgp4Mfma:    rc = route.gaps ? dispatch_filter_mfma4_sgp_gaps(io, ma, st) : dispatch_filter_mfma4_sgp(io, ma, st); break;
     case FilterRoute::kSgp4Coop:    rc = dispatch_filter_coop4_sgp(io, ma, st); break;
     case FilterRoute::kLane4Ekf:
     case FilterRoute::kLane4Sgp:    rc = dispatch_filter_lane4(method, io, ma, st); break;
     case FilterRoute::kEkf8Coop:    rc = dispatch_filter_coop8_ekf(model->n_harm, io, ma, st); break;
     case FilterRoute::kSgp8Coop:    rc = dispatch_filter_coop8_sgp(model->n_harm, io, ma, st); break;
-    case FilterRoute::kCdEkf4Mfma:  rc = dispatch_filter_mfma4_cdekf(io, ma, st); break;
+    case FilterRoute::kCdEkf4Mfma:  rc = route.gaps ? dispatch_filter_mfma4_cdekf_gaps(io, ma, st) : dispatch_filter_mfma4_cdekf(io, ma, st); break;
     case FilterRoute::kCdEkf4Coop:  rc = dispatch_filter_coop4_cdekf(io, ma, st); break;
-    case FilterRoute::kCdSgp4Mfma:  rc = dispatch_filter_mfma4_cdsgp(io, ma, st); break;
+    case FilterRoute::kCdSgp4Mfma:  rc = route.gaps ? dispatch_filter_mfma4_cdsgp_gaps(io, ma, st) : dispatch_filter_mfma4_cdsgp(io, ma, st); break;
     case FilterRoute::kCdSgp4Coop:  rc = dispatch_filter_coop4_cdsgp(io, ma, st); break;
     case FilterRoute::kKpt8Coop:    rc = dispatch_filter_kpt8(model->n_harm, io, ma, st); break;
     case FilterRoute::kGenericKpt:  rc = dispatch_filter_kpt(model->n_harm, wave, io, ma, st); break;
@@ -460,6 +460,9 @@ int cgp_filter_time_split(cgp_ctx* ctx, int method, const cgp_model* model, cons
                           int64_t B, int64_t T, double* mfs, double* Pfs, double* nll, uint32_t flags,
                           int64_t segments, int64_t burn_in, double* junction_err, void* stream) {
     if (ctx && segments < 1) return fail(ctx, CGP_E_ARG, "segments must be >= 1");
+    if (ctx && (flags & CGP_SKIP_MISSING))
+        return fail(ctx, CGP_E_UNSUPPORTED, "CGP_SKIP_MISSING goes with cgp_filter and cgp_filter_custom only: a time-split filter's burn-in that starts "
+                                            "inside a gap has no junction to compare");
     if (ctx && segments == 1 && junction_err && B > 0) {                 // nothing is split: no junction, no mismatch
         DeviceScope on_device(ctx->device);
         if (!on_device.ok || hipMemsetAsync(junction_err, 0, sizeof(double) * (size_t)B, (hipStream_t)stream) != hipSuccess) return fail(ctx, CGP_E_HIP, "hipMemsetAsync failed");

@@ -233,10 +233,21 @@ struct Tile4FilterOut {
     }
     CGP_DEV OobWindow P_window(bool burn) const { return burn ? wnull : wP; }
     CGP_DEV OobWindow m_window(bool burn) const { return burn ? wnull : wm; }
-    // the NLL of a chunk whose steps parked (S, innovation) in park[slot]; returns the new running total
-    CGP_DEV double flush_nll(const double2* park, int lane, int nsteps, double cum, int64_t t0) const {
+    // the NLL of a chunk whose steps parked (S, innovation) in park[slot]; returns the new running total.  GAPS (CGP_SKIP_MISSING):
+    // y_lane is the measurement of step `lane`; a missing step adds +0.0 and shows the previous step's total (nll_hold_gaps)
+    template <bool GAPS = false>
+    CGP_DEV double flush_nll(const double2* park, int lane, int nsteps, double cum, int64_t t0, double y_lane = 0.0) const {
         wave_lds_fence();
         const double2 si = park[lane < nsteps ? lane : 0];
+        if constexpr (GAPS) {
+            const bool present = lane < nsteps && !is_missing(y_lane);
+            double v = present ? nll_increment(si.x, si.y) : 0.0;
+            v = wave_inclusive_scan(v);
+            v += cum;
+            v = nll_hold_gaps(v, present, lane, cum);
+            if (nll && lane < nsteps) nll[t0 + lane] = v;
+            return readlane_f64(v, nsteps - 1);
+        }
         return nll_flush_wave(si.x, si.y, lane, nsteps, cum, nll ? nll + t0 : nullptr);
     }
     CGP_DEV void store_nll_total(const FilterIO& io, int64_t trial, int lane, double cum) const {

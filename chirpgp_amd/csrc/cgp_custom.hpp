@@ -152,13 +152,13 @@ template <int D_, class U> struct CustomMeasurement {
     static constexpr int D = D_;
     static constexpr bool LINEAR = false;
     CGP_DEV static void update(const Vec<D>& mp, const Sym<D>& Pp, const Vec<D>& q, double Xi, double y, Vec<D>& mf, Sym<D>& Pf,
-                               double& S, double& innov) {
+                               double& S, double& innov, bool skip_missing = false) {
         ad::Dual<D> x[D];
         CGP_UNROLL for (int i = 0; i < D; i++) { x[i] = ad::Dual<D>(mp.v[i]); x[i].d[i] = 1.0; }
         const ad::Dual<D> h = U::template measure<ad::Dual<D>>(x, q.v);
         Vec<D> H;
         CGP_UNROLL for (int i = 0; i < D; i++) H.v[i] = h.d[i];
-        scalar_update<D>(mp, Pp, H, Xi, y, true, h.v, mf, Pf, S, innov);
+        scalar_update<D>(mp, Pp, H, Xi, y, true, h.v, mf, Pf, S, innov, skip_missing);
     }
 };
 

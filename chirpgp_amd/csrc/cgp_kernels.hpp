@@ -244,8 +244,8 @@ inline ModelArgs model_args(const cgp_model* m, const cgp_sigma* sg, double dt, 
 template <int D> struct LinearMeasurement {
     static constexpr bool LINEAR = true;
     CGP_DEV static void update(const Vec<D>& mp, const Sym<D>& Pp, const Vec<D>& H, double Xi, double y, Vec<D>& mf, Sym<D>& Pf,
-                               double& S, double& innov) {
-        scalar_update<D>(mp, Pp, H, Xi, y, false, 0.0, mf, Pf, S, innov);
+                               double& S, double& innov, bool skip_missing = false) {
+        scalar_update<D>(mp, Pp, H, Xi, y, false, 0.0, mf, Pf, S, innov, skip_missing);
     }
 };
 // ekf_for_kpt (filters_smoothers.py:298-311): H = grad h(mp), pred = h(mp).
@@ -253,10 +253,10 @@ template <int NH, bool UNIFORM = false> struct KptUpdate {
     static constexpr int D = NH + 2;
     static constexpr bool LINEAR = false;
     CGP_DEV static void update(const Vec<D>& mp, const Sym<D>& Pp, const Vec<D>&, double Xi, double y, Vec<D>& mf, Sym<D>& Pf,
-                               double& S, double& innov) {
+                               double& S, double& innov, bool skip_missing = false) {
         Vec<D> H;
         const double pred = KptMeasurement<NH, UNIFORM>::eval(mp, H);
-        scalar_update<D>(mp, Pp, H, Xi, y, true, pred, mf, Pf, S, innov);
+        scalar_update<D>(mp, Pp, H, Xi, y, true, pred, mf, Pf, S, innov, skip_missing);
     }
 };
 
@@ -400,6 +400,8 @@ filter_kernel(FilterIO io, ModelArgs ma) {
     const bool nll_final = (io.flags & CGP_NLL_FINAL_ONLY) != 0;
     double* __restrict__ nll = (io.nll && !nll_final) ? io.nll + trial * T : nullptr;
     const bool writer = !WAVE || lane == 0;
+    // CGP_SKIP_MISSING: a NaN measurement leaves the prediction as the step's result (scalar_update) and adds +0.0 to the NLL
+    const bool gaps = (io.flags & CGP_SKIP_MISSING) != 0;
 
     // The negative log-likelihood needs sqrt, log and a divide per step but nothing downstream depends on it, so the
     // wave-per-trial shape keeps it off the serial chain: lane (t mod 64) latches (S, innovation) of step t, and every
@@ -421,7 +423,7 @@ filter_kernel(FilterIO io, ModelArgs ma) {
                 Vec<D> mp; Sym<D> Pp;
                 double S, innov;
                 pred.predict(lane, lds, mf, Pf, mp, Pp);
-                Meas::update(mp, Pp, H, Xi, y, mf, Pf, S, innov);
+                Meas::update(mp, Pp, H, Xi, y, mf, Pf, S, innov, gaps);
                 if (lane == slot) { S_l = S; innov_l = innov; }
                 if constexpr (D >= 6) {
                     if (mfs || Pfs) wave_store_step<D>(rowpark, lane, mf, Pf, mfs ? mfs + t * D : nullptr, Pfs ? Pfs + t * D * D : nullptr);
@@ -431,8 +433,12 @@ filter_kernel(FilterIO io, ModelArgs ma) {
                 }
             }
             if (want_nll) {
+                // (lane l still holds the measurement of step l)
+                const bool present = lane < nsteps && !(gaps && is_missing(ychunk));
                 double v = (lane < nsteps) ? nll_increment(S_l, innov_l) : 0.0;
+                if (gaps) v = present ? v : 0.0;
                 v = wave_inclusive_scan(v) + cum;
+                if (gaps) v = nll_hold_gaps(v, present, lane, cum);
                 if (nll && lane < nsteps) nll[t0 + lane] = v;
                 cum = readlane_f64(v, nsteps - 1);
             }
@@ -467,9 +473,9 @@ filter_kernel(FilterIO io, ModelArgs ma) {
                 Vec<D> mp; Sym<D> Pp;
                 double S, innov;
                 pred.predict(lane, lds, mf, Pf, mp, Pp);
-                Meas::update(mp, Pp, H, Xi, y, mf, Pf, S, innov);
+                Meas::update(mp, Pp, H, Xi, y, mf, Pf, S, innov, gaps);
                 if (want_nll) {
-                    cum += nll_increment(S, innov);
+                    if (!(gaps && is_missing(y))) cum += nll_increment(S, innov);
                     ytile[lane * kYPitch + k] = cum;
                 }
                 if (io.mfs) {
@@ -502,9 +508,9 @@ filter_kernel(FilterIO io, ModelArgs ma) {
             Vec<D> mp; Sym<D> Pp;
             double S, innov;
             pred.predict(lane, lds, mf, Pf, mp, Pp);
-            Meas::update(mp, Pp, H, Xi, y, mf, Pf, S, innov);
+            Meas::update(mp, Pp, H, Xi, y, mf, Pf, S, innov, gaps);
             if (want_nll) {
-                cum += nll_increment(S, innov);
+                if (!(gaps && is_missing(y))) cum += nll_increment(S, innov);
                 if (nll) nll[t] = cum;
             }
             if constexpr (TILED) {
@@ -727,6 +733,11 @@ int dispatch_filter_mfma4_cdekf(const FilterIO&, const ModelArgs&, hipStream_t);
 int dispatch_filter_coop4_cdekf(const FilterIO&, const ModelArgs&, hipStream_t);
 int dispatch_filter_mfma4_cdsgp(const FilterIO&, const ModelArgs&, hipStream_t);
 int dispatch_filter_coop4_cdsgp(const FilterIO&, const ModelArgs&, hipStream_t);
+// the one-wavefront-per-trial matrix-core filters for records with gaps (CGP_SKIP_MISSING; cgp_inst_gaps4.hip, cgp_inst_gaps4_sigma.hip)
+int dispatch_filter_mfma4_gaps(const FilterIO&, const ModelArgs&, hipStream_t);          // ekf (cgp_inst_gaps4.hip)
+int dispatch_filter_mfma4_sgp_gaps(const FilterIO&, const ModelArgs&, hipStream_t);
+int dispatch_filter_mfma4_cdekf_gaps(const FilterIO&, const ModelArgs&, hipStream_t);
+int dispatch_filter_mfma4_cdsgp_gaps(const FilterIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_disc_linear(int method, int key, bool wave, const SmootherIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_disc_harm(int method, int key, bool wave, const SmootherIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_sde_linear(int method, int key, bool wave, const SmootherIO&, const ModelArgs&, hipStream_t);

@@ -128,9 +128,14 @@ template <int D> CGP_DEV void cho_solve_mat(const Sym<D>& L, const Vec<D>& inv_d
 // Pf = Pp - (K K^T) S (the reference's form, not Joseph).  Here K = (Pp H) * (1 / S) with a Newton-refined reciprocal
 // and (K K^T) S is formed as K (Pp H)^T -- the same matrix, one rounding fewer.  Returns S and the innovation; the
 // negative log-likelihood increment is nll_increment(S, innov) (cgp_fastmath.hpp).
+// skip_missing (CGP_SKIP_MISSING): a NaN measurement -- decided from y alone, never from the innovation or S -- zeroes the gain's
+// reciprocal and the innovation, so that Pf = fma(-(PH 0), PH, Pp) = Pp and mf = fma(PH 0, 0, mp) = mp exactly for finite operands,
+// while a present measurement runs the very operations of the unflagged step.  The caller adds no NLL for such a step (is_missing).
+CGP_DEV bool is_missing(double y) { return y != y; }
 template <int D>
 CGP_DEV void scalar_update(const Vec<D>& mp, const Sym<D>& Pp, const Vec<D>& H, double Xi, double y,
-                           bool override_pred, double pred_in, Vec<D>& mf, Sym<D>& Pf, double& S_out, double& innov_out) {
+                           bool override_pred, double pred_in, Vec<D>& mf, Sym<D>& Pf, double& S_out, double& innov_out,
+                           bool skip_missing = false) {
     Vec<D> PH;
     CGP_UNROLL for (int i = 0; i < D; i++) {
         double s = Pp(i, 0) * H.v[0];
@@ -147,9 +152,12 @@ CGP_DEV void scalar_update(const Vec<D>& mp, const Sym<D>& Pp, const Vec<D>& H, 
     rS = fma(rS, e, rS);
     e = fma(-S, rS, 1.0);
     rS = fma(rS, e, rS);
+    const bool gap = skip_missing && is_missing(y);
+    rS = gap ? 0.0 : rS;
+    const double dy = gap ? 0.0 : innov;
     Vec<D> K;
     CGP_UNROLL for (int i = 0; i < D; i++) K.v[i] = PH.v[i] * rS;
-    CGP_UNROLL for (int i = 0; i < D; i++) mf.v[i] = fma(K.v[i], innov, mp.v[i]);
+    CGP_UNROLL for (int i = 0; i < D; i++) mf.v[i] = fma(K.v[i], dy, mp.v[i]);
     CGP_UNROLL for (int i = 0; i < D; i++)
         CGP_UNROLL for (int j = 0; j <= i; j++) Pf(i, j) = fma(-K.v[i], PH.v[j], Pp(i, j));
     S_out = S;
@@ -233,6 +241,18 @@ CGP_DEV double readlane_f64(double x, int src) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(x), src);
     const int hi = __builtin_amdgcn_readlane(__double2hiint(x), src);
     return __hiloint2double(hi, lo);
+}
+// Cumulative NLL of a chunk with missing steps (CGP_SKIP_MISSING).  `v` is the lane's inclusive total, a missing step's increment
+// entered as +0.0; lane l holds step l, `present` says whether its measurement was one.  The scan sums every lane's prefix in an
+// order of its own, so two neighbouring totals that differ by a zero increment need not agree in the last bit: each missing lane
+// takes the total of the last present step before it (`before`, the total in front of the chunk, where there is none).  The
+// cumulative value at a gap is then the previous step's, bit for bit; present lanes keep their own.
+CGP_DEV double nll_hold_gaps(double v, bool present, int lane, double before) {
+    const unsigned long long upto = __builtin_amdgcn_ballot_w64(present) & (~0ull >> (63 - lane));      // present steps 0 .. lane
+    const int src = upto ? 63 - __builtin_clzll(upto) : lane;
+    const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(v));
+    const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(v));
+    return upto ? __hiloint2double(hi, lo) : before;
 }
 
 }  // namespace cgp

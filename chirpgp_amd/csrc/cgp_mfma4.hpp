@@ -140,7 +140,10 @@ struct Ekf4State {
 // lanes.  The chain still counts in the step's tail: H Pp as mfma(A = H, B = Pp) + S as its quad broadcast (no P a, no
 // v_readlane) is three instructions shorter but one matrix instruction deeper, and measured 2.64 against 2.60 ms -- the
 // linear filter, whose step is the tail alone, takes that form and gains 4 % (kf4_mfma_trial).
-template <int E1 = 0>
+// GAPS (CGP_SKIP_MISSING; the kernel for records with gaps below, ekf4_gaps_trial): a NaN measurement zeroes the gain's reciprocal and the
+// innovation, so that Pf = fma(-(PHr 0), PHq, Pp) = Pp and mf = fma(PH, 0 0, mp) = mp exactly -- y is the same in every lane: one condition,
+// two selects; a present measurement runs the operations of the unflagged step.  Defaulted: every other call site compiles to what it did.
+template <int E1 = 0, bool GAPS = false>
 // kjd = (kj ang) x the softplus derivative: this lane's factor of the Jacobian column d f / d u2
 CGP_DEV void ekf4_mfma_finish_j(const Ekf4MfmaConst& K, double y, double A, double B2, double kjd, Ekf4State& x, double& S, double& innov) {
     // E1 != 0: (A, B2) is the lane's column pair -- f by column on the vector ALU, the matrix operand J0[q][r] picked from the pair;
@@ -184,21 +187,26 @@ CGP_DEV void ekf4_mfma_finish_j(const Ekf4MfmaConst& K, double y, double A, doub
         S = mfma4(K.Hr, PHr, K.Xi);
         innov = y - mfma4(K.Hr, f_r, 0.0);
     }
-    const double rS = rcp_nr1(S);                               // 2e-15 (one Newton step): two FMAs less on the chain
+    double rS = rcp_nr1(S), dy = innov;                         // 2e-15 (one Newton step): two FMAs less on the chain
+    if constexpr (GAPS) {
+        const bool gap = is_missing(y);
+        rS = gap ? 0.0 : rS;
+        dy = gap ? 0.0 : innov;
+    }
     // (v_fmac_f64 is VOP2 and takes its first source through the 64-bit DPP: "+= rowbcast1(Pp) * x" as one instruction would
     // spare the move that forms Pp H by row.  The compiler does not form it; as inline assembly it measured 2.48 against 2.40 ms.)
     x.P = fma(-(PHr * rS), PHq, Pp);                            // Pf = Pp - K (Pp H)^T
-    const double g = rS * innov;
+    const double g = rS * dy;
     if constexpr (E1 == 0) x.ur = fma(PHr, g, f_r);             // mf = mp + K innov, in both layouts (H = e_1: by column only)
     x.uq = fma(PHq, g, f_q);
 }
-template <int E1 = 0>
+template <int E1 = 0, bool GAPS = false>
 CGP_DEV void ekf4_mfma_finish(const Ekf4MfmaConst& K, double y, double c1, double s1, double dsp, Ekf4State& x, double& S, double& innov) {
     if constexpr (E1 != 0) {
-        ekf4_mfma_finish_j<E1>(K, y, fma(K.pa, c1, K.pA0), fma(K.pb, s1, K.pB0), K.kja * dsp, x, S, innov);
+        ekf4_mfma_finish_j<E1, GAPS>(K, y, fma(K.pa, c1, K.pA0), fma(K.pb, s1, K.pB0), K.kja * dsp, x, S, innov);
     } else {
         const double J0T = fma(K.kcr, c1, fma(K.ksr, s1, K.kk));       // rho (kc cos + ks sin) + kk: rho rides in kcr, ksr
-        ekf4_mfma_finish_j<E1>(K, y, J0T, 0.0, K.kja * dsp, x, S, innov);
+        ekf4_mfma_finish_j<E1, GAPS>(K, y, J0T, 0.0, K.kja * dsp, x, S, innov);
     }
 }
 
@@ -206,25 +214,25 @@ CGP_DEV void ekf4_mfma_finish(const Ekf4MfmaConst& K, double y, double c1, doubl
 // (cgp_fastmath.hpp: softplus_pair_any, fast_sincos_spec) -- what a chunk outside the lean regime runs on; `bad` collects the steps outside
 // even that (the chunk is then repeated with the checked step).  Records whose frequency state wanders below 1.5 -- low signal-to-noise,
 // low or high chirp rates: two thirds of bench.py's C2_spread combinations -- ran 3 x slower on the checked step before.
-template <int E1 = 0>
+template <int E1 = 0, bool GAPS = false>
 CGP_DEV void ekf4_mfma_step_wide(const Ekf4MfmaConst& K, const WideRegs& W, double y, Ekf4State& x, double& S, double& innov, bool& bad) {
     double sp, dsp, s1, c1;
     bool ok1, ok2;
     softplus_pair_any(W, x.u2(), sp, dsp, ok1);
     fast_sincos_spec(W, K.ang * sp, s1, c1, ok2);
     bad = bad || !(ok1 && ok2);
-    ekf4_mfma_finish<E1>(K, y, c1, s1, dsp, x, S, innov);
+    ekf4_mfma_finish<E1, GAPS>(K, y, c1, s1, dsp, x, S, innov);
 }
 
 // The checked step: full softplus and sincos, regime branches and all (the reference's naive arithmetic anywhere).
-template <int E1 = 0>
+template <int E1 = 0, bool GAPS = false>
 CGP_DEV void ekf4_mfma_step_checked(const Ekf4MfmaConst& K, double y, Ekf4State& x, double& S, double& innov) {
     double sp, dsp, s1, c1;
     softplus_pair_uniform(x.u2(), sp, dsp);
     // theta = dt 2 pi g(u2) fs as ONE multiply by the constant dt 2 pi fs (the reference rounds three times,
     // models.py:296-297: a relative 1e-16 on an angle of ~0.05 rad)
     fast_sincos_uniform(K.ang * sp, s1, c1);
-    ekf4_mfma_finish<E1>(K, y, c1, s1, dsp, x, S, innov);
+    ekf4_mfma_finish<E1, GAPS>(K, y, c1, s1, dsp, x, S, innov);
 }
 
 // The speculative step.  Softplus: t = exp(-u2), then theta = ang (u2 + t q(t)) with the lean degree-7 polynomials of
@@ -750,6 +758,96 @@ __global__ void __launch_bounds__(64) ekf4_mfma_kernel(FilterIO io, ModelArgs ma
 
 
 #endif  // CGP_EKF4_KERNELS
+
+#ifdef CGP_EKF4_GAPS_KERNELS     // instantiated by cgp_inst_gaps4.hip alone
+// ---------------------------------------------------------------------------------------------- ekf on records with gaps
+// CGP_SKIP_MISSING on the chirp / La Scala LCD models, one wavefront per trial: a plain chunk loop on the branch-free full-accuracy WIDE
+// step (any |u2| < 700, a fresh sincos per step) with the gate of ekf4_mfma_finish_j; a chunk with a step outside even that is repeated from
+// its saved state on the checked step.  No speculative regimes, no anchors, no back-off counters: what they buy (the wide step's chunks ran
+// at about 1.8 x the common regime's) is bought with state that a gap would have to be taught to leave alone -- the rotation
+// pair carried from step to step, the regime chosen at a chunk's start -- and the headline kernel's chunk loop stays as it is.  A step
+// costs the wide step's issue cycles plus one compare and four v_cndmask.  Whole records only (route_filter refuses a flagged time-split call).
+template <bool E1>
+CGP_DEV void ekf4_gaps_trial(const FilterIO& io, const ModelArgs& ma) {
+    const int lane = threadIdx.x;
+    const int r = lane >> 4, q = lane & 3;
+    const int64_t trial = blockIdx.x;
+
+    HarmonicLCD<1> model;
+    model.setup(ma.params + trial * ma.param_stride, ma.dt, ma.model_id);
+    Ekf4MfmaConst K;
+    K.template load<E1>(model, io, trial, r, q);
+    Ekf4State x;
+    x.template load<E1>(io, trial, r, q);
+    const int64_t T = io.T;
+    const double* __restrict__ ys = io.record(trial);
+    Tile4FilterOut out;
+    out.init(io, trial, lane);
+    const unsigned p_off = out.offP, m_off = out.offm;
+    WideRegs W;                                                             // the wide step's constants, pinned for the kernel
+    W.init();
+
+    __shared__ double2 park[64];                                            // (S, innovation) of the chunk's steps, for the NLL flush
+    __shared__ double ybuf[64];                                             // the chunk's measurements: broadcast ds_read_b128, four steps a time
+    double cum = 0.0;
+    unsigned n_wide = 0, n_checked = 0;                                     // chunks by step (cgp_debug_counters)
+    double ynext = (lane < T) ? ys[lane] : 0.0;                             // one chunk ahead (see ekf4_mfma_trial)
+    for (int64_t t0 = 0; t0 < T; t0 += 64) {
+        wave_lds_fence();                                                   // the previous chunk's NLL flush has read its slots
+        double ychunk = ynext;
+        asm volatile("" : "+v"(ychunk));
+        ynext = (t0 + 64 + lane < T) ? ys[t0 + 64 + lane] : 0.0;
+        const int nsteps = (T - t0 < 64) ? (int)(T - t0) : 64;
+        const Ekf4State x0 = x;
+        ybuf[lane] = ychunk;
+        wave_lds_fence();
+        bool bad = false;
+        auto wide_one = [&](int slot, double y) {
+            double S, innov;
+            ekf4_mfma_step_wide<E1 ? 2 : 0, true>(K, W, y, x, S, innov, bad);
+            park[slot] = make_double2(S, innov);
+            const unsigned t = (unsigned)(t0 + slot);
+            out.wP.store_s(x.P, p_off, t * 128u);
+            out.wm.store_s(x.uq, m_off, t * 32u);
+        };
+        int slot = 0;
+        for (; slot + 4 <= nsteps; slot += 4) {
+            const double2 ya = *reinterpret_cast<const double2*>(ybuf + slot), yb = *reinterpret_cast<const double2*>(ybuf + slot + 2);
+            wide_one(slot, ya.x); wide_one(slot + 1, ya.y); wide_one(slot + 2, yb.x); wide_one(slot + 3, yb.y);
+        }
+        for (; slot < nsteps; slot++) wide_one(slot, readlane_f64(ychunk, slot));
+        if (__builtin_amdgcn_ballot_w64(bad) != 0) {                        // a step at |u2| >= 700, an angle beyond 1e5, inf, NaN: the checked step
+            x = x0;
+            for (int s = 0; s < nsteps; s++) {
+                double S, innov;
+                ekf4_mfma_step_checked<E1 ? 2 : 0, true>(K, readlane_f64(ychunk, s), x, S, innov);
+                park[s] = make_double2(S, innov);
+                const unsigned t = (unsigned)(t0 + s);
+                out.wP.store_s(x.P, p_off, t * 128u);
+                out.wm.store_s(x.uq, m_off, t * 32u);
+            }
+            n_checked++;
+        } else n_wide++;
+        if (out.want_nll) cum = out.template flush_nll<true>(park, lane, nsteps, cum, t0, ychunk);
+    }
+    out.store_nll_total(io, trial, lane, cum);
+    if (io.counters && lane == 0) {                                         // (the slots of ekf4_mfma_trial: 3 = checked, 5 = wide)
+        atomicAdd(io.counters + 3, (unsigned long long)n_checked);
+        atomicAdd(io.counters + 5, (unsigned long long)n_wide);
+    }
+}
+__global__ void __launch_bounds__(64) ekf4_gaps_kernel(FilterIO io, ModelArgs ma) {
+    if ((int64_t)blockIdx.x >= io.B) return;
+    if (h_is_e1(io.H + (int64_t)blockIdx.x * io.H_stride)) ekf4_gaps_trial<true>(io, ma);
+    else ekf4_gaps_trial<false>(io, ma);
+}
+inline int launch_ekf4_gaps(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
+    if (io.B <= 0 || io.T <= 0) return CGP_OK;
+    if (!ekf4_mfma_fits(io) || io.segs > 1) return CGP_E_UNSUPPORTED;
+    hipLaunchKernelGGL(ekf4_gaps_kernel, dim3((unsigned)io.B), dim3(64), 0, stream, io, ma);
+    return hip_rc(hipGetLastError());
+}
+#endif  // CGP_EKF4_GAPS_KERNELS
 
 // (round 5) the four-trials-per-wavefront kernel lives in a translation unit of its own (cgp_inst_ekf4_x4.hip): the one-trial kernel's
 // unit is compiled without machine-level loop-invariant code motion (Makefile), which costs this one 14 %

@@ -107,6 +107,9 @@ CGP_DEV void cd4_mfma_rhs(const SM& model, const SoftplusRegs& R, const Cd4LaneC
 
 // Scalar-measurement update (filters_smoothers.py:55-68) in the matrix-core layout: three matrix instructions (see
 // cgp_mfma4_sigma.hpp); the mean in column form (Hq = H[q]: H f is a sum over the quad).
+// GAPS (CGP_SKIP_MISSING): a NaN measurement zeroes the gain's reciprocal and the innovation -- Pf = Pp and mf = mp exactly, as in
+// scalar_update (cgp_math.hpp); y is wave-uniform, so the gate is one condition and two selects.
+template <bool GAPS = false>
 CGP_DEV void mfma4_update_col(double Pp, double fcol, double Hk, double Hq, double Xi, double y,
                               double& P, double& ucol, double& S, double& innov) {
     const double PHc = mfma4x4(Hk, Pp, 0.0);                             // (Pp H^T)[q] in every row
@@ -116,14 +119,20 @@ CGP_DEV void mfma4_update_col(double Pp, double fcol, double Hk, double Hq, doub
     pred += dpp_f64<kQuadSwap1>(pred);
     pred += dpp_f64<kQuadSwap2>(pred);
     innov = y - pred;
-    const double rS = rcp_nr1(S);
+    double rS = rcp_nr1(S), dy = innov;
+    if constexpr (GAPS) {
+        const bool gap = is_missing(y);
+        rS = gap ? 0.0 : rS;
+        dy = gap ? 0.0 : innov;
+    }
     P = fma(-(PHr * rS), PHc, Pp);                                       // Pf = Pp - K (Pp H)^T
-    ucol = fma(PHc, rS * innov, fcol);                                   // mf = mp + K innov
+    ucol = fma(PHc, rS * dy, fcol);                                      // mf = mp + K innov
 }
 
 // ------------------------------------------------------------------------------------------------ cd_sgp_filter, d = 4
-template <class SM, bool TWO, bool SPLIT>
+template <class SM, bool TWO, bool SPLIT, bool GAPS = false>
 __global__ void __launch_bounds__(64) cdsgp4_mfma_kernel(FilterIO io, ModelArgs ma) {
+    static_assert(!(SPLIT && GAPS), "the time-split launches know no gaps");
     static_assert(SM::D == 4, "d = 4 kernel");
     __shared__ double2 park[64];                                         // (S, innovation) of the chunk's steps, for the NLL
     const int lane = threadIdx.x;
@@ -176,13 +185,13 @@ __global__ void __launch_bounds__(64) cdsgp4_mfma_kernel(FilterIO io, ModelArgs 
             rk4_lane(dt, f, Pp, [&](double tm, double tP, double& km, double& kP) { cd4_mfma_rhs<TWO>(model, R, K, grp, tm, tP, km, kP); });
             // ---- update
             double S, innov;
-            mfma4_update_col(Pp, f, Hk, Hq, Xi, y, P, u, S, innov);
+            mfma4_update_col<GAPS>(Pp, f, Hk, Hq, Xi, y, P, u, S, innov);
             park[slot] = make_double2(S, innov);                        // every lane holds them: same address, same value
             wPc.store(P, t * 128u + offP);
             wmc.store(u, t * 32u + offm);
         }
         if (out.want_nll && !burn) {
-            cum = out.flush_nll(park, lane, nsteps, cum, t0);
+            cum = out.template flush_nll<GAPS>(park, lane, nsteps, cum, t0, ychunk);
             wave_lds_fence();
         }
     }
@@ -295,7 +304,8 @@ CGP_DEV void cd4_ekf_eval(const SoftplusRegs& R, const Cd4LaneCoef& K, const Cd4
     JT = fma(Jc.cb, w, fma(Jc.cg0, jv0, fma(Jc.cg1, jv1, Jc.ck)));
 }
 
-#ifndef CGP_NO_CD_EKF_KERNELS       // the two non-template kernels below live in ONE translation unit (cgp_inst_mfma4.hip)
+#ifndef CGP_NO_CD_EKF_KERNELS       // the kernels below are instantiated in cgp_inst_mfma4.hip (GAPS: cgp_inst_gaps4_sigma.hip)
+template <bool GAPS = false>
 __global__ void __launch_bounds__(64) cdekf4_mfma_kernel(FilterIO io, ModelArgs ma) {
     __shared__ double2 park[64];                                         // (S, innovation) of the chunk's steps, for the NLL
     const int lane = threadIdx.x;
@@ -340,13 +350,13 @@ __global__ void __launch_bounds__(64) cdekf4_mfma_kernel(FilterIO io, ModelArgs 
                 kP = mfma4x4(JP, K.ident, JP + K.gam);                   // (J P)^T + J P + gamma
             });
             double S, innov;
-            mfma4_update_col(Pp, f, Hk, Hq, Xi, y, P, u, S, innov);
+            mfma4_update_col<GAPS>(Pp, f, Hk, Hq, Xi, y, P, u, S, innov);
             park[slot] = make_double2(S, innov);
             out.wP.store(P, t * 128u + out.offP);
             out.wm.store(u, t * 32u + out.offm);
         }
         if (out.want_nll) {
-            cum = out.flush_nll(park, lane, nsteps, cum, t0);
+            cum = out.template flush_nll<GAPS>(park, lane, nsteps, cum, t0, ychunk);
             wave_lds_fence();
         }
     }
@@ -385,10 +395,11 @@ __global__ void __launch_bounds__(64) cdeks4_mfma_kernel(SmootherIO io, ModelArg
     });
 }
 
+template <bool GAPS = false>
 inline int launch_cdekf4_mfma(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
     if (!mfma4_rows_fit(io.T)) return CGP_E_UNSUPPORTED;
-    hipLaunchKernelGGL(cdekf4_mfma_kernel, dim3((unsigned)io.B), dim3(64), 0, stream, io, ma);
+    hipLaunchKernelGGL(cdekf4_mfma_kernel<GAPS>, dim3((unsigned)io.B), dim3(64), 0, stream, io, ma);
     return hip_rc(hipGetLastError());
 }
 inline int launch_cdeks4_mfma(const SmootherIO& io, const ModelArgs& ma, hipStream_t stream) {
@@ -404,11 +415,17 @@ inline int launch_cdeks4_mfma(const SmootherIO& io, const ModelArgs& ma, hipStre
 }
 #endif  // CGP_NO_CD_EKF_KERNELS
 
-template <class SM>
+template <class SM, bool GAPS = false>
 inline int launch_cdsgp4_mfma(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
     if (!sgp4_mfma_fits(io.T, ma)) return CGP_E_UNSUPPORTED;
     const bool two = ma.sg.n_groups > 16;
+    if constexpr (GAPS) {                                                           // (CGP_SKIP_MISSING: whole records only, route_filter)
+        if (io.segs > 1) return CGP_E_UNSUPPORTED;
+        if (two) hipLaunchKernelGGL((cdsgp4_mfma_kernel<SM, true, false, true>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
+        else hipLaunchKernelGGL((cdsgp4_mfma_kernel<SM, false, false, true>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
+        return hip_rc(hipGetLastError());
+    }
     if (io.segs > 1) {                                                              // time-split: one wavefront per (trial, segment)
         const unsigned grid = (unsigned)(io.B * io.segs);
         if (two) hipLaunchKernelGGL((cdsgp4_mfma_kernel<SM, true, true>), dim3(grid), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);

@@ -112,7 +112,9 @@ CGP_DEV void sgp4_mfma_fan(const DM& model, const FanRegs& R, const Sgp4LaneCoef
 // E1 (round 4): the measurement vector is e_1, as in every chirp / La Scala builder of the reference (models.py:118) -- H then PICKS
 // entries of Pp (cgp_mfma4.hpp: ekf4_mfma_finish_j): Pp H by row is a row broadcast of Pp, S = Pp_11 + Xi a row broadcast of
 // (H Pp) by column, H . mp = mp_1 -- one matrix instruction where the general update has three, and no dot product.
-template <class DM, bool TWO, bool E1, bool SPLIT>
+// GAPS (CGP_SKIP_MISSING): a NaN measurement zeroes the gain's reciprocal and the innovation -- Pf = Pp and mf = mp exactly, as in
+// scalar_update (cgp_math.hpp) -- and adds nothing to the NLL (Tile4FilterOut::flush_nll).
+template <class DM, bool TWO, bool E1, bool SPLIT, bool GAPS = false>
 CGP_DEV void sgp4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
     static_assert(DM::D == 4, "d = 4 kernel");
     __shared__ double2 park[64];                                         // (S, innovation) of the chunk's steps, for the NLL
@@ -227,9 +229,14 @@ CGP_DEV void sgp4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
                 pred = fma(H3, f3, fma(H2, f2, fma(H1, f1, H0 * f0)));
             }
             const double innov = y - pred;
-            const double rS = rcp_nr1(S);
+            double rS = rcp_nr1(S), dy = innov;
+            if constexpr (GAPS) {                                        // (y is wave-uniform: one condition, two selects)
+                const bool gap = is_missing(y);
+                rS = gap ? 0.0 : rS;
+                dy = gap ? 0.0 : innov;
+            }
             P = fma(-(PHr * rS), PHc, Pp);                               // Pf = Pp - K (Pp H)^T
-            const double g = rS * innov;
+            const double g = rS * dy;
             u0 = fma(row_bcast_f64<0>(PHc), g, f0);                  // mf = mp + K innov
             u1 = fma(row_bcast_f64<1>(PHc), g, f1);
             u2 = fma(row_bcast_f64<2>(PHc), g, f2);
@@ -240,7 +247,7 @@ CGP_DEV void sgp4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
             wmc.store2(u2, u3, t * 32u + 16u + offm);
         }
         if (out.want_nll && !burn) {
-            cum = out.flush_nll(park, lane, nsteps, cum, t0);
+            cum = out.template flush_nll<GAPS>(park, lane, nsteps, cum, t0, ychunk);
             wave_lds_fence();
         }
     }
@@ -250,20 +257,27 @@ CGP_DEV void sgp4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
         Seg::put_nll(span.state, lane, cum);
     } else out.store_nll_total(io, trial, lane, cum);
 }
-template <class DM, bool TWO, bool SPLIT>
+template <class DM, bool TWO, bool SPLIT, bool GAPS = false>
 __global__ void __launch_bounds__(64) sgp4_mfma_kernel(FilterIO io, ModelArgs ma) {
+    static_assert(!(SPLIT && GAPS), "the time-split launches know no gaps");
     const int64_t trial = filter_span<SPLIT>(io, blockIdx.x).trial;
     if (trial >= io.B) return;
-    if (h_is_e1(io.H + trial * io.H_stride)) sgp4_mfma_trial<DM, TWO, true, SPLIT>(io, ma);
-    else sgp4_mfma_trial<DM, TWO, false, SPLIT>(io, ma);
+    if (h_is_e1(io.H + trial * io.H_stride)) sgp4_mfma_trial<DM, TWO, true, SPLIT, GAPS>(io, ma);
+    else sgp4_mfma_trial<DM, TWO, false, SPLIT, GAPS>(io, ma);
 }
 
 // The matrix-core kernel takes collapsible sets of at most 32 groups whose output windows fit a raw buffer.
-template <class DM>
+template <class DM, bool GAPS = false>
 inline int launch_sgp4_mfma(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
     if (!sgp4_mfma_fits(io.T, ma)) return CGP_E_UNSUPPORTED;
     const bool two = ma.sg.n_groups > 16;
+    if constexpr (GAPS) {                                                           // (CGP_SKIP_MISSING: whole records only, route_filter)
+        if (io.segs > 1) return CGP_E_UNSUPPORTED;
+        if (two) hipLaunchKernelGGL((sgp4_mfma_kernel<DM, true, false, true>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
+        else hipLaunchKernelGGL((sgp4_mfma_kernel<DM, false, false, true>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
+        return hip_rc(hipGetLastError());
+    }
     if (io.segs > 1) {                                                              // time-split: one wavefront per (trial, segment)
         const unsigned grid = (unsigned)(io.B * io.segs);
         if (two) hipLaunchKernelGGL((sgp4_mfma_kernel<DM, true, true>), dim3(grid), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);

@@ -90,6 +90,15 @@ inline bool lane4_smoother_fits(const SmootherIO& io) {
 // lane kernel it replaces there kept the round-3 limits of 20 / 24).  Smoothers: eks on the d = 4 chirp models beyond 24 trials per
 // SIMD -- 1.21 against 1.48 ms at 32 768 x 500, 8.0 against 10.6 ms at 262 144 x 500, the walk ahead below: 0.70 against 0.93 ms at
 // 16 384; profiles/r05_lane_smoothers.txt -- and cd_eks from 3: 1.74 against 2.48 ms at 4096 x 500.
+// Calls with CGP_SKIP_MISSING (tools/gaps_probe.py, flagged launches at T = 500 on 1024 SIMDs, one wavefront against one lane per trial,
+// the lane shape being the generic kernel's -- the large-batch lane kernels know no gaps):
+//     EKF, chirp d = 4 (the kernel for gaps, one trial per wave)             0.40 ms vs 0.92 at 2 K, 0.73 vs 0.99 at 4 K, 1.37 vs 1.01 at 8 K, 2.60 vs 1.04 at 16 K
+//                                                                           (linear in between: equal near 5.7 K trials)                         -> 11 / 2
+//     sigma-point filter GH-3, d = 4 (MFMA sums, GAPS form)                  0.73 vs 6.94 at 2 K, 1.41 vs 7.02 at 4 K, 2.74 vs 7.01 at 8 K, 5.32 vs 7.01 at 16 K
+//                                                                           (0.314 us a trial beyond: equal near 21.8 K, not measured there;
+//                                                                           other sets go by GH-3's figure, as they do unflagged)               -> 21
+// Every other flagged call -- cd_ekf, cd_sgp_filter, whatever the generic kernel runs -- is unmeasured and goes by the generic limits
+// ({5, 2}, sigma-point {8, 1}) whatever kernel it takes (route_filter).
 struct ShapeLimit { int num, den; };                      // one wavefront per trial while B * den < num * SIMDs; num < 0: always
 constexpr ShapeLimit kWaveAlways{-1, 1};
 inline bool choose_wave(int num_cus, int64_t B, uint32_t flags, ShapeLimit limit, const cgp_sigma* sg) {
@@ -119,6 +128,14 @@ enum class FilterRoute {
     kCdEkf4Mfma, kCdEkf4Coop, kCdSgp4Mfma, kCdSgp4Coop,        // continuous-discrete, d = 4
     kKpt8Coop, kGenericKpt                                     // ekf_for_kpt: tile layout / matrix cores, or filter_kernel in either shape
 };
+// CGP_SKIP_MISSING (include/chirpgp_hip.h, cgp_filter): a flagged call may only reach a kernel that honours the flag -- filter_kernel in
+// both shapes (the gate of scalar_update, cgp_math.hpp) and the one-wavefront-per-trial matrix-core kernels at d = 4, whose launchers
+// take the EKF's kernel for records with gaps or the GAPS instantiation of the others (cgp_inst_gaps4.hip, cgp_inst_gaps4_sigma.hip).
+// Every other route is replaced by the generic kernel of the shape the call has (route_filter).
+inline bool honours_gaps(FilterRoute r) {
+    return r == FilterRoute::kGenericWave || r == FilterRoute::kGenericLane || r == FilterRoute::kGenericKpt || r == FilterRoute::kEkf4Mfma ||
+           r == FilterRoute::kSgp4Mfma || r == FilterRoute::kCdEkf4Mfma || r == FilterRoute::kCdSgp4Mfma;
+}
 // the kernels that know the segments of a time-split launch (kEkf4Mfma: as kEkf4MfmaSeg)
 inline bool knows_segments(FilterRoute r) {
     return r == FilterRoute::kEkf4Mfma || r == FilterRoute::kSgp4Mfma || r == FilterRoute::kSgp8Coop || r == FilterRoute::kCdSgp4Mfma;
@@ -140,6 +157,7 @@ struct FilterDecision {
     bool wave = true;
     uint32_t flags = 0;              // the call's, with CGP_WAVE_PER_TRIAL where the segments force it
     int segs = 1;                    // effective: without the empty ones
+    bool gaps = false;               // CGP_SKIP_MISSING: the launcher of a matrix-core route takes the kernel's GAPS instantiation
     int64_t seg_len = 0;
 };
 
@@ -211,7 +229,18 @@ inline FilterDecision route_filter(const FilterQuery& q) {
     auto refuse = [&d](const char* message) { d.rc = CGP_E_UNSUPPORTED; d.message = message; return d; };
     const bool sig = q.method == CGP_F_SGP || q.method == CGP_F_CD_SGP;
     const int64_t B = q.io->B, T = q.io->T;
-    const WaveCandidate<FilterRoute> wave = filter_wave_candidate(q);
+    WaveCandidate<FilterRoute> wave = filter_wave_candidate(q);
+    d.gaps = (q.flags & CGP_SKIP_MISSING) != 0;
+    if (d.gaps) {
+        if (q.segments > 1)
+            return refuse("CGP_SKIP_MISSING goes with cgp_filter and cgp_filter_custom only: a time-split filter's burn-in that starts inside a gap "
+                          "has no junction to compare");
+        if (!honours_gaps(wave.route)) wave.route = q.model->model_id == CGP_M_KPT ? FilterRoute::kGenericKpt : FilterRoute::kGenericWave;
+        // the crossovers of flagged calls (see the measured ones above): against the generic lane kernel in every case
+        wave.limit = wave.route == FilterRoute::kEkf4Mfma ? ShapeLimit{11, 2} : wave.route == FilterRoute::kSgp4Mfma ? ShapeLimit{21, 1}
+                     : sig ? ShapeLimit{8, 1} : ShapeLimit{5, 2};
+        wave.limit_lane4 = wave.limit;
+    }
     // ---- time-split with burn-in (cgp_filter_time_split): segments of whole 64-step chunks, one wavefront each
     if (q.segments > 1) {
         // (kept as found: admission goes by the REQUESTED segments -- a record too short to split is refused all the same where the
@@ -231,7 +260,8 @@ inline FilterDecision route_filter(const FilterQuery& q) {
             d.flags |= CGP_WAVE_PER_TRIAL;
         }
     }
-    const FilterRoute lane = filter_lane_candidate(q, d.segs);
+    FilterRoute lane = filter_lane_candidate(q, d.segs);
+    if (d.gaps && !honours_gaps(lane)) lane = FilterRoute::kGenericLane;
     const bool lane4 = lane == FilterRoute::kLane4Ekf || lane == FilterRoute::kLane4Sgp;
     d.wave = choose_wave(q.num_cus, B, d.flags, lane4 ? wave.limit_lane4 : wave.limit, sig ? q.sigma : nullptr);
     // (kept as found: unreachable -- the segments set CGP_WAVE_PER_TRIAL, and the one thing that overrides it was refused above)
@@ -241,6 +271,7 @@ inline FilterDecision route_filter(const FilterQuery& q) {
         // beyond one wave per SIMD the four MFMA blocks carry four trials (CGP_ONE_TRIAL_PER_WAVE keeps one, for tests).  Kept as found:
         // "one wave per SIMD" is the literal 1024, whatever num_cus says.
         if (d.segs > 1) d.route = FilterRoute::kEkf4MfmaSeg;
+        else if (d.gaps) d.route = FilterRoute::kEkf4Mfma;        // (the four-trials-per-wavefront kernel knows no gaps)
         else if ((B > 1024 || (q.flags & CGP_FOUR_TRIALS_PER_WAVE)) && ekf4_mfma_x4_fits(*q.io) && !(q.flags & CGP_ONE_TRIAL_PER_WAVE))
             d.route = FilterRoute::kEkf4MfmaX4;
     }

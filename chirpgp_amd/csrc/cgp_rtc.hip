@@ -195,7 +195,7 @@ int cgp_filter_custom(cgp_ctx* ctx, const cgp_custom_model* m, const cgp_sigma* 
     io.H = init->H; io.H_stride = init->H_stride; io.Xi = init->Xi; io.Xi_stride = init->Xi_stride;
     io.m0 = init->m0; io.m0_stride = init->m0_stride; io.P0 = init->P0; io.P0_stride = init->P0_stride;
     io.ys = ys; io.ys_stride = ys_stride; io.ys_repeat = ys_repeat; io.ys_index = ys_index; io.B = B; io.T = T;
-    io.mfs = mfs; io.Pfs = Pfs; io.nll = nll; io.flags = flags & CGP_NLL_FINAL_ONLY;
+    io.mfs = mfs; io.Pfs = Pfs; io.nll = nll; io.flags = flags & (CGP_NLL_FINAL_ONLY | CGP_SKIP_MISSING);
     if (sigma && (!sigma->xi || !sigma->w || sigma->s < 1 || sigma->d != m->d)) return fail(ctx, CGP_E_ARG, "cgp_sigma needs xi, w, s >= 1 and d = the model's");
     ModelArgs ma = custom_args(params, param_stride, gamma, gamma_stride, dt, sigma);
     void* args[] = {&io, &ma};

@@ -7,7 +7,9 @@ filters_smoothers.py:26-36).  Differences a caller sees:
   a plain Python closure raises ``TypeError`` -- it cannot be run inside a HIP kernel and there is no CPU fallback;
 * ``ys`` (filters) and ``mfs, Pfs`` (smoothers) may carry a leading batch axis -- the reference's
   ``jax.vmap(..., in_axes=0)`` (tetralith/jobs/crlb_ekf.py:68-72); so may ``m0, P0, H, Xi`` and the model parameters;
-* NumPy in -> NumPy out, torch CUDA tensors in -> torch CUDA tensors out (results stay in HBM).
+* NumPy in -> NumPy out, torch CUDA tensors in -> torch CUDA tensors out (results stay in HBM);
+* every filter takes ``missing='skip'``: a NaN measurement is then a missing sample (the prediction is the step's result, its NLL
+  increment exactly 0) instead of the reference's poison -- records with dropped samples, gated segments or a tail to forecast.
 """
 import numpy as np
 
@@ -141,7 +143,7 @@ def cd_sgp_smoother(a, b, sgps, mfs, Pfs, dt, **kw):
     return E.run_smoother(E.S_CD_SGP, spec, _sgps(sgps, spec.d), _gamma_from_matrix(b), dt, mfs, Pfs, **kw)
 
 
-def _custom_kw(kw, allowed=('nll_final_only', 'want', 'flags')):
+def _custom_kw(kw, allowed=('nll_final_only', 'want', 'flags', 'missing')):
     """Keywords a runtime-compiled model understands (one launch shape, dense records); anything else is refused by name."""
     extra = set(kw) - set(allowed)
     if extra:

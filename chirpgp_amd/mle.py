@@ -25,7 +25,7 @@ def _rows_per_record(G, ys, record_index):
     return G // n_rec
 
 
-def batched_nll(method, build, thetas, ys, Xi, dt, sgps=None, record_index=None, **build_kw):
+def batched_nll(method, build, thetas, ys, Xi, dt, sgps=None, record_index=None, *, missing=None, **build_kw):
     """Final cumulative NLL of ``method`` for every row of ``thetas`` (unconstrained parameters, g() maps them to the
     positive model parameters as in the reference).  ``ys`` is ONE record (T,) read by all G rows, or R records (R, T) of
     which each serves G / R consecutive rows (``record_index`` (n,) first picks n of them: G / n rows each).  The records
@@ -34,10 +34,12 @@ def batched_nll(method, build, thetas, ys, Xi, dt, sgps=None, record_index=None,
 
     method: 'ekf' | 'sgp_filter' | 'cd_ekf' | 'cd_sgp_filter' with a 6-tuple builder (models.build_chirp_model,
     build_harmonic_chirp_model, build_lascala_model), or 'ekf_for_kpt' with models.build_kpt_chirp_model (pass ``fs=``,
-    ``num_harmonics=``): tetralith/jobs/kpt_mle.py:41-44."""
+    ``num_harmonics=``): tetralith/jobs/kpt_mle.py:41-44.
+
+    ``missing='skip'``: NaN samples of the records are gaps (filters_smoothers: the likelihood of the observed samples alone)."""
     thetas = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
     kw = dict(nll_final_only=True, want=(False, False, True), trials_per_record=_rows_per_record(thetas.shape[0], ys, record_index),
-              record_index=record_index)
+              record_index=record_index, missing=missing)
     with np.errstate(all='ignore'):        # a probe whose parameters under- or overflow yields a NaN objective, which the line search rejects
         built = build(M.g(thetas), **build_kw)
     if method == 'ekf_for_kpt':
@@ -188,6 +190,18 @@ EXACT_FROM_RECORDS = 1500
 
 def _exact_by_default(method, build, Xi, n_records, build_kw):
     return method == 'ekf' and has_exact_gradient(method, build, Xi) and not build_kw and n_records >= EXACT_FROM_RECORDS
+
+
+def _exact_with_gaps(exact, missing):
+    """``exact`` of an objective over records with gaps: the tangent kernels know no gaps (they take no flags, a NaN measurement
+    propagates there), so missing='skip' resolves exact=None to the difference gradient and refuses exact=True."""
+    from chirpgp_amd import _engine as E
+    if not E._missing_flag(missing):
+        return exact
+    if exact:
+        raise ValueError("exact=True does not go with missing='skip': the tangent kernels know no gaps (a NaN measurement propagates "
+                         "through them); the difference gradient (exact=False, the default here) does")
+    return False
 
 
 def _exact_unsupported():
@@ -353,12 +367,14 @@ def fit_scoring(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=100,
     return M.g(x), dict(fun=f, grad=g, nit=nit, launches=launches, converged=converged, fisher=F, mu=mu, history=history, iterates=iterates)
 
 
-def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=None, **build_kw):
+def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=None, *, missing=None, **build_kw):
     """-> fun(theta) returning (nll, gradient): value and central differences from one batched launch of 2 P + 1 filter passes, or --
     ``exact=True``, the discrete EKF or the sigma-point filter (with a d = 4 ``sgps``) on the chirp / La Scala models -- value and EXACT
     gradient from one launch of a tangent kernel (cgp_ekf_nll_grad: within 8e-13 of the gradient's scale against 100-digit arithmetic where
     the differences carry 2e-7; slower for a single record, see EXACT_FROM_RECORDS; cgp_sgp_nll_grad).  exact=None takes the tangent kernel
-    for the EKF from EXACT_FROM_RECORDS records only and never for the sigma-point filter."""
+    for the EKF from EXACT_FROM_RECORDS records only and never for the sigma-point filter.  ``missing='skip'`` (a record with gaps):
+    differences only."""
+    exact = _exact_with_gaps(exact, missing)
     if exact is None:
         exact = _exact_by_default(method, build, Xi, 1, build_kw)
     if exact:
@@ -382,7 +398,7 @@ def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=No
         for i in range(P):
             batch[1 + 2 * i, i] += h[i]
             batch[2 + 2 * i, i] -= h[i]
-        nll = batched_nll(method, build, batch, ys, Xi, dt, sgps, **build_kw)
+        nll = batched_nll(method, build, batch, ys, Xi, dt, sgps, missing=missing, **build_kw)
         grad = (nll[1::2] - nll[2::2]) / (2 * h)
         f = float(nll[0])
         if not np.isfinite(f):                      # diverged filter: the reference writes NaN results and moves on
@@ -395,7 +411,7 @@ def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=No
 DIFFERENCE_STOP = dict(ftol=1e-13, gtol=1e-7)
 
 
-def fit(method, build, init_params, ys, Xi, dt, sgps=None, maxiter=200, exact=None, **build_kw):
+def fit(method, build, init_params, ys, Xi, dt, sgps=None, maxiter=200, exact=None, *, missing=None, **build_kw):
     """L-BFGS-B from ``init_params`` (positive model parameters, e.g. [0.1, 0.1, 0.1, 1, 1, 7]).
     Returns (opt_params, scipy OptimizeResult).
 
@@ -407,20 +423,22 @@ def fit(method, build, init_params, ys, Xi, dt, sgps=None, maxiter=200, exact=No
     the optimum, for 60 - 85 objective launches where the default took 45 - 55.  (The tangent kernels' searches, exact=True, keep
     SciPy's rule.)"""
     from scipy.optimize import minimize
+    exact = _exact_with_gaps(exact, missing)
     if exact is None:
         exact = _exact_by_default(method, build, Xi, 1, build_kw)
-    fun = make_objective(method, build, ys, Xi, dt, sgps, exact=exact, **build_kw)
+    fun = make_objective(method, build, ys, Xi, dt, sgps, exact=exact, missing=missing, **build_kw)
     stop = {} if exact else DIFFERENCE_STOP
     res = minimize(fun, M.g_inv(np.asarray(init_params, dtype=np.float64)), jac=True, method='L-BFGS-B',
                    options=dict(maxiter=maxiter, **stop))
     return M.g(res.x), res
 
 
-def _value_and_grad_many(method, build, thetas, yss, Xi, dt, sgps, rel_step, build_kw, record_index=None, exact=None):
+def _value_and_grad_many(method, build, thetas, yss, Xi, dt, sgps, rel_step, build_kw, record_index=None, exact=None, missing=None):
     """NLL and gradient of R records (the rows ``record_index`` of yss; all of them by default) at R parameter vectors: exact (the tangent
     kernel, R P lanes) for the discrete EKF on the chirp / La Scala models (and, with exact=True, the sigma-point filter's, R wavefronts),
     else central differences -- ONE launch of R (2 P + 1) trials, each record read in place by its 2 P + 1 probes."""
     R, P = thetas.shape
+    exact = _exact_with_gaps(exact, missing)
     if exact is None:
         exact = _exact_by_default(method, build, Xi, R, build_kw)
     if exact:
@@ -435,7 +453,7 @@ def _value_and_grad_many(method, build, thetas, yss, Xi, dt, sgps, rel_step, bui
     idx = np.arange(P)
     batch[:, 1 + 2 * idx, idx] += h
     batch[:, 2 + 2 * idx, idx] -= h
-    nll = batched_nll(method, build, batch.reshape(-1, P), yss, Xi, dt, sgps, record_index=record_index, **build_kw).reshape(R, 2 * P + 1)
+    nll = batched_nll(method, build, batch.reshape(-1, P), yss, Xi, dt, sgps, record_index=record_index, missing=missing, **build_kw).reshape(R, 2 * P + 1)
     f = nll[:, 0].copy()
     grad = (nll[:, 1::2] - nll[:, 2::2]) / (2 * h)
     f[~np.isfinite(f)] = np.inf
@@ -443,14 +461,15 @@ def _value_and_grad_many(method, build, thetas, yss, Xi, dt, sgps, rel_step, bui
 
 
 def fit_many(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=200, history=10, gtol=1e-5, ftol=2.2e-9,
-             rel_step=1e-6, exact=None, **build_kw):
+             rel_step=1e-6, exact=None, *, missing=None, **build_kw):
     """Maximum likelihood for R measurement records in lock step: limited-memory BFGS with a backtracking (Armijo) line
     search, every record with its own iterate, history and step length, and every probe of every record evaluated in
     the SAME kernel launch (R x 13 trials for the chirp model).  A launch costs T x 0.35 us whatever the batch up to
     ~4000 trials, so R records take the wall time of one -- the reference's Monte-Carlo jobs (tetralith/jobs/*_mle.py)
     run one L-BFGS-B per record.  Same objective, same unconstrained parametrisation g() as :func:`fit`.
 
-    yss (R, T);  init_params (P,) or (R, P) positive model parameters  ->  (opt_params (R, P), info dict)."""
+    yss (R, T);  init_params (P,) or (R, P) positive model parameters  ->  (opt_params (R, P), info dict).
+    ``missing='skip'``: NaN samples of the records are gaps (difference gradient only, as in :func:`make_objective`)."""
     from chirpgp_amd import _engine as E
     yss = E.dev(yss)                                  # uploaded once; every probe of every line search reads it in place
     if yss.ndim == 1:
@@ -458,7 +477,7 @@ def fit_many(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=200, hi
     R = yss.shape[0]
     x = np.array(np.broadcast_to(M.g_inv(np.asarray(init_params, dtype=np.float64)), (R, np.shape(init_params)[-1])))
     P = x.shape[1]
-    f, g = _value_and_grad_many(method, build, x, yss, Xi, dt, sgps, rel_step, build_kw, exact=exact)
+    f, g = _value_and_grad_many(method, build, x, yss, Xi, dt, sgps, rel_step, build_kw, exact=exact, missing=missing)
     S, Y = [], []                                    # lists of (R, P) pairs, newest last
     done = ~np.isfinite(f)
     nit = np.zeros(R, dtype=int)
@@ -493,7 +512,7 @@ def fit_many(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=200, hi
                 break
             idx = np.flatnonzero(searching)
             xt = x[idx] + step[idx, None] * d[idx]
-            ft, gt = _value_and_grad_many(method, build, xt, yss, Xi, dt, sgps, rel_step, build_kw, record_index=idx, exact=exact)
+            ft, gt = _value_and_grad_many(method, build, xt, yss, Xi, dt, sgps, rel_step, build_kw, record_index=idx, exact=exact, missing=missing)
             launches += 1
             ok = ft <= f[idx] + 1e-4 * step[idx] * gd[idx]
             acc = idx[ok]

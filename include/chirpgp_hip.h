@@ -166,7 +166,8 @@ typedef struct cgp_init {
                                         composed maps are exact in exact arithmetic but only as accurate as products of the caller's gains
                                         are well conditioned (1e-11 of the one-wave walk for the chirp models, 1e-7 seen for a random F)   */
 #define CGP_NO_TIME_SPLIT     0x1000u /* ... never                                                                                      */
-#define CGP_SIM_FIXED_X0      0x20u  /* cgp_simulate: x_0 = m0 exactly, P0 unused (simulate_sde_init, simulate_lgssm)       */
+#define CGP_SKIP_MISSING      0x2000u /* filters (cgp_filter, cgp_filter_custom): a NaN measurement is a missing sample, not poison -- see cgp_filter */
+#define CGP_SIM_FIXED_X0      0x20u /* cgp_simulate: x_0 = m0 exactly, P0 unused (simulate_sde_init, simulate_lgssm)       */
 
 /* ---- error codes ---------------------------------------------------------------------------------------- */
 #define CGP_OK              0
@@ -192,7 +193,22 @@ const char* cgp_last_error(const cgp_ctx* ctx);
  *               shared by every trial; any value >= 0 is legal (records are only read, they may overlap)
  *   ys_repeat   >= 1; consecutive trials served by the same record (G grid points or 2 P + 1 gradient probes per record)
  *   ys_index    NULL, or a DEVICE array of ceil(B / ys_repeat) record numbers (a subset / permutation of the records)
- * The dense batched call is (ys_stride, ys_repeat, ys_index) = (T, 1, NULL). */
+ * The dense batched call is (ys_stride, ys_repeat, ys_index) = (T, 1, NULL).
+ *
+ * Missing measurements.  By default a NaN measurement is what it is in the reference: it poisons the state, and the rest of the
+ * record comes out as NaN.  With CGP_SKIP_MISSING a step whose measurement is NaN is a gap:
+ *   - mf_t = mp_t and Pf_t = Pp_t: the prediction is the filtering result;
+ *   - its NLL increment is exactly +0.0: the cumulative NLL at a gap is the previous step's, bit for bit (0.0 before the first step);
+ *   - "missing" is decided from the measurement alone (y != y), never from the innovation or from S: a filter that has diverged (a NaN
+ *     state, a finite y) still propagates NaN and a NaN NLL, and +-inf is a measurement, not a gap;
+ *   - shared and indexed records work unchanged (the gate reads whatever record the trial reads); a record of NaN only is a pure
+ *     forecast: finite rows, NLL identically 0.
+ * Without the flag nothing changes.  The smoothers need no flag: they read mfs / Pfs and predict again.  The flag is honoured by the
+ * generic kernels (every method, model, dimension and launch shape, cgp_filter_custom included) and by the one-wavefront-per-trial
+ * matrix-core kernels of ekf, sgp_filter, cd_ekf and cd_sgp_filter on the d = 4 chirp / La Scala models; every other specialised kernel
+ * (kf at d = 4, d = 6 / 8, ekf_for_kpt's tile layout, the DPP variants, the four-trials-per-wavefront EKF, the large-batch lane kernels)
+ * hands a flagged call to the generic kernel in the launch shape the call has.  cgp_filter_time_split refuses the flag (CGP_E_UNSUPPORTED): a burn-in that starts inside a gap has no
+ * junction to compare.  The gradient and Fisher entries take no flags; a NaN propagates there. */
 int cgp_filter(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init,
                double dt, const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index,
                int64_t B, int64_t T, double* mfs, double* Pfs, double* nll, uint32_t flags, void* stream);
