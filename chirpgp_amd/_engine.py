@@ -588,29 +588,31 @@ DIR_DOUBLES = 24        # include/chirpgp_hip.h: CGP_DIR_DOUBLES
 FISHER_MAX_DIR = 16     # include/chirpgp_hip.h: CGP_FISHER_MAX_DIR
 
 
-def run_ekf_nll_grad(spec, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None):
+def run_ekf_nll_grad(spec, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None, missing=None):
     """cgp_ekf_nll_grad: the EKF's final NLL and its derivative along `dirs` (B, n_dir, 24) -- forward tangents through the scan, one
-    launch.  ys (T,) or (R, T) with the shared-record addressing of run_filter.  Returns (nll (B,), grad (B, n_dir)) as device tensors."""
-    return _run_nll_grad(spec, None, False, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
+    launch.  ys (T,) or (R, T) with the shared-record addressing of run_filter.  Returns (nll (B,), grad (B, n_dir)) as device tensors.
+    ``missing='skip'`` (CGP_SKIP_MISSING, here and in the three entry points below): a NaN measurement is a missing sample -- the step adds
+    exactly nothing to nll, grad and fisher -- instead of the poison it is by default (None / 'propagate')."""
+    return _run_nll_grad(spec, None, False, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing)
 
 
-def run_sgp_nll_grad(spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None):
+def run_sgp_nll_grad(spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None, missing=None):
     """cgp_sgp_nll_grad: the sigma-point filter's final NLL and its derivative along `dirs` (B, n_dir, 24), any d = 4 SigmaPoints `sgps`
     -- forward tangents through the scan, one launch; arguments and results as run_ekf_nll_grad.  The kernel sums over the points
     literally, so the set goes over ungrouped."""
-    return _run_nll_grad(spec, _need_sigma(sgps, 'cgp_sgp_nll_grad'), False, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
+    return _run_nll_grad(spec, _need_sigma(sgps, 'cgp_sgp_nll_grad'), False, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing)
 
 
-def run_ekf_nll_fisher(spec, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None):
+def run_ekf_nll_fisher(spec, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None, missing=None):
     """cgp_ekf_nll_fisher: run_ekf_nll_grad's results and the Fisher information of the EKF's Gaussian innovations model along `dirs`
     (B, n_dir <= 16, 24), sum_t (d nu_i d nu_j / S + d S_i d S_j / (2 S^2)) -- one launch.  Returns (nll (B,), grad (B, n_dir),
     fisher (B, n_dir, n_dir)) as device tensors."""
-    return _run_nll_grad(spec, None, True, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
+    return _run_nll_grad(spec, None, True, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing)
 
 
-def run_sgp_nll_fisher(spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None):
+def run_sgp_nll_fisher(spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None, missing=None):
     """cgp_sgp_nll_fisher: the same for the sigma-point filter, any d = 4 SigmaPoints `sgps`; arguments and results as run_ekf_nll_fisher."""
-    return _run_nll_grad(spec, _need_sigma(sgps, 'cgp_sgp_nll_fisher'), True, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index)
+    return _run_nll_grad(spec, _need_sigma(sgps, 'cgp_sgp_nll_fisher'), True, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing)
 
 
 def _need_sigma(sgps, entry):
@@ -619,8 +621,10 @@ def _need_sigma(sgps, entry):
     return sgps
 
 
-def _run_nll_grad(spec, sgps, fisher, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index):
-    """The four tangent entry points: the sigma-point filter's with `sgps`, the EKF's with None; `fisher`: the matrix as a third output."""
+def _run_nll_grad(spec, sgps, fisher, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing=None):
+    """The four tangent entry points: the sigma-point filter's with `sgps`, the EKF's with None; `fisher`: the matrix as a third output;
+    `missing`: as run_filter's, through _missing_flag."""
+    gaps = _missing_flag(missing)
     torch = _torch()
     ys_d = dev(ys)
     if ys_d.ndim == 1:
@@ -644,7 +648,7 @@ def _run_nll_grad(spec, sgps, fisher, H, Xi, m0, P0, dt, ys, dirs, trials_per_re
         entry = f'cgp_{"ekf" if sgps is None else "sgp"}_nll_{"fisher" if fisher else "grad"}'
         sig = [] if sgps is None else [C.byref(_sigma_struct(sgps, d, keep, None))]
         rc = _timed('filter', lambda: getattr(load_library(), entry)(ctx, C.byref(model), *sig, C.byref(init), float(dt), _ptr(ys_d), T, rep, _ptr(idx_d),
-                                                                     B, T, _ptr(dirs_d), n_dir, *(_ptr(o) for o in outs), 0, _stream()))
+                                                                     B, T, _ptr(dirs_d), n_dir, *(_ptr(o) for o in outs), gaps, _stream()))
         _check(ctx, rc, entry)
         return tuple(outs)
 

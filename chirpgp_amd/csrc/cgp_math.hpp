@@ -132,6 +132,33 @@ template <int D> CGP_DEV void cho_solve_mat(const Sym<D>& L, const Vec<D>& inv_d
 // reciprocal and the innovation, so that Pf = fma(-(PH 0), PH, Pp) = Pp and mf = fma(PH 0, 0, mp) = mp exactly for finite operands,
 // while a present measurement runs the very operations of the unflagged step.  The caller adds no NLL for such a step (is_missing).
 CGP_DEV bool is_missing(double y) { return y != y; }
+// The same gate for an update written out with its tangents (cgp_tangent4.hpp: tangent_update; cgp_tangent4_sigma.hpp): GAPS and a NaN
+// measurement zero the gain's reciprocal and the innovation in place, two selects, and the step is reported as a gap -- the caller adds
+// +0.0 to the NLL for it.  Every product that carries one of the two is then an exact zero for finite operands: K = PH 0,
+// dK = (dPH - K dS) 0, the gradient's increment and the Fisher weights iS and iS^2 / 2.  Not GAPS: nothing, and false at compile time.
+template <bool GAPS>
+CGP_DEV bool gate_missing(double y, double& iS, double& nu) {
+    if constexpr (GAPS) {
+        const bool gap = is_missing(y);
+        iS = gap ? 0.0 : iS;
+        nu = gap ? 0.0 : nu;
+        return gap;
+    } else {
+        return false;
+    }
+}
+// ... and the NLL's increment of such a step, the third select: +0.0 at a gap.  The increment is pinned (an empty asm on its registers), so
+// that it is computed on every path and the select is a v_cndmask pair: left to itself the compiler moves the ~80 instructions of
+// nll_increment into a block of their own behind an s_cbranch_execz -- a branch in a step that is to run the unflagged step's operations.
+template <bool GAPS>
+CGP_DEV double gated_increment(bool gap, double inc) {
+    if constexpr (GAPS) {
+        asm volatile("" : "+v"(inc));
+        return gap ? 0.0 : inc;
+    } else {
+        return inc;
+    }
+}
 template <int D>
 CGP_DEV void scalar_update(const Vec<D>& mp, const Sym<D>& Pp, const Vec<D>& H, double Xi, double y,
                            bool override_pred, double pred_in, Vec<D>& mf, Sym<D>& Pf, double& S_out, double& innov_out,

@@ -82,6 +82,11 @@ struct TangentUpdate {
         return fma(dnu * nj, wn, fma(dS * sj, ws, Fij));
     }
 };
+// GAPS (CGP_SKIP_MISSING): a NaN measurement is a missing sample -- gate_missing (cgp_math.hpp) zeroes iS and nu, so that mf = mp, Pf = Pp,
+// d mf = d mp, d Pf = d Pp, and the increments of d nll and of the Fisher row (weights iS, iS^2 / 2) are exact zeros; the NLL's own
+// increment takes the third select.  No branch: a present measurement runs the operations of the unflagged step.  Defaulted: the
+// unflagged kernels compile to what they compiled to.
+template <bool GAPS = false>
 CGP_DEV TangentUpdate tangent_update(const double (&h)[4], double Xi, double dXi, double y, const double (&mp)[4], const double (&dmp)[4],
                                      const double (&Pp)[10], const double (&dPp)[10], double (&m)[4], double (&dm)[4],
                                      double (&P)[10], double (&dP)[10], double& nll, double& dnll) {
@@ -98,6 +103,7 @@ CGP_DEV TangentUpdate tangent_update(const double (&h)[4], double Xi, double dXi
     const double pred = h[0] * mp[0] + h[1] * mp[1] + h[2] * mp[2] + h[3] * mp[3];
     u.nu = y - pred;
     u.dnu = -(h[0] * dmp[0] + h[1] * dmp[1] + h[2] * dmp[2] + h[3] * dmp[3]);
+    const bool gap = gate_missing<GAPS>(y, u.iS, u.nu);
     const double S = u.S, dS = u.dS, iS = u.iS, nu = u.nu, dnu = u.dnu;
     double K[4], dK[4];
     CGP_UNROLL for (int i = 0; i < 4; i++) { K[i] = PH[i] * iS; dK[i] = (dPH[i] - K[i] * dS) * iS; }
@@ -109,7 +115,7 @@ CGP_DEV TangentUpdate tangent_update(const double (&h)[4], double Xi, double dXi
         dP[kk] = dPp[kk] - (dK[i] * K[j] + K[i] * dK[j]) * S - kk_ij * dS;
         kk++;
     }
-    nll += nll_increment(S, nu);
+    nll += gated_increment<GAPS>(gap, nll_increment(S, nu));
     dnll += 0.5 * (dS * iS + (2.0 * nu * dnu - nu * nu * dS * iS) * iS);
     return u;
 }
@@ -121,11 +127,30 @@ struct TangentCall {
     bool sgp, fisher;                    // takes a sigma-point set (sigma-point sets beyond the LDS stage are refused) / writes the matrix
 };
 
-// The argument checks in the ABI's order, then io and ma filled.  -> CGP_OK with io.B > 0: launch; CGP_OK with io.B == 0: nothing to do
+// The header's name of one flag bit, for the message that refuses it
+inline const char* tangent_flag_name(uint32_t bit) {
+    switch (bit) {
+    case CGP_NLL_FINAL_ONLY: return "CGP_NLL_FINAL_ONLY";
+    case CGP_WAVE_PER_TRIAL: return "CGP_WAVE_PER_TRIAL";
+    case CGP_THREAD_PER_TRIAL: return "CGP_THREAD_PER_TRIAL";
+    case CGP_SEQUENTIAL_SCAN: return "CGP_SEQUENTIAL_SCAN";
+    case CGP_GENERIC_KERNEL: return "CGP_GENERIC_KERNEL";
+    case CGP_SIM_FIXED_X0: return "CGP_SIM_FIXED_X0";
+    case CGP_LITERAL_SIGMA_SUM: return "CGP_LITERAL_SIGMA_SUM";
+    case CGP_DPP_KERNEL: return "CGP_DPP_KERNEL";
+    case CGP_FOUR_TRIALS_PER_WAVE: return "CGP_FOUR_TRIALS_PER_WAVE";
+    case CGP_ONE_TRIAL_PER_WAVE: return "CGP_ONE_TRIAL_PER_WAVE";
+    case CGP_TIME_SPLIT: return "CGP_TIME_SPLIT";
+    case CGP_NO_TIME_SPLIT: return "CGP_NO_TIME_SPLIT";
+    default: return "no flag of chirpgp_hip.h";
+    }
+}
+
+// The argument checks in the ABI's order (flags last: CGP_SKIP_MISSING or nothing), then io and ma filled.  -> CGP_OK with io.B > 0: launch; CGP_OK with io.B == 0: nothing to do
 // (B == 0 or n_dir == 0, decided before anything else is looked at); otherwise the code, with the message left in the context.
 inline int tangent_args(cgp_ctx* ctx, TangentCall call, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init, double dt,
                         const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
-                        const double* dirs, int32_t n_dir, double* nll, double* grad, double* fisher, TangentIO& io, ModelArgs& ma) {
+                        const double* dirs, int32_t n_dir, double* nll, double* grad, double* fisher, uint32_t flags, TangentIO& io, ModelArgs& ma) {
     const std::string entry = call.entry;
     io.B = 0;
     if (!ctx) return CGP_E_ARG;
@@ -150,6 +175,12 @@ inline int tangent_args(cgp_ctx* ctx, TangentCall call, const cgp_model* model, 
     if (ys_stride < 0 || ys_repeat < 1) return fail(ctx, CGP_E_ARG, "ys_stride must be >= 0 and ys_repeat >= 1");
     if (!dirs || !nll || !grad || (call.fisher && !fisher))
         return fail(ctx, CGP_E_ARG, call.fisher ? "dirs / nll / grad / fisher must be set" : "dirs / nll / grad must be set");
+    if (const uint32_t other = flags & ~(uint32_t)CGP_SKIP_MISSING) {     // the one flag these entry points take
+        const uint32_t bit = other & (~other + 1u);                       // the lowest bit that is not it
+        char hex[16];
+        snprintf(hex, sizeof hex, "0x%x", (unsigned)bit);
+        return fail(ctx, CGP_E_ARG, entry + " takes CGP_SKIP_MISSING and no other flag: bit " + hex + " (" + tangent_flag_name(bit) + ") is set");
+    }
     io.H = init->H; io.H_stride = init->H_stride; io.Xi = init->Xi; io.Xi_stride = init->Xi_stride;
     io.m0 = init->m0; io.m0_stride = init->m0_stride; io.P0 = init->P0; io.P0_stride = init->P0_stride;
     io.ys = ys; io.ys_stride = ys_stride; io.ys_repeat = ys_repeat; io.ys_index = ys_index;
@@ -171,7 +202,9 @@ inline int tangent_launch(cgp_ctx* ctx, Launch launch) {
 }
 
 #ifndef CGP_TANGENT4_IO_ONLY      // the sigma-point units take TangentIO and not a second copy of this kernel
-template <int kSlots>                 // 0: cgp_ekf_nll_grad; 4 / 6 / 8 / 16: cgp_ekf_nll_fisher with n_dir <= kSlots
+// GAPS: the update gated per lane on its trial's measurement (tangent_update; the lanes of a trial read the same y, the trials of a
+// wavefront of the Fisher form need not) -- the shuffles stay unguarded.  Instantiated in cgp_inst_gaps4_tangent.hip only.
+template <int kSlots, bool GAPS = false>      // 0: cgp_ekf_nll_grad; 4 / 6 / 8 / 16: cgp_ekf_nll_fisher with n_dir <= kSlots
 __global__ void __launch_bounds__(64) ekf4_tangent_kernel(TangentIO io, ModelArgs ma) {
     constexpr bool kFisher = kSlots > 0;
     int64_t gidx;
@@ -276,7 +309,7 @@ __global__ void __launch_bounds__(64) ekf4_tangent_kernel(TangentIO io, ModelArg
             }
             // ---- update and its tangent; kFisher: d nu and d S of the trial's other directions into this lane's row
             const double mpv[4] = {mp0, mp1, mp2, mp3}, dmpv[4] = {dmp0, dmp1, dmp2, dmp3};
-            const TangentUpdate u = tangent_update(h, Xi, dXi, y, mpv, dmpv, Pp, dPp, m, dm, P, dP, nll, dnll);
+            const TangentUpdate u = tangent_update<GAPS>(h, Xi, dXi, y, mpv, dmpv, Pp, dPp, m, dm, P, dP, nll, dnll);
             if constexpr (kFisher) {
                 double nj[kSlots], sj[kSlots];
                 CGP_UNROLL for (int j = 0; j < kSlots; j++) { nj[j] = shuffle_f64(u.dnu, base + j); sj[j] = shuffle_f64(u.dS, base + j); }
@@ -299,15 +332,29 @@ __global__ void __launch_bounds__(64) ekf4_tangent_kernel(TangentIO io, ModelArg
 }
 
 // kSlots > 0: 64 / n_dir whole trials per wavefront; 1 <= n_dir <= kSlots and ceil(B / (64 / n_dir)) < 2^31 (the caller).
-template <int kSlots = 0>
+template <int kSlots = 0, bool GAPS = false>
 inline hipError_t launch_ekf4_tangent(const TangentIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.n_dir <= 0) return hipSuccess;                    // (T == 0 launches: the kernel skips its loop and writes nll = 0, grad = 0)
     const int64_t total = io.B * io.n_dir, tpw = 64 / io.n_dir;
     const int64_t blocks = kSlots > 0 ? (io.B + tpw - 1) / tpw : (total + 63) / 64;
-    hipLaunchKernelGGL(ekf4_tangent_kernel<kSlots>, dim3((unsigned)blocks), dim3(64), 0, stream, io, ma);
+    hipLaunchKernelGGL((ekf4_tangent_kernel<kSlots, GAPS>), dim3((unsigned)blocks), dim3(64), 0, stream, io, ma);
     return hipGetLastError();
 }
 
+// cgp_ekf_nll_fisher: the smallest compiled row that holds n_dir slots (a template: only the unit that calls it compiles its kernels)
+template <bool GAPS = false>
+inline hipError_t launch_ekf4_fisher(const TangentIO& io, const ModelArgs& ma, hipStream_t stream) {
+    if (io.n_dir <= 4) return launch_ekf4_tangent<4, GAPS>(io, ma, stream);
+    if (io.n_dir <= 6) return launch_ekf4_tangent<6, GAPS>(io, ma, stream);
+    if (io.n_dir <= 8) return launch_ekf4_tangent<8, GAPS>(io, ma, stream);
+    return launch_ekf4_tangent<kFisherMaxDir, GAPS>(io, ma, stream);
+}
+
 #endif  // CGP_TANGENT4_IO_ONLY
+
+// The GAPS instantiations (CGP_SKIP_MISSING) live in units of their own -- cgp_inst_gaps4_tangent.hip, cgp_inst_gaps4_tangent_sgp.hip -- so
+// that the unflagged units compile to what they compiled to; fisher: the form that writes the matrix.
+hipError_t launch_ekf4_tangent_gaps(const TangentIO& io, const ModelArgs& ma, bool fisher, hipStream_t stream);
+hipError_t launch_sgp4_tangent_gaps(const TangentIO& io, const ModelArgs& ma, bool fisher, hipStream_t stream);
 
 }  // namespace cgp

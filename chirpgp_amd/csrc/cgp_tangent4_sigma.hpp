@@ -97,7 +97,9 @@ struct FanPoint {
     }
 };
 
-template <bool kFisher>
+// GAPS (CGP_SKIP_MISSING): the update gated on the step's measurement, the wavefront's one y (gate_missing, cgp_math.hpp; as tangent_update
+// of cgp_tangent4.hpp).  Instantiated in cgp_inst_gaps4_tangent_sgp.hip only.
+template <bool kFisher, bool GAPS = false>
 __global__ void __launch_bounds__(64) sgp4_tangent_kernel(SgpTangentIO sio, ModelArgs ma) {
     __shared__ double red[kFanLdsDoubles];
     __shared__ __attribute__((aligned(16))) double dtab[(kSgpMaxDir + 1) * kSgpDirPitch];
@@ -242,10 +244,11 @@ __global__ void __launch_bounds__(64) sgp4_tangent_kernel(SgpTangentIO sio, Mode
             }
             const double S = h[0] * PH[0] + h[1] * PH[1] + h[2] * PH[2] + h[3] * PH[3] + Xi;
             const double dS_ = h[0] * dPH[0] + h[1] * dPH[1] + h[2] * dPH[2] + h[3] * dPH[3] + dXi;
-            const double iS = rcp_nr(S);
+            double iS = rcp_nr(S);
             const double pred = h[0] * mp[0] + h[1] * mp[1] + h[2] * mp[2] + h[3] * mp[3];
-            const double nu = y - pred;
+            double nu = y - pred;
             const double dnu = -(h[0] * dmp[0] + h[1] * dmp[1] + h[2] * dmp[2] + h[3] * dmp[3]);
+            const bool gap = gate_missing<GAPS>(y, iS, nu);                // GAPS and a NaN y: iS = nu = 0; otherwise nothing, false
             double K[4], dK[4];
             CGP_UNROLL for (int i = 0; i < 4; i++) { K[i] = PH[i] * iS; dK[i] = (dPH[i] - K[i] * dS_) * iS; }
             CGP_UNROLL for (int i = 0; i < 4; i++) { m[i] = mp[i] + K[i] * nu; dm[i] = dmp[i] + dK[i] * nu + K[i] * dnu; }
@@ -255,7 +258,7 @@ __global__ void __launch_bounds__(64) sgp4_tangent_kernel(SgpTangentIO sio, Mode
                     P(i, j) = Pp(i, j) - kk * S;
                     dP(i, j) = dPp(i, j) - (dK[i] * K[j] + K[i] * dK[j]) * S - kk * dS_;
                 }
-            nll += nll_increment(S, nu);
+            nll += gated_increment<GAPS>(gap, nll_increment(S, nu));
             dnll += 0.5 * (dS_ * iS + (2.0 * nu * dnu - nu * nu * dS_ * iS) * iS);
             if constexpr (kFisher) {
                 // F[lane][j] += d nu_lane d nu_j / S + d S_lane d S_j / (2 S^2), as cgp_tangent4.hpp: S is replicated, the products commute
@@ -286,14 +289,14 @@ __global__ void __launch_bounds__(64) sgp4_tangent_kernel(SgpTangentIO sio, Mode
 
 // One launch per slice of kSgpMaxDir directions; every slice repeats the primal (nll is written by the first).  B < 2^31 (the caller).
 // kFisher: n_dir <= kSgpMaxDir (the caller), so there is one slice with every direction in it.
-template <bool kFisher = false>
+template <bool kFisher = false, bool GAPS = false>
 inline hipError_t launch_sgp4_tangent(const TangentIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.n_dir <= 0) return hipSuccess;
     for (int dir0 = 0; dir0 < io.n_dir; dir0 += kSgpMaxDir) {
         SgpTangentIO sio;
         sio.t = io; sio.dir0 = dir0;
         sio.nd = io.n_dir - dir0 < kSgpMaxDir ? io.n_dir - dir0 : kSgpMaxDir;
-        hipLaunchKernelGGL(sgp4_tangent_kernel<kFisher>, dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, sio, ma);
+        hipLaunchKernelGGL((sgp4_tangent_kernel<kFisher, GAPS>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, sio, ma);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

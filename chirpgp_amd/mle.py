@@ -209,8 +209,9 @@ def _exact_unsupported():
                       'set, sgps=) on build_chirp_model / build_lascala_model with a scalar Xi')
 
 
-def _tangent_launch(fisher, build, thetas, ys, Xi, dt, record_index, method, sgps):
-    """One launch of a tangent kernel along tangent_directions at every row of thetas: (nll, grad) or, fisher, (nll, grad, F) as NumPy."""
+def _tangent_launch(fisher, build, thetas, ys, Xi, dt, record_index, method, sgps, missing=None):
+    """One launch of a tangent kernel along tangent_directions at every row of thetas: (nll, grad) or, fisher, (nll, grad, F) as NumPy.
+    ``missing='skip'``: NaN samples of the records are gaps (CGP_SKIP_MISSING: such a step adds exactly nothing to any of the three)."""
     from chirpgp_amd import _engine as E
     if not has_exact_gradient(method, build, Xi, sgps):
         raise _exact_unsupported()
@@ -220,25 +221,30 @@ def _tangent_launch(fisher, build, thetas, ys, Xi, dt, record_index, method, sgp
         drift, disp, disc, m0, P0, H = build(M.g(thetas))
     dirs = tangent_directions(build, thetas, dt, Xi)
     if method == 'sgp_filter':
-        out = (E.run_sgp_nll_fisher if fisher else E.run_sgp_nll_grad)(disc, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=rows, record_index=record_index)
+        out = (E.run_sgp_nll_fisher if fisher else E.run_sgp_nll_grad)(disc, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=rows, record_index=record_index,
+                                                                       missing=missing)
     else:
-        out = (E.run_ekf_nll_fisher if fisher else E.run_ekf_nll_grad)(disc, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=rows, record_index=record_index)
+        out = (E.run_ekf_nll_fisher if fisher else E.run_ekf_nll_grad)(disc, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=rows, record_index=record_index,
+                                                                       missing=missing)
     return tuple(o.cpu().numpy() for o in out)
 
 
-def value_and_grad(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf', sgps=None):
+def value_and_grad(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf', sgps=None, missing=None):
     """Objective and its EXACT gradient (forward tangents through the scan) at every row of thetas (G, P), in ONE launch: the EKF's
     (method='ekf', cgp_ekf_nll_grad: G P lanes) or the sigma-point filter's (method='sgp_filter' with a d = 4 SigmaPoints ``sgps``,
-    cgp_sgp_nll_grad: G wavefronts).  ys (T,) or (R, T) shared out evenly over the rows as in batched_nll.  -> (nll (G,), grad (G, P))."""
-    return _tangent_launch(False, build, thetas, ys, Xi, dt, record_index, method, sgps)
+    cgp_sgp_nll_grad: G wavefronts).  ys (T,) or (R, T) shared out evenly over the rows as in batched_nll.  -> (nll (G,), grad (G, P)).
+    ``missing='skip'``: NaN samples of the records are gaps, as in batched_nll -- the likelihood of the observed samples alone and its
+    exact gradient; a record of NaN only gives 0 and a zero gradient."""
+    return _tangent_launch(False, build, thetas, ys, Xi, dt, record_index, method, sgps, missing)
 
 
-def value_grad_fisher(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf', sgps=None):
+def value_grad_fisher(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf', sgps=None, missing=None):
     """value_and_grad's results and, from the same launch, the Fisher information of the filter's Gaussian innovations model
     F[i][j] = sum_t (d nu_i d nu_j / S + d S_i d S_j / (2 S^2)) (cgp_ekf_nll_fisher, cgp_sgp_nll_fisher): the Gauss-Newton part of the NLL's
     Hessian, taken along tangent_directions -- the information in the UNCONSTRAINED theta.  Same eligibility and record addressing as
-    value_and_grad.  -> (nll (G,), grad (G, P), fisher (G, P, P)); fisher is exactly symmetric."""
-    return _tangent_launch(True, build, thetas, ys, Xi, dt, record_index, method, sgps)
+    value_and_grad.  -> (nll (G,), grad (G, P), fisher (G, P, P)); fisher is exactly symmetric.  ``missing='skip'``: the sum runs over the
+    observed steps only -- the information of the observed samples; a record of NaN only gives F = 0."""
+    return _tangent_launch(True, build, thetas, ys, Xi, dt, record_index, method, sgps, missing)
 
 
 SINGULAR_RCOND = 1e-12       # covariance_from_fisher: below this 1 / cond of the scaled information, the estimate has a flat direction
@@ -278,12 +284,13 @@ def covariance_from_fisher(F, theta):
     return dg * np.sqrt(np.diag(cov)), cov, cond, False
 
 
-def standard_errors(build, theta_hat, ys, Xi, dt, *, method='ekf', sgps=None):
+def standard_errors(build, theta_hat, ys, Xi, dt, *, method='ekf', sgps=None, missing=None):
     """Standard errors of the fitted positive parameters g(theta_hat) of ONE record ys (T,) from the Fisher information at theta_hat (one
     launch of value_grad_fisher; covariance_from_fisher).  -> (se_params (P,), cov_theta (P, P), info) with info['fisher'], ['cond'],
-    ['singular'], ['nll'] and ['grad']; a singular information gives inf everywhere and info['singular'] = True."""
+    ['singular'], ['nll'] and ['grad']; a singular information gives inf everywhere and info['singular'] = True.  ``missing='skip'``: NaN
+    samples are gaps and the information is the observed samples'; a record of NaN only has none (F = 0: singular)."""
     theta_hat = np.asarray(theta_hat, dtype=np.float64).reshape(-1)
-    nll, grad, F = value_grad_fisher(build, theta_hat[None, :], ys, Xi, dt, method=method, sgps=sgps)
+    nll, grad, F = value_grad_fisher(build, theta_hat[None, :], ys, Xi, dt, method=method, sgps=sgps, missing=missing)
     se, cov, cond, singular = covariance_from_fisher(F[0], theta_hat)
     return se, cov, dict(fisher=F[0], cond=cond, singular=singular, nll=float(nll[0]), grad=grad[0])
 
@@ -304,7 +311,7 @@ def scoring_step(F, grad, mu):
     return step
 
 
-def fit_scoring(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=100, gtol=1e-5, mu0=1e-3, nu=4.0, mu_max=1e12):
+def fit_scoring(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=100, gtol=1e-5, mu0=1e-3, nu=4.0, mu_max=1e12, *, missing=None):
     """Maximum likelihood for R records in lock step by damped Fisher scoring: every iteration is ONE launch of value_grad_fisher for all
     the records still active, each with its own iterate and damping.  A tangent launch costs the same whatever the batch
     (EXACT_FROM_RECORDS), so the launches are the cost; scoring uses the curvature the kernel already carries instead of building it up
@@ -316,10 +323,14 @@ def fit_scoring(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=100,
 
     yss (R, T); init_params (P,) or (R, P) positive model parameters -> (opt_params (R, P), info): fit_many's fun, grad, nit, launches,
     converged (by the gradient rule), and fisher (R, P, P) at the final iterates, mu (R,), and per launch history (the (R,) NLLs of the
-    iterates after it) and iterates (those iterates, (R, P), in the unconstrained theta = g_inv(params))."""
+    iterates after it) and iterates (those iterates, (R, P), in the unconstrained theta = g_inv(params)).
+
+    ``missing='skip'``: NaN samples of the records are gaps -- value, exact gradient and information of the observed samples, from the same
+    launches (the L-BFGS front ends fit, fit_many and make_objective still take the difference gradient on such records)."""
     from chirpgp_amd import _engine as E
     if not has_exact_gradient(method, build, Xi, sgps):
         raise _exact_unsupported()
+    E._missing_flag(missing)                           # a misspelt value fails here, before anything is copied
     yss = E.dev(yss)
     if yss.ndim == 1:
         yss = yss[None, :]
@@ -328,7 +339,7 @@ def fit_scoring(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=100,
     P = x.shape[1]
 
     def evaluate(xt, idx):
-        ft, gt, Ft = value_grad_fisher(build, xt, yss, Xi, dt, record_index=idx, method=method, sgps=sgps)
+        ft, gt, Ft = value_grad_fisher(build, xt, yss, Xi, dt, record_index=idx, method=method, sgps=sgps, missing=missing)
         ok = np.isfinite(ft) & np.isfinite(gt).all(axis=1) & np.isfinite(Ft).all(axis=(1, 2))
         return np.where(ok, ft, np.inf), gt, Ft, ok
 

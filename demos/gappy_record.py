@@ -1,12 +1,15 @@
 """A record with gaps: MLE (central differences) -> EKF -> EKS -> E[g(V)] on a toy chirp with three gaps and a tail to forecast.
 
-    python demos/gappy_record.py [--T 3141] [--seed 555] [--maxiter 200] [--out results.npz]
+    python demos/gappy_record.py [--T 3141] [--seed 555] [--maxiter 200] [--stderr] [--out results.npz]
 
 Missing samples are NaN in the record and every filter call says missing='skip': at such a step the prediction is the filtering result
 and the likelihood gains nothing, so the objective is the likelihood of the observed samples alone.  The smoother needs no keyword -- it
 reads the filtering rows and predicts again -- and fills the gaps from both sides; the tail it can only forecast.  The RMSE of the
-frequency estimate is printed over the observed steps and over the gaps apart.  (The exact-gradient kernels know no gaps: with
-missing='skip' the objective's gradient is always differenced.)"""
+frequency estimate is printed over the observed steps and over the gaps apart.
+
+--stderr: the estimates with their standard errors, from the Fisher information of the observed samples' innovations at the optimum (one
+more launch: cgp_ekf_nll_fisher with CGP_SKIP_MISSING, mle.standard_errors(..., missing='skip')); "flat" where the information is singular.
+(The tangent kernels take gaps, but mle.fit still differences the objective's gradient on a record with gaps.)"""
 import argparse
 import math
 import os
@@ -28,6 +31,7 @@ def main():
     ap.add_argument('--T', type=int, default=3141)
     ap.add_argument('--seed', type=int, default=555)
     ap.add_argument('--maxiter', type=int, default=200)
+    ap.add_argument('--stderr', action='store_true', help='standard errors of the estimates from the observed samples\' Fisher information')
     ap.add_argument('--out', default=None, help='write the estimate, the gap mask and the two RMSE figures to this .npz file')
     args = ap.parse_args()
 
@@ -52,9 +56,17 @@ def main():
     print(f'{int(missing.sum())} of {T} samples missing   params {np.array2string(opt_params, precision=3)}  nll {res.fun:.2f}  iters {res.nit} '
           f'({res.nfev} launches)  [{time.time() - t0:.2f} s]')
     print(f'RMSE of the frequency estimate: {rmse_obs:.3f} Hz over the observed steps, {rmse_gap:.3f} Hz over the gaps and the forecast tail')
+    extra = {}
+    if args.stderr:
+        se, _, info = mle.standard_errors(build_chirp_model, res.x, ys, Xi, dt, missing='skip')
+        print(f'standard errors from the information of the {T - int(missing.sum())} observed samples '
+              f'(cond of the scaled information {info["cond"]:.3g}):')
+        for name, p, s in zip(('lam', 'b', 'delta', 'ell', 'sigma', 'm0_v'), opt_params, se):
+            print(f'  {name:6s} {p:10.4g} +- {"flat" if info["singular"] or not np.isfinite(s) else f"{s:.3g}"}')
+        extra = dict(standard_errors=se, fisher=info['fisher'])      # (stored with --stderr only; inf where flat)
     if args.out:
         np.savez(args.out, estimate=est, smoothed_mean=mss, filtered_nll=nll, missing=missing.astype(np.float64), params=opt_params,
-                 rmse_observed=rmse_obs, rmse_gaps=rmse_gap)
+                 rmse_observed=rmse_obs, rmse_gaps=rmse_gap, **extra)
 
 
 if __name__ == '__main__':

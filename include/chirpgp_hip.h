@@ -166,7 +166,8 @@ typedef struct cgp_init {
                                         composed maps are exact in exact arithmetic but only as accurate as products of the caller's gains
                                         are well conditioned (1e-11 of the one-wave walk for the chirp models, 1e-7 seen for a random F)   */
 #define CGP_NO_TIME_SPLIT     0x1000u /* ... never                                                                                      */
-#define CGP_SKIP_MISSING      0x2000u /* filters (cgp_filter, cgp_filter_custom): a NaN measurement is a missing sample, not poison -- see cgp_filter */
+#define CGP_SKIP_MISSING      0x2000u /* filters (cgp_filter, cgp_filter_custom) and the four gradient / Fisher entry points: a NaN measurement is
+                                         a missing sample, not poison -- see cgp_filter, cgp_ekf_nll_grad */
 #define CGP_SIM_FIXED_X0      0x20u /* cgp_simulate: x_0 = m0 exactly, P0 unused (simulate_sde_init, simulate_lgssm)       */
 
 /* ---- error codes ---------------------------------------------------------------------------------------- */
@@ -208,7 +209,8 @@ const char* cgp_last_error(const cgp_ctx* ctx);
  * matrix-core kernels of ekf, sgp_filter, cd_ekf and cd_sgp_filter on the d = 4 chirp / La Scala models; every other specialised kernel
  * (kf at d = 4, d = 6 / 8, ekf_for_kpt's tile layout, the DPP variants, the four-trials-per-wavefront EKF, the large-batch lane kernels)
  * hands a flagged call to the generic kernel in the launch shape the call has.  cgp_filter_time_split refuses the flag (CGP_E_UNSUPPORTED): a burn-in that starts inside a gap has no
- * junction to compare.  The gradient and Fisher entries take no flags; a NaN propagates there. */
+ * junction to compare.  The gradient and Fisher entries (cgp_ekf_nll_grad, cgp_sgp_nll_grad, cgp_ekf_nll_fisher, cgp_sgp_nll_fisher) take
+ * this flag and no other: a gap then adds exactly nothing to nll, grad and fisher -- see there. */
 int cgp_filter(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init,
                double dt, const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index,
                int64_t B, int64_t T, double* mfs, double* Pfs, double* nll, uint32_t flags, void* stream);
@@ -242,7 +244,13 @@ int cgp_filter_time_split(cgp_ctx* ctx, int method, const cgp_model* model, cons
  * computed by the caller from its model builder (chirpgp_amd/mle.py does it by complex step); the derivative through the state-
  * dependent part of the model (softplus frequency, rotation, Jacobian) is taken by the kernel.  dirs: [B][n_dir][CGP_DIR_DOUBLES]
  * (device), nll: [B], grad: [B][n_dir] = d nll[b] / d direction.  Records are addressed as in cgp_filter.  One lane per
- * (trial, direction). */
+ * (trial, direction).
+ * flags: 0 or CGP_SKIP_MISSING, here and in the three entry points below; any other bit is CGP_E_ARG, with the bit's name in the message.
+ * With CGP_SKIP_MISSING a step whose measurement is NaN (y != y alone decides, as in cgp_filter) is a gap: mf = mp and Pf = Pp, along
+ * every direction d mf = d mp and d Pf = d Pp, and the increments of nll, of grad and of every Fisher entry are exactly zero -- the
+ * likelihood of the observed samples, its exact gradient, and the information of the observed samples' innovations model.  A record of
+ * NaN only gives nll = +0.0, grad = 0, fisher = 0.  +-inf is a measurement; a diverged filter (NaN state, finite y) still writes NaN;
+ * without the flag a NaN measurement propagates as before. */
 #define CGP_DIR_DOUBLES 24
 int cgp_ekf_nll_grad(cgp_ctx* ctx, const cgp_model* model, const cgp_init* init, double dt,
                      const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
@@ -254,7 +262,7 @@ int cgp_ekf_nll_grad(cgp_ctx* ctx, const cgp_model* model, const cgp_init* init,
  * chirp / La Scala LCD), directions, records and outputs as cgp_ekf_nll_grad, with ANY d = 4 sigma-point set: the kernel takes the
  * literal sum over the points (group_start and the CGP_SIGMA_* flags are not needed and not used).  One wavefront per trial; B < 2^31.
  * CGP_E_UNSUPPORTED for another model or a set of another dimension; a Cholesky that breaks down writes NaN to nll and grad, as
- * sgp_filter writes NaN; T = 0 writes nll = 0 and grad = 0. */
+ * sgp_filter writes NaN; T = 0 writes nll = 0 and grad = 0.  flags: 0 or CGP_SKIP_MISSING, as cgp_ekf_nll_grad. */
 int cgp_sgp_nll_grad(cgp_ctx* ctx, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init, double dt,
                      const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
                      const double* dirs, int32_t n_dir, double* nll, double* grad, uint32_t flags, void* stream);
@@ -267,7 +275,9 @@ int cgp_sgp_nll_grad(cgp_ctx* ctx, const cgp_model* model, const cgp_sigma* sigm
  * row-major, device; exactly symmetric (both triangles are written, by the same operations).  nll and grad as the gradient entry points
  * write them; every other argument as theirs.  The matrix couples all the directions of a launch, so they are not sliced:
  * n_dir <= CGP_FISHER_MAX_DIR, CGP_E_UNSUPPORTED beyond.  The EKF form runs 64 / n_dir whole trials per wavefront.  T = 0 writes
- * nll = 0, grad = 0, fisher = 0; a diverged filter (a non-positive S, a Cholesky that breaks down) writes NaN to all three. */
+ * nll = 0, grad = 0, fisher = 0; a diverged filter (a non-positive S, a Cholesky that breaks down) writes NaN to all three.
+ * flags: 0 or CGP_SKIP_MISSING, as cgp_ekf_nll_grad -- the sum then runs over the observed steps only (the EKF form gates every lane on
+ * its own trial's measurement). */
 #define CGP_FISHER_MAX_DIR 16
 int cgp_ekf_nll_fisher(cgp_ctx* ctx, const cgp_model* model, const cgp_init* init, double dt,
                        const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
