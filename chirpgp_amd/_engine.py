@@ -54,11 +54,15 @@ class CgpSmoothOut(C.Structure):
                 ('expect', _vp), ('xi', _vp), ('w', _vp), ('order', C.c_int32)]
 
 
+class CgpSampleOut(C.Structure):
+    _fields_ = [('paths', _vp), ('comp_paths', _vp), ('comp', C.c_int32), ('func', C.c_int32)]
+
+
 EXPORTS = ('cgp_version', 'cgp_create', 'cgp_destroy', 'cgp_last_error', 'cgp_filter', 'cgp_smoother',
            'cgp_gaussian_expectation', 'cgp_debug_math', 'cgp_simulate', 'cgp_add_noise', 'cgp_debug_philox',
            'cgp_debug_set', 'cgp_debug_counters', 'cgp_gaussian_expectation_fn', 'cgp_filter_time_split', 'cgp_squared_error_sums',
            'cgp_reserve_workspace', 'cgp_release_workspace', 'cgp_source_hash', 'cgp_smoother_select', 'cgp_ekf_nll_grad', 'cgp_sgp_nll_grad', 'cgp_ekf_nll_fisher', 'cgp_sgp_nll_fisher', 'cgp_model_from_source', 'cgp_custom_model_destroy',
-           'cgp_filter_custom', 'cgp_smoother_custom', 'cgp_smoother_time_split')
+           'cgp_filter_custom', 'cgp_smoother_custom', 'cgp_smoother_time_split', 'cgp_smoother_sample')
 
 _lib = None
 _lock = threading.Lock()
@@ -100,6 +104,9 @@ def load_library():
         lib.cgp_smoother_select.restype = C.c_int
         lib.cgp_smoother_select.argtypes = [_vp, C.c_int, C.POINTER(CgpModel), C.POINTER(CgpSigma), C.c_double,
                                             _vp, _vp, C.c_int64, C.c_int64, C.POINTER(CgpSmoothOut), C.c_uint32, _vp]
+        lib.cgp_smoother_sample.restype = C.c_int
+        lib.cgp_smoother_sample.argtypes = [_vp, C.c_int, C.POINTER(CgpModel), C.POINTER(CgpSigma), C.c_double, _vp, _vp, C.c_int64, C.c_int64, C.c_int64,
+                                            C.c_uint64, C.c_int64, C.c_int64, _vp, C.POINTER(CgpSampleOut), C.c_uint32, _vp]
         lib.cgp_ekf_nll_grad.restype = C.c_int
         lib.cgp_ekf_nll_grad.argtypes = [_vp, C.POINTER(CgpModel), C.POINTER(CgpInit), C.c_double, _vp, C.c_int64, C.c_int64, _vp,
                                          C.c_int64, C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_uint32, _vp]
@@ -773,6 +780,71 @@ def run_smoother(method, spec, sgps, gamma, dt, mfs, Pfs, flags=0, want=(True, T
         _check(ctx, rc, 'cgp_smoother_select')
         selection = SmootherSelection({k: _out(v, like_numpy, squeeze) for k, v in sel.items()})
         return (None if mss is None else _out(mss, like_numpy, squeeze), None if Pss is None else _out(Pss, like_numpy, squeeze), selection)
+
+
+def run_smoother_sample(method, spec, sgps, dt, mfs, Pfs, n_samples, seed=0, trial0=0, sample0=0, normals=None, want_paths=True, select=None,
+                        flags=0):
+    """cgp_smoother_sample with NumPy / torch marshalling: ``n_samples`` joint posterior sample paths per trial by backward simulation on the
+    discrete smoother's own affine maps (include/chirpgp_hip.h).  mfs / Pfs are (T, d) / (T, d, d) or carry a leading batch axis, and are
+    taken as run_smoother takes them (float64, contiguous, on the GPU -- converted where they are not).
+
+    ``normals`` None: the engine's Philox stream, addressed by (seed, trial0 + b, sample0 + s, step) alone -- a path does not depend on the
+    batch, on n_samples or on how trials and samples are split over calls.  Otherwise the caller's standard normals, (B, S, T, d) ((S, T, d)
+    without the batch axis).  ``select = dict(comp=k, func='softplus' | 'exp' | 'identity' | 'square')`` asks for func(x[comp]) of every sample
+    and step.  Returns ``(paths | None, comp_paths | None)``: (B, S, T, d) and (B, S, T), without B for unbatched rows."""
+    torch = _torch()
+    like_numpy = not _is_torch(mfs)
+    m, P = dev(mfs), dev(Pfs)
+    squeeze = m.ndim == 2
+    if squeeze:
+        m, P = m[None], P[None]
+    if m.ndim != 3 or P.ndim != 4 or P.shape[:2] != m.shape[:2] or P.shape[2] != m.shape[2] or P.shape[3] != m.shape[2]:
+        raise ValueError(f'mfs / Pfs must be (B, T, d) / (B, T, d, d); got {tuple(m.shape)} / {tuple(P.shape)}')
+    B, T, d = (int(v) for v in m.shape)
+    S = int(n_samples)
+    if S < 0:
+        raise ValueError('n_samples must be >= 0')
+    if d != int(spec.d):
+        raise ValueError(f'model dimension {spec.d} != data dimension {d}')
+    _check_dimension(spec)
+    if not want_paths and select is None:
+        raise ValueError('nothing to write: want_paths=False needs select=dict(comp=..., func=...)')
+    o = CgpSampleOut()
+    if select is not None:
+        unknown = set(select) - {'comp', 'func'}
+        if unknown:
+            raise ValueError(f'select: unknown keys {sorted(unknown)}')
+        comp = int(select['comp'])
+        if comp < 0:
+            comp += d
+        if not 0 <= comp < d:
+            raise ValueError(f'select: component {select["comp"]} outside the state dimension {d}')
+        func = str(select.get('func', 'identity'))
+        if func not in _FUNCS:
+            raise ValueError(f'select: func must be one of {sorted(_FUNCS)} (an enumerated function: a Python callable cannot run in a kernel)')
+        o.comp, o.func = comp, _FUNCS[func]
+    with torch.cuda.device(m.device):
+        ctx = context(m.device.index)
+        keep = [m, P]
+        z = None
+        if normals is not None:
+            z = dev(normals, m.device)
+            if squeeze and z.ndim == 3:
+                z = z[None]
+            if tuple(z.shape) != (B, S, T, d):
+                raise ValueError(f'normals must be (B, S, T, d) = {(B, S, T, d)}; got {tuple(z.shape)}')
+            keep.append(z)
+        model = _model_struct(spec, None, B, keep)
+        sig = _sigma_struct(sgps, d, keep, _nonlinear_coord(spec))
+        opts = dict(dtype=torch.float64, device=m.device)
+        paths = torch.empty((B, S, T, d), **opts) if want_paths else None
+        comp_paths = torch.empty((B, S, T), **opts) if select is not None else None
+        o.paths, o.comp_paths = _ptr(paths), _ptr(comp_paths)
+        rc = _timed('sample', lambda: load_library().cgp_smoother_sample(ctx, int(method), C.byref(model), C.byref(sig) if sig is not None else None, float(dt),
+                                                                         _ptr(m), _ptr(P), B, T, S, int(seed), int(trial0), int(sample0), _ptr(z),
+                                                                         C.byref(o), int(flags), _stream()))
+        _check(ctx, rc, 'cgp_smoother_sample')
+    return (None if paths is None else _out(paths, like_numpy, squeeze), None if comp_paths is None else _out(comp_paths, like_numpy, squeeze))
 
 
 FN_SOFTPLUS, FN_EXP, FN_IDENTITY, FN_SQUARE = 0, 1, 2, 3

@@ -5,6 +5,7 @@
 #include <string>
 #include "cgp_kernels.hpp"
 #include "cgp_ctx.hpp"
+#include "cgp_sample4.hpp"
 
 namespace cgp {
 
@@ -610,6 +611,83 @@ int cgp_smoother_select(cgp_ctx* ctx, int method, const cgp_model* model, const 
                         const double* mfs, const double* Pfs, int64_t B, int64_t T, const cgp_smooth_out* out,
                         uint32_t flags, void* stream) {
     return smoother_impl(ctx, method, model, sigma, dt, mfs, Pfs, B, T, out, flags, stream);
+}
+
+// The header's name of a flag bit that cgp_smoother_sample refuses (it takes none)
+static const char* sample_flag_name(uint32_t bit) {
+    switch (bit) {
+    case CGP_NLL_FINAL_ONLY: return "CGP_NLL_FINAL_ONLY";
+    case CGP_WAVE_PER_TRIAL: return "CGP_WAVE_PER_TRIAL";
+    case CGP_THREAD_PER_TRIAL: return "CGP_THREAD_PER_TRIAL";
+    case CGP_SEQUENTIAL_SCAN: return "CGP_SEQUENTIAL_SCAN";
+    case CGP_GENERIC_KERNEL: return "CGP_GENERIC_KERNEL";
+    case CGP_SIM_FIXED_X0: return "CGP_SIM_FIXED_X0";
+    case CGP_LITERAL_SIGMA_SUM: return "CGP_LITERAL_SIGMA_SUM";
+    case CGP_DPP_KERNEL: return "CGP_DPP_KERNEL";
+    case CGP_FOUR_TRIALS_PER_WAVE: return "CGP_FOUR_TRIALS_PER_WAVE";
+    case CGP_ONE_TRIAL_PER_WAVE: return "CGP_ONE_TRIAL_PER_WAVE";
+    case CGP_TIME_SPLIT: return "CGP_TIME_SPLIT";
+    case CGP_NO_TIME_SPLIT: return "CGP_NO_TIME_SPLIT";
+    case CGP_SKIP_MISSING: return "CGP_SKIP_MISSING";
+    default: return "no flag of chirpgp_hip.h";
+    }
+}
+
+int cgp_smoother_sample(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, double dt,
+                        const double* mfs, const double* Pfs, int64_t B, int64_t T, int64_t S,
+                        uint64_t seed, int64_t trial0, int64_t sample0, const double* normals,
+                        const cgp_sample_out* out, uint32_t flags, void* stream) {
+    if (!ctx) return CGP_E_ARG;
+    if (B < 0 || T < 0 || S < 0) return fail(ctx, CGP_E_ARG, "negative B, T or S");
+    if (flags) {
+        const uint32_t bit = flags & (~flags + 1u);                        // the lowest bit set
+        char hex[16];
+        snprintf(hex, sizeof hex, "0x%x", (unsigned)bit);
+        return fail(ctx, CGP_E_ARG, std::string("cgp_smoother_sample takes no flag: bit ") + hex + " (" + sample_flag_name(bit) + ") is set");
+    }
+    if (B == 0 || T == 0 || S == 0) return CGP_OK;                        // nothing to write
+    if (!out || (!out->paths && !out->comp_paths)) return fail(ctx, CGP_E_ARG, "cgp_sample_out.paths and comp_paths are both NULL: nothing to write");
+    if (method < CGP_S_EKS || method > CGP_S_CD_SGP) return fail(ctx, CGP_E_ARG, "unknown smoother method");
+    if (method == CGP_S_CD_EKS || method == CGP_S_CD_SGP)
+        return fail(ctx, CGP_E_UNSUPPORTED, "cgp_smoother_sample walks the discrete smoothers' affine maps (rts, eks, sgp_smoother): a continuous-discrete "
+                                            "smoother's backward ODE is not such a map");
+    const bool sig = method == CGP_S_SGP;
+    int rc = check_model(ctx, model, false, sig, sigma);
+    if (rc != CGP_OK) return rc;
+    const bool lcd = (model->model_id == CGP_M_HARMONIC_LCD && model->n_harm == 1) || model->model_id == CGP_M_LASCALA_LCD;
+    const bool built = model->d == 4 && (lcd || (model->model_id == CGP_M_LINEAR && method == CGP_S_EKS));
+    if (!built)
+        return fail(ctx, CGP_E_UNSUPPORTED, "cgp_smoother_sample is built for d = 4: rts on CGP_M_LINEAR, eks and sgp_smoother on CGP_M_HARMONIC_LCD with n_harm = 1 "
+                                            "and CGP_M_LASCALA_LCD");
+    if (sig && SigmaSet::stage_bytes(sigma->s, 4, 0, false) > (size_t)kSigLdsMaxBytes)
+        return fail(ctx, CGP_E_UNSUPPORTED, "the sigma-point set does not fit the LDS stage of cgp_smoother_sample");
+    if (out->comp_paths) {
+        if (out->comp < 0 || out->comp >= model->d) return fail(ctx, CGP_E_ARG, "cgp_sample_out.comp outside 0..d-1");
+        if (out->func < CGP_FN_SOFTPLUS || out->func > CGP_FN_SQUARE) return fail(ctx, CGP_E_ARG, "cgp_sample_out.func is no CGP_FN_*");
+    }
+    const uint64_t two32 = (uint64_t)1 << 32;
+    if (B > 0x7FFFFFFF) return fail(ctx, CGP_E_ARG, "B must be < 2^31 (one workgroup column per trial)");
+    if (!normals) {                                                        // the counter's words: (trial, sample, index)
+        if (trial0 < 0 || sample0 < 0) return fail(ctx, CGP_E_ARG, "negative trial0 or sample0");
+        if ((uint64_t)trial0 + (uint64_t)B > two32) return fail(ctx, CGP_E_ARG, "trial0 + B must be <= 2^32 (the trial is one word of the Philox counter)");
+        if ((uint64_t)sample0 + (uint64_t)S > two32) return fail(ctx, CGP_E_ARG, "sample0 + S must be <= 2^32 (the sample is one word of the Philox counter)");
+        if ((uint64_t)T > two32 / 2) return fail(ctx, CGP_E_ARG, "T * ceil(d / 2) must be <= 2^32 (the pair index is one word of the Philox counter)");
+    }
+    if (!mfs || !Pfs) return fail(ctx, CGP_E_ARG, "mfs / Pfs must be set");
+    DeviceScope on_device(ctx->device);
+    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
+    std::lock_guard<std::recursive_mutex> launches(ctx->launch_mutex);
+    SampleIO io;
+    io.mfs = mfs; io.Pfs = Pfs; io.normals = normals; io.B = B; io.T = T; io.S = S;
+    io.seed = seed; io.trial0 = (uint64_t)trial0; io.sample0 = (uint64_t)sample0;
+    io.paths = out->paths; io.comp_paths = out->comp_paths; io.comp = out->comp_paths ? out->comp : 0; io.func = out->func;
+    // the literal per-point sums: the kernel takes no groups, so a grouped set is staged without its group table
+    ModelArgs ma = model_args(model, sig ? sigma : nullptr, dt, CGP_LITERAL_SIGMA_SUM);
+    ma.sg.group_start = nullptr; ma.sg.n_groups = 0;
+    rc = dispatch_sample4(method, model->model_id, io, ma, (hipStream_t)stream);
+    if (rc == CGP_E_UNSUPPORTED) return fail(ctx, rc, "this (method, model, dimension) combination is not compiled in");
+    if (rc == CGP_E_HIP) return fail(ctx, rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return rc;
 }
 
 int cgp_gaussian_expectation(cgp_ctx* ctx, const double* ms, const double* sd, int64_t n, int64_t in_stride,

@@ -26,6 +26,7 @@ constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
 constexpr uint32_t kStreamInit = 0;      // x0 = m0 + chol(P0) z          index = pair number
 constexpr uint32_t kStreamState = 1;     // process noise of step k       index = k * pairs_per_step + pair
 constexpr uint32_t kStreamMeas = 2;      // measurement noise             index = k / 2 (the pair serves steps 2j, 2j + 1)
+constexpr uint32_t kStreamPosterior = 3; // posterior sample paths (cgp_sample4.hpp): z_t of (trial | sample << 32)   index = t * ceil(d / 2) + pair
 
 struct U32x4 { uint32_t v[4]; };
 

@@ -9,7 +9,9 @@ filters_smoothers.py:26-36).  Differences a caller sees:
   ``jax.vmap(..., in_axes=0)`` (tetralith/jobs/crlb_ekf.py:68-72); so may ``m0, P0, H, Xi`` and the model parameters;
 * NumPy in -> NumPy out, torch CUDA tensors in -> torch CUDA tensors out (results stay in HBM);
 * every filter takes ``missing='skip'``: a NaN measurement is then a missing sample (the prediction is the step's result, its NLL
-  increment exactly 0) instead of the reference's poison -- records with dropped samples, gated segments or a tail to forecast.
+  increment exactly 0) instead of the reference's poison -- records with dropped samples, gated segments or a tail to forecast;
+* ``rts_sample``, ``eks_sample`` and ``sgp_smoother_sample`` (no counterpart in the reference) draw joint posterior sample paths from the
+  discrete smoothers by backward simulation.
 """
 import numpy as np
 
@@ -141,6 +143,41 @@ def cd_sgp_smoother(a, b, sgps, mfs, Pfs, dt, **kw):
     if isinstance(spec, M.CustomDrift):
         return E.run_smoother_custom(spec, _gamma_from_matrix(b), dt, mfs, Pfs, sgps=_sgps(sgps, spec.d), **_custom_kw(kw, ('flags',)))
     return E.run_smoother(E.S_CD_SGP, spec, _sgps(sgps, spec.d), _gamma_from_matrix(b), dt, mfs, Pfs, **kw)
+
+
+_SAMPLE_MODELS = ('posterior sample paths are built for d = 4: rts_sample on a linear model, eks_sample and sgp_smoother_sample on disc_chirp_lcd '
+                  '(disc_harmonic_chirp_lcd with one harmonic) and disc_lascala_lcd; custom (run-time compiled) models and the continuous-discrete '
+                  'smoothers (cd_eks, cd_sgp_smoother: their backward ODE is not an affine map) are not supported')
+
+
+def _sample_spec(cond_m_cov, dt, linear):
+    if isinstance(cond_m_cov, (M.CustomDiscrete, M.CustomDrift, M.DriftModel, M.Dispersion)):
+        raise ValueError(_SAMPLE_MODELS)
+    spec = _discrete(cond_m_cov, dt)
+    lcd = spec.model_id == M.M_LASCALA_LCD or (spec.model_id == M.M_HARMONIC_LCD and int(spec.n_harm) == 1)
+    if int(spec.d) != 4 or not (lcd or (linear and spec.model_id == M.M_LINEAR)):
+        raise ValueError(_SAMPLE_MODELS)
+    return spec
+
+
+def rts_sample(F, Sigma, mfs, Pfs, n_samples, **kw):
+    """``n_samples`` joint posterior sample paths of the RTS smoother's Gaussian posterior by backward simulation:
+    x_{T-1} ~ N(mf, Pf), x_t | x_{t+1} ~ N(c_t + G_t x_{t+1}, C_t) with the smoother's own (G_t, c_t, C_t).
+    Keywords: seed=0, trial0=0, sample0=0, normals=None, want_paths=True, select=None (``dict(comp=2, func='softplus')``).
+    -> (paths (B, S, T, d) | None, comp_paths (B, S, T) | None), without B for unbatched rows."""
+    spec = _sample_spec(M.linear_cond_m_cov(_np(F), _np(Sigma)), None, True)
+    return E.run_smoother_sample(E.S_EKS, spec, None, 0., mfs, Pfs, n_samples, **kw)
+
+
+def eks_sample(cond_m_cov, mfs, Pfs, dt, n_samples, **kw):
+    """Sample paths of the posterior the extended Kalman smoother approximates; see rts_sample."""
+    return E.run_smoother_sample(E.S_EKS, _sample_spec(cond_m_cov, dt, True), None, dt, mfs, Pfs, n_samples, **kw)
+
+
+def sgp_smoother_sample(cond_m_cov, sgps, mfs, Pfs, dt, n_samples, **kw):
+    """Sample paths of the posterior the sigma-point smoother approximates (any d = 4 sigma-point set); see rts_sample."""
+    spec = _sample_spec(cond_m_cov, dt, False)
+    return E.run_smoother_sample(E.S_SGP, spec, _sgps(sgps, spec.d), dt, mfs, Pfs, n_samples, **kw)
 
 
 def _custom_kw(kw, allowed=('nll_final_only', 'want', 'flags', 'missing')):

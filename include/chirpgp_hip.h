@@ -18,6 +18,8 @@
  *   cgp_smoother (method = CGP_S_CD_SGP)                               cd_sgp_smoother filters_smoothers.py:585-632
  *   cgp_smoother_select                                                the smoothers above + the marginal step behind them in every driver
  *                                                                      (demos/ekfs_mle.py:69-77: mss[:, k], Pss[:, k, k], gaussian_expectation), fused
+ *   cgp_smoother_sample                                                (no counterpart: the reference reports marginals only) joint posterior sample paths
+ *                                                                      of rts / eks / sgp_smoother by backward simulation on the smoother's own affine maps
  *   cgp_ekf_nll_grad                                                   value_and_grad of ekf(...)[-1][-1] through the scan, demos/ekfs_mle.py:43-51
  *   cgp_sgp_nll_grad                                                   value_and_grad of sgp_filter(...)[-1][-1] through the scan, demos/ghfs_mle.py:53-56
  *   cgp_ekf_nll_fisher / cgp_sgp_nll_fisher                            (no counterpart: the reference's jobs report point estimates only)
@@ -384,6 +386,39 @@ typedef struct cgp_smooth_out {
 int cgp_smoother_select(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma,
                         double dt, const double* mfs, const double* Pfs, int64_t B, int64_t T,
                         const cgp_smooth_out* out, uint32_t flags, void* stream);
+
+/* Posterior sample paths of the discrete smoothers (rts, eks, sgp_smoother) by backward simulation (forward filtering, backward sampling).
+ * The smoother's backward recursion is an affine map per step, ms_t = G_t ms_{t+1} + c_t, Ps_t = G_t Ps_{t+1} G_t^T + C_t, with
+ * c_t = mf_t - G_t mp_t and C_t = Pf_t - G_t Pp_t G_t^T built from the filtering rows alone; the same (G_t, c_t, C_t) are the backward
+ * kernel of the Gauss-Markov posterior that the smoother approximates, x_t | x_{t+1} ~ N(c_t + G_t x_{t+1}, C_t).  A path is
+ *     x_{T-1} = mf_{T-1} + L(Pf_{T-1}) z_{T-1},        x_t = c_t + G_t x_{t+1} + L(C_t) z_t,   t = T-2 .. 0,
+ * z_t standard normal, L(A) the lower-triangular Cholesky factor of A under the PIVOT RULE (a definition, not a tolerance): in the
+ * factorisation of C_t, a pivot p_j <= 2^-40 Pf_t[j][j] makes column j of L zero (Pf_{T-1} is held against its own diagonal), so that
+ * component is deterministic given x_{t+1} -- the chirp block of the La Scala model has no process noise, its C_t has rank 2 in exact
+ * arithmetic -- and at most 2^-40 of the filtering variance is dropped.  A NaN pivot stays NaN: a broken filtering row gives NaN paths from
+ * there back, as the smoothers do, and is not an error.  Sample means, covariances and lag-one cross-covariances of the paths converge to
+ * mss, Pss and G_t Pss_{t+1}.
+ *   normals == NULL: z is drawn in the kernel from the Philox stream of csrc/cgp_rng.hpp: component j of z_t of sample s of trial b is member
+ *     j & 1 of normal_pair(seed, (trial0 + b) | (uint64_t)(sample0 + s) << 32, index = t * ceil(d / 2) + (j >> 1), stream 3).  A path does not
+ *     depend on B, S, the launch shape or how trials and samples are split over launches or ranks.  trial0 + B <= 2^32, sample0 + S <= 2^32
+ *     and T * ceil(d / 2) <= 2^32, or CGP_E_ARG.
+ *   normals != NULL: a DEVICE array [B][S][T][d] of the caller's z (antithetic or quasi-random draws; a deterministic path); seed, trial0
+ *     and sample0 are not read.
+ * Built for CGP_S_EKS on CGP_M_LINEAR at d = 4, CGP_M_HARMONIC_LCD with n_harm = 1 and CGP_M_LASCALA_LCD, and for CGP_S_SGP on the two LCD
+ * models with any d = 4 sigma-point set (the literal sum over the points).  Everything else -- the continuous-discrete smoothers, whose
+ * backward ODE is not this affine map, other dimensions, other models -- is CGP_E_UNSUPPORTED.  flags: 0; any bit is CGP_E_ARG with the
+ * bit's name.  Both outputs NULL is CGP_E_ARG; T = 0 or S = 0 (or B = 0) writes nothing; T = 1 is the last-row draw alone.  No workspace;
+ * capturable into a graph. */
+typedef struct cgp_sample_out {
+    double* paths;        /* [B][S][T][d] or NULL                                                                                            */
+    double* comp_paths;   /* [B][S][T]: func(x[comp]) of every sample and step, or NULL                                                      */
+    int32_t comp;         /* 0 <= comp < d                                                                                                   */
+    int32_t func;         /* CGP_FN_* applied pointwise (softplus: an instantaneous-frequency path; identity: the component)                 */
+} cgp_sample_out;
+int cgp_smoother_sample(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, double dt,
+                        const double* mfs, const double* Pfs, int64_t B, int64_t T, int64_t S,
+                        uint64_t seed, int64_t trial0, int64_t sample0, const double* normals,
+                        const cgp_sample_out* out, uint32_t flags, void* stream);
 
 /* E[softplus(V)] for n scalar Gaussian marginals N(ms[i], sd[i]^2) by 1-D Gauss-Hermite of the given order
  * (nodes xi[order], weights w[order] already in the reference's scaling): quadratures.py:234-274 with func = g. */
