@@ -102,6 +102,13 @@ __global__ void __launch_bounds__(256) smooth_select_kernel(const double* __rest
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         sel_write(sel, ghrule, i, mss[i * d + sel.comp], Pss[i * d * d + sel.comp * (d + 1)]);
 }
+// the selected outputs of a cgp_smooth_out as the kernels take them: in their SmootherIO, or as the argument of smooth_select_kernel
+static SmoothSel smooth_sel(const cgp_smooth_out& out) {
+    SmoothSel sel;
+    sel.comp = out.comp; sel.func = out.func; sel.order = out.order;
+    sel.mean = out.comp_mean; sel.var = out.comp_var; sel.expect = out.expect; sel.xi = out.xi; sel.w = out.w;
+    return sel;
+}
 
 // Scales of the debug ops that evaluate a form with its scales folded into the coefficients (ops 14 / 15): neither is a power of two, so a
 // coefficient that missed its scale shows.  The test divides them out again (tests/fastmath_points.py holds the same two numbers).
@@ -445,9 +452,7 @@ static int filter_impl(cgp_ctx* ctx, int method, const cgp_model* model, const c
             else if (hipMemsetAsync(junction_err, 0, sizeof(double) * (size_t)B, st) != hipSuccess) rc = CGP_E_HIP;
         }
     }
-    if (rc == CGP_E_UNSUPPORTED) return fail(ctx, rc, "this (method, model, dimension) combination is not compiled in");
-    if (rc == CGP_E_HIP) return fail(ctx, rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return rc;
+    return launch_result(ctx, rc);
 }
 
 int cgp_filter(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init,
@@ -500,65 +505,31 @@ static int smoother_impl(cgp_ctx* ctx, int method, const cgp_model* model, const
 
     SmootherIO io;
     io.mfs = mfs; io.Pfs = Pfs; io.B = B; io.T = T; io.mss = mss; io.Pss = Pss; io.flags = flags;
-    io.host_ctx = ctx;
-    io.lane_buffers = ctx->lane_buffers;
-    // Time-split form of the discrete wave-per-trial smoothers: when the batch leaves two thirds of the SIMDs idle (or on
-    // request).  cgp_debug_set(CGP_DBG_WALK_SEGMENTS) caps the number of segments of this context (tuning aid).
-    io.num_cus = ctx->num_cus;
-    {
-        const long env_segs = ctx->walk_segments;
-        const bool forced = (flags & CGP_TIME_SPLIT) != 0;
-        // Not by default for the LINEAR model (rts): its F is the caller's, and composing the affine maps of hundreds of steps
-        // (C = Pf - G Pp G^T, A <- G A) is only as accurate as those products are well conditioned -- 1e-11 of the whole-record
-        // walk for the chirp family's gains (d = 4 ... 8, every parameter set of the tests), but 1e-7 for a random F at d = 6,
-        // where partial products of the gains grow in directions the true carry never excites.  The split is exact in exact
-        // arithmetic either way; for a linear model it is the caller's choice (CGP_TIME_SPLIT).
-        const bool own_model = model->model_id != CGP_M_LINEAR;
-        if ((flags & CGP_NO_TIME_SPLIT) || (!forced && (!own_model || 3 * B > (int64_t)ctx->num_cus * 4))) io.segs = 1;      // measured: x3 at B = 125, x1.6 at 250, x0.9 at 500
-        else io.segs = env_segs > 1 ? (int)env_segs : (env_segs == 1 ? 1 : 0);
-        io.min_tiles = forced ? 1 : 4;
-    }
     const ModelArgs ma = model_args(model, sigma, dt, flags);
-    // which kernel takes the launch -- decided before anything is enqueued, because only some of them write the selected outputs themselves
-    const SmootherDecision decided = route_smoother({method, model, sigma, &io, &ma, flags, ctx->num_cus});
-    const SmootherRoute route = decided.route;
-    const bool wave = decided.wave;
+    // the whole plan -- kernel, launch shape, segments, how the selected outputs get written -- decided before anything is enqueued
+    SmootherQuery query{method, model, sigma, &io, &ma, flags, ctx->num_cus};
+    query.walk_cap = ctx->walk_segments;
+    query.segments = segments; query.burn_in = burn_in;
+    query.want_sel = want_sel; query.null_rows = !mss || !Pss;
+    const SmootherDecision plan = route_smoother(query);
+    if (plan.rc != CGP_OK) return fail(ctx, plan.rc, plan.message);
+    const bool wave = plan.wave;
     hipStream_t st = (hipStream_t)stream;
-    const bool sel_native = writes_selection(route);
-    if (want_sel) {
-        if (sel_native) {
-            io.sel.comp = out->comp; io.sel.func = out->func; io.sel.order = out->order;
-            io.sel.mean = out->comp_mean; io.sel.var = out->comp_var; io.sel.expect = out->expect;
-            io.sel.xi = out->xi; io.sel.w = out->w;
-        } else if (!mss || !Pss)
-            return fail(ctx, CGP_E_UNSUPPORTED, "this (method, model, launch shape) writes selected outputs from its full rows only: pass mss and Pss as well");
+    const SmootherLaunch host{ctx, ctx->num_cus, plan.split, ctx->lane_buffers};
+    if (plan.select == SmootherSelect::kKernel) io.sel = smooth_sel(*out);
+    if (plan.bsegs > 1) {
+        // time-split with burn-in (cgp_smoother_time_split): one wavefront per (trial, segment), their states at the junctions for the fix-up pass
+        io.bsegs = plan.bsegs; io.chunks_per_bseg = plan.chunks_per_bseg; io.burn_chunks = plan.burn_chunks;
+        io.junction = (double*)ctx_workspace(ctx, st, sizeof(double) * SmootherIO::kJunctionDoubles * (size_t)B * (size_t)plan.bsegs);
+        if (!io.junction) return fail(ctx, CGP_E_HIP, "no workspace for the junction states (allocation failed, or the buffer would grow inside a graph capture: cgp_reserve_workspace first)");
     }
-    // ---- time-split with burn-in (cgp_smoother_time_split): the continuous-discrete sigma-point smoother on the d = 4 matrix-core kernel
-    if (segments > 1) {
-        if (burn_in < 0) return fail(ctx, CGP_E_ARG, "burn_in must be >= 0");
-        if (!junction_err) return fail(ctx, CGP_E_ARG, "junction_err must be set: a time-split smoother is only as good as its junctions");
-        if (want_sel) return fail(ctx, CGP_E_UNSUPPORTED, "cgp_smoother_time_split writes full rows only");
-        if (!knows_segments(route))
-            return fail(ctx, CGP_E_UNSUPPORTED, "time-split smoothers with burn-in are built for cd_eks and cd_sgp_smoother on the d = 4 chirp / La Scala SDE (matrix-core "
-                                                "kernels; standard sigma set); the discrete smoothers split exactly (CGP_TIME_SPLIT)");
-        const int64_t chunks = (T - 1 + 63) / 64;
-        if (chunks >= 2) {
-            const int64_t cps = (chunks + segments - 1) / segments;
-            const int64_t segs = (chunks + cps - 1) / cps;
-            if (segs > 1) {
-                io.bsegs = (int)segs; io.chunks_per_bseg = (int)cps; io.burn_chunks = (int)((burn_in + 63) / 64);
-                io.junction = (double*)ctx_workspace(ctx, st, sizeof(double) * SmootherIO::kJunctionDoubles * (size_t)B * (size_t)segs);
-                if (!io.junction) return fail(ctx, CGP_E_HIP, "no workspace for the junction states (allocation failed, or the buffer would grow inside a graph capture: cgp_reserve_workspace first)");
-            }
-        }
-    }
-    switch (route) {
-    case SmootherRoute::kCoop8Linear: rc = dispatch_smoother_coop8_linear(method, model->d, io, ma, st); break;
-    case SmootherRoute::kWalk4Linear: rc = dispatch_smoother_walk4_linear(method, io, ma, st); break;
+    switch (plan.route) {
+    case SmootherRoute::kCoop8Linear: rc = dispatch_smoother_coop8_linear(method, model->d, io, host, ma, st); break;
+    case SmootherRoute::kWalk4Linear: rc = dispatch_smoother_walk4_linear(method, io, host, ma, st); break;
     case SmootherRoute::kDiscLinear:  rc = dispatch_smoother_disc_linear(method, model->d, wave, io, ma, st); break;
-    case SmootherRoute::kCoop8Harm:   rc = dispatch_smoother_coop8_harm(method, model->n_harm, io, ma, st); break;
-    case SmootherRoute::kWalk4Harm:   rc = dispatch_smoother_walk4_harm(method, io, ma, st); break;
-    case SmootherRoute::kLane4:       rc = dispatch_smoother_lane4(method, model->model_id, io, ma, st); break;
+    case SmootherRoute::kCoop8Harm:   rc = dispatch_smoother_coop8_harm(method, model->n_harm, io, host, ma, st); break;
+    case SmootherRoute::kWalk4Harm:   rc = dispatch_smoother_walk4_harm(method, io, host, ma, st); break;
+    case SmootherRoute::kLane4:       rc = dispatch_smoother_lane4(method, model->model_id, io, host, ma, st); break;
     case SmootherRoute::kDiscHarm:    rc = dispatch_smoother_disc_harm(method, model->n_harm, wave, io, ma, st); break;
     case SmootherRoute::kSdeLinear:   rc = dispatch_smoother_sde_linear(method, model->d, wave, io, ma, st); break;
     case SmootherRoute::kCdSgp4Mfma:  rc = dispatch_smoother_mfma4_cdsgp(io, ma, st); break;
@@ -574,17 +545,12 @@ static int smoother_impl(cgp_ctx* ctx, int method, const cgp_model* model, const
             rc = hip_rc(hipGetLastError());
         } else if (hipMemsetAsync(junction_err, 0, sizeof(double) * (size_t)B, st) != hipSuccess) rc = CGP_E_HIP;      // nothing was split: no junction, no mismatch
     }
-    if (rc == CGP_OK && want_sel && !sel_native) {
-        SmoothSel sel;
-        sel.comp = out->comp; sel.func = out->func; sel.order = out->order;
-        sel.mean = out->comp_mean; sel.var = out->comp_var; sel.expect = out->expect; sel.xi = out->xi; sel.w = out->w;
+    if (rc == CGP_OK && plan.select == SmootherSelect::kGather) {
         const int64_t n = B * T, blocks = (n + 255) / 256;
-        hipLaunchKernelGGL(smooth_select_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, mss, Pss, n, model->d, sel);
+        hipLaunchKernelGGL(smooth_select_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, mss, Pss, n, model->d, smooth_sel(*out));
         if (hipGetLastError() != hipSuccess) rc = CGP_E_HIP;
     }
-    if (rc == CGP_E_UNSUPPORTED) return fail(ctx, rc, "this (method, model, dimension) combination is not compiled in");
-    if (rc == CGP_E_HIP) return fail(ctx, rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return rc;
+    return launch_result(ctx, rc);
 }
 
 int cgp_smoother(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, double dt,
@@ -684,10 +650,7 @@ int cgp_smoother_sample(cgp_ctx* ctx, int method, const cgp_model* model, const 
     // the literal per-point sums: the kernel takes no groups, so a grouped set is staged without its group table
     ModelArgs ma = model_args(model, sig ? sigma : nullptr, dt, CGP_LITERAL_SIGMA_SUM);
     ma.sg.group_start = nullptr; ma.sg.n_groups = 0;
-    rc = dispatch_sample4(method, model->model_id, io, ma, (hipStream_t)stream);
-    if (rc == CGP_E_UNSUPPORTED) return fail(ctx, rc, "this (method, model, dimension) combination is not compiled in");
-    if (rc == CGP_E_HIP) return fail(ctx, rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return rc;
+    return launch_result(ctx, dispatch_sample4(method, model->model_id, io, ma, (hipStream_t)stream));
 }
 
 int cgp_gaussian_expectation(cgp_ctx* ctx, const double* ms, const double* sd, int64_t n, int64_t in_stride,

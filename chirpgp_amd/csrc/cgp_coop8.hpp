@@ -491,22 +491,6 @@ constexpr int kElemC = 64, kElemc = 100, kElemZero = 108;
 constexpr int kMap8Doubles = 112;                 // a segment's map in the workspace: the same layout, padded to 16-byte multiples
 enum { kWalkWhole = 0, kWalkCompose = 1, kWalkApply = 2 };
 
-// Wavefronts per trial for the time-split form: as many as keep every workgroup resident at once (what the occupancy query
-// says a CU holds of the kernel: registers, the LDS records plus the staged sigma-point set), each with at least
-// io.min_tiles tiles; 1 = one wave per trial.
-inline int walk_segments(const SmootherIO& io, int blocks_per_cu) {
-    if (io.segs == 1) return 1;
-    const int64_t tiles = (io.T - 1 + 63) / 64;
-    int64_t per_cu = blocks_per_cu > 0 ? blocks_per_cu : 4;
-    if (per_cu > 8) per_cu = 8;
-    int64_t segs = ((int64_t)io.num_cus * per_cu) / (io.B > 0 ? io.B : 1);
-    if (io.segs > 1 && segs > io.segs) segs = io.segs;
-    const int64_t min_tiles = io.min_tiles > 0 ? io.min_tiles : 1;
-    if (segs > tiles / min_tiles) segs = tiles / min_tiles;
-    if (segs > 64) segs = 64;
-    return segs < 2 ? 1 : (int)segs;
-}
-
 // ---- one wavefront per trial: records (G, Pp, mp) in quarters of 16, the tile's filtering rows (Pf, mf) parked beside them
 constexpr int kRowDoubles = 45;                   // Pf (packed lower, 36) | mf (8) | one zero; odd: conflict-free lane stride
 constexpr int kRowmf = 36, kRowZero = 44;
@@ -796,15 +780,16 @@ __global__ void __launch_bounds__(64) coop8_split_kernel(SmootherIO io, ModelArg
 
 // The launcher of the cooperative walks (here and cgp_walk4.hpp): one wavefront per trial with kWhole, or the time-split form -- kCompose
 // leaves every segment's map (`map_doubles` each) in the context's per-stream workspace, kApply walks the segments.  The *Sel kernels
-// write the selected outputs (cgp_smoother_select) as well.
+// write the selected outputs (cgp_smoother_select) as well.  How many segments of how many tiles: walk_segments (cgp_route.hpp), from the
+// launch's policy (host.split, decided by route_smoother) and the one thing asked here, the workgroups a CU holds of the split kernel.
 using WalkKernel = void (*)(SmootherIO, ModelArgs);
 template <class Elem, WalkKernel kWhole, WalkKernel kWholeSel, WalkKernel kCompose, WalkKernel kApply, WalkKernel kApplySel>
-inline hipError_t launch_walk_smoother(const SmootherIO& io_in, const ModelArgs& ma, hipStream_t stream, int map_doubles) {
+inline hipError_t launch_walk_smoother(const SmootherIO& io_in, const SmootherLaunch& host, const ModelArgs& ma, hipStream_t stream, int map_doubles) {
     const size_t dyn = Elem::USES_SIGMA ? sigma_lds_bytes(ma, Elem::D) : 0;
     // workgroups of the split kernel a CU holds (registers, LDS): asked once per kernel and dynamic-LDS size, then remembered
     static std::atomic<long long> occ_cache{-1};                           // (dyn << 8) | per_cu
     int per_cu = 0;
-    if (io_in.segs != 1) {
+    if (host.split.cap != 1) {
         const long long seen = occ_cache.load(std::memory_order_relaxed);
         if (seen >= 0 && (size_t)(seen >> 8) == dyn) per_cu = (int)(seen & 0xFF);
         else {
@@ -812,21 +797,19 @@ inline hipError_t launch_walk_smoother(const SmootherIO& io_in, const ModelArgs&
             occ_cache.store(((long long)dyn << 8) | (per_cu & 0xFF), std::memory_order_relaxed);
         }
     }
-    const int segs = walk_segments(io_in, per_cu);
+    const WalkSegments plan = walk_segments(host.split, io_in.B, io_in.T, host.num_cus, per_cu);
     const bool sel = io_in.sel.comp >= 0;
     const WalkKernel whole_kernel = sel ? kWholeSel : kWhole, apply_kernel = sel ? kApplySel : kApply;
     auto whole = [&]() {
         hipLaunchKernelGGL(whole_kernel, dim3((unsigned)io_in.B), dim3(64), dyn, stream, io_in, ma);
         return hipGetLastError();
     };
-    if (segs <= 1) return whole();
+    if (plan.segs <= 1) return whole();
     // time-split: two passes with the segments' maps in the context's per-stream workspace (nothing the caller sees)
     SmootherIO io = io_in;
-    io.segs = segs;
-    const int64_t tiles = (io.T - 1 + 63) / 64;
-    io.tiles_per_seg = (int)((tiles + io.segs - 1) / io.segs);
-    io.segs = (int)((tiles + io.tiles_per_seg - 1) / io.tiles_per_seg);           // no empty segments
-    void* ws = ctx_workspace(io.host_ctx, stream, sizeof(double) * map_doubles * (size_t)io.B * io.segs);
+    io.segs = plan.segs;
+    io.tiles_per_seg = plan.tiles_per_seg;
+    void* ws = ctx_workspace(host.ctx, stream, sizeof(double) * map_doubles * (size_t)io.B * io.segs);
     if (!ws) return whole();             // no workspace (allocation failed, pinned too small, growth inside a graph capture): the one-wave-per-trial form needs none
     io.ws = (double*)ws;
     const unsigned grid = (unsigned)(io.B * io.segs);
@@ -836,11 +819,11 @@ inline hipError_t launch_walk_smoother(const SmootherIO& io_in, const ModelArgs&
 }
 
 template <class Elem>
-inline hipError_t launch_coop8_smoother(const SmootherIO& io, const ModelArgs& ma, hipStream_t stream) {
+inline hipError_t launch_coop8_smoother(const SmootherIO& io, const SmootherLaunch& host, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return hipSuccess;
     if (!coop8_smoother_ok(Elem::D, io.T, ma)) return hipErrorInvalidValue;      // 2 GiB buffer windows, LDS
     return launch_walk_smoother<Elem, coop8_smoother_kernel<Elem, false>, coop8_smoother_kernel<Elem, true>, coop8_split_kernel<Elem, kWalkCompose, false>,
-                                coop8_split_kernel<Elem, kWalkApply, false>, coop8_split_kernel<Elem, kWalkApply, true>>(io, ma, stream, kMap8Doubles);
+                                coop8_split_kernel<Elem, kWalkApply, false>, coop8_split_kernel<Elem, kWalkApply, true>>(io, host, ma, stream, kMap8Doubles);
 }
 
 }  // namespace cgp

@@ -13,24 +13,24 @@ int dispatch_filter_coop8_sgp(int n_harm, const FilterIO& io, const ModelArgs& m
     default: return CGP_E_UNSUPPORTED;
     }
 }
-int dispatch_smoother_coop8_linear(int method, int d, const SmootherIO& io, const ModelArgs& ma, hipStream_t st) {
+int dispatch_smoother_coop8_linear(int method, int d, const SmootherIO& io, const SmootherLaunch& host, const ModelArgs& ma, hipStream_t st) {
     if (method != CGP_S_EKS && method != CGP_S_SGP) return CGP_E_UNSUPPORTED;
     const bool sg = method == CGP_S_SGP;
     switch (d) {
-    case 5: return hip_rc(sg ? launch_coop8_smoother<SgpsElement<LinearDisc<5>>>(io, ma, st) : launch_coop8_smoother<EksElement<LinearDisc<5>>>(io, ma, st));
-    case 6: return hip_rc(sg ? launch_coop8_smoother<SgpsElement<LinearDisc<6>>>(io, ma, st) : launch_coop8_smoother<EksElement<LinearDisc<6>>>(io, ma, st));
-    case 7: return hip_rc(sg ? launch_coop8_smoother<SgpsElement<LinearDisc<7>>>(io, ma, st) : launch_coop8_smoother<EksElement<LinearDisc<7>>>(io, ma, st));
-    case 8: return hip_rc(sg ? launch_coop8_smoother<SgpsElement<LinearDisc<8>>>(io, ma, st) : launch_coop8_smoother<EksElement<LinearDisc<8>>>(io, ma, st));
+    case 5: return hip_rc(sg ? launch_coop8_smoother<SgpsElement<LinearDisc<5>>>(io, host, ma, st) : launch_coop8_smoother<EksElement<LinearDisc<5>>>(io, host, ma, st));
+    case 6: return hip_rc(sg ? launch_coop8_smoother<SgpsElement<LinearDisc<6>>>(io, host, ma, st) : launch_coop8_smoother<EksElement<LinearDisc<6>>>(io, host, ma, st));
+    case 7: return hip_rc(sg ? launch_coop8_smoother<SgpsElement<LinearDisc<7>>>(io, host, ma, st) : launch_coop8_smoother<EksElement<LinearDisc<7>>>(io, host, ma, st));
+    case 8: return hip_rc(sg ? launch_coop8_smoother<SgpsElement<LinearDisc<8>>>(io, host, ma, st) : launch_coop8_smoother<EksElement<LinearDisc<8>>>(io, host, ma, st));
     default: return CGP_E_UNSUPPORTED;
     }
 }
 // (the sigma-point elements of the harmonic models in their collapsed form only: coop8_smoother_harm_ok, cgp_route.hpp)
-int dispatch_smoother_coop8_harm(int method, int n_harm, const SmootherIO& io, const ModelArgs& ma, hipStream_t st) {
+int dispatch_smoother_coop8_harm(int method, int n_harm, const SmootherIO& io, const SmootherLaunch& host, const ModelArgs& ma, hipStream_t st) {
     if (method != CGP_S_EKS && method != CGP_S_SGP) return CGP_E_UNSUPPORTED;
     const bool sg = method == CGP_S_SGP;
     switch (n_harm) {
-    case 2: return hip_rc(sg ? launch_coop8_smoother<SgpsElement<HarmonicLCD<2>, true>>(io, ma, st) : launch_coop8_smoother<EksElement<HarmonicLCD<2>>>(io, ma, st));
-    case 3: return hip_rc(sg ? launch_coop8_smoother<SgpsElement<HarmonicLCD<3>, true>>(io, ma, st) : launch_coop8_smoother<EksElement<HarmonicLCD<3>>>(io, ma, st));
+    case 2: return hip_rc(sg ? launch_coop8_smoother<SgpsElement<HarmonicLCD<2>, true>>(io, host, ma, st) : launch_coop8_smoother<EksElement<HarmonicLCD<2>>>(io, host, ma, st));
+    case 3: return hip_rc(sg ? launch_coop8_smoother<SgpsElement<HarmonicLCD<3>, true>>(io, host, ma, st) : launch_coop8_smoother<EksElement<HarmonicLCD<3>>>(io, host, ma, st));
     default: return CGP_E_UNSUPPORTED;
     }
 }

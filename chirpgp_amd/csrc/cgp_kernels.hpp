@@ -199,23 +199,25 @@ struct SmootherIO {
     uint32_t flags;
     // time-split discrete smoothers (cgp_walk4.hpp, cgp_coop8.hpp): `segs` wavefronts per trial, each walking `tiles_per_seg`
     // 64-step tiles; the segments' composed maps (A, c, C) live in `ws` between the two passes.  segs <= 1: one wave per trial.
-    int segs = 1;                 // as handed to a launcher: 0 = choose from (B, T, num_cus); 1 = off; > 1 = this many at most
-    int min_tiles = 4;            // per segment (1 when the caller forces the time-split form)
-    int num_cus = 256;
+    // (How many: walk_segments, cgp_route.hpp.)  The three sit at byte offsets 52, 64 and 72, where the walks were measured, with the
+    // integers of the split with burn-in between them: packed together they shift, and the register allocation of coop8_split_kernel
+    // shifts with its arguments' offsets (2 and 6 more AGPR spill slots at d = 6 and d = 8).
+    int segs = 1;
+    int bsegs = 1, chunks_per_bseg = 0;      // (time-split with burn-in: below)
     int tiles_per_seg = 0;
+    int burn_chunks = 0;
     double* __restrict__ ws = nullptr;
-    cgp_ctx* host_ctx = nullptr;  // host side only: the context whose per-stream workspace (cgp::ctx_workspace) serves `ws`
     // Time-split with burn-in of the continuous-discrete smoothers (cgp_smoother_time_split; round 6): their backward ODE is not affine in the
     // carry, so a segment cannot be composed exactly -- but the recursion FORGETS its terminal condition like the filters forget their initial
     // one: segment s (0 = the last in time) starts `burn_chunks` 64-step chunks LATER than its piece from the filtering row there, writes
     // nothing until its piece begins, and leaves its state at the junction in junction[(trial * bsegs + s) * kJunctionDoubles] (m 4 | P 16)
     // for the fix-up pass to compare with the row the segment before it wrote.  bsegs <= 1: off.
     static constexpr int kJunctionDoubles = 4 + 16;
-    int bsegs = 1, chunks_per_bseg = 0, burn_chunks = 0;
     double* __restrict__ junction = nullptr;
     SmoothSel sel;                // cgp_smoother_select: selected outputs (mss / Pss may then be NULL); comp < 0: off
-    int lane_buffers = 0;         // host side: cgp_debug_set(CGP_DBG_LANE_BUFFERS) -- 3 = the large-batch smoothers request their rows two steps ahead, else one
 };
+static_assert(__builtin_offsetof(SmootherIO, segs) == 52 && __builtin_offsetof(SmootherIO, tiles_per_seg) == 64 && __builtin_offsetof(SmootherIO, ws) == 72,
+              "the walks' arguments moved: compare their register use (tools/resusage.py) before and after");
 
 // Dynamic LDS (sized by the launch): the staged sigma-point set.  The static LDS in front of it (the 17 152-byte
 // reduction buffer) is a multiple of 16 bytes, so the base stays 16-byte aligned (cdna_hip_programming.md G17).
@@ -742,17 +744,32 @@ int dispatch_smoother_disc_linear(int method, int key, bool wave, const Smoother
 int dispatch_smoother_disc_harm(int method, int key, bool wave, const SmootherIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_sde_linear(int method, int key, bool wave, const SmootherIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_sde_harm(int method, int key, bool wave, const SmootherIO&, const ModelArgs&, hipStream_t);
-int dispatch_smoother_walk4_linear(int method, const SmootherIO&, const ModelArgs&, hipStream_t);
-int dispatch_smoother_walk4_harm(int method, const SmootherIO&, const ModelArgs&, hipStream_t);
-int dispatch_smoother_coop8_linear(int method, int d, const SmootherIO&, const ModelArgs&, hipStream_t);
-int dispatch_smoother_coop8_harm(int method, int n_harm, const SmootherIO&, const ModelArgs&, hipStream_t);
-int dispatch_smoother_lane4(int method, int model_id, const SmootherIO&, const ModelArgs&, hipStream_t);
+// The host side of a smoother launch on the cooperative walks and the large-batch lane kernels: what their launchers need beside the
+// kernel's arguments.  Filled from the SmootherDecision (cgp_route.hpp) and the context.
+struct WalkSplit { int cap = 1; int min_tiles = 4; };      // exact time split: at most `cap` segments (1: off, 0: as many as fit), of `min_tiles` tiles or more
+struct SmootherLaunch {
+    cgp_ctx* ctx = nullptr;       // whose per-stream workspace (ctx_workspace) serves SmootherIO::ws
+    int num_cus = 256;
+    WalkSplit split;
+    int lane_buffers = 0;         // cgp_debug_set(CGP_DBG_LANE_BUFFERS): 3 = the large-batch smoothers request their rows two steps ahead, else one
+};
+int dispatch_smoother_walk4_linear(int method, const SmootherIO&, const SmootherLaunch&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_walk4_harm(int method, const SmootherIO&, const SmootherLaunch&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_coop8_linear(int method, int d, const SmootherIO&, const SmootherLaunch&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_coop8_harm(int method, int n_harm, const SmootherIO&, const SmootherLaunch&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_lane4(int method, int model_id, const SmootherIO&, const SmootherLaunch&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_mfma4_cdsgp(const SmootherIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_coop4_cdsgp(const SmootherIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_mfma4_cdeks(const SmootherIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_coop4_cdeks(const SmootherIO&, const ModelArgs&, hipStream_t);
 
 inline int hip_rc(hipError_t e) { return e == hipSuccess ? CGP_OK : CGP_E_HIP; }
+// What a dispatch table or a launcher returned, as the C-ABI entry returns it: the two codes a launch ends in get their message
+inline int launch_result(cgp_ctx* ctx, int rc) {
+    if (rc == CGP_E_UNSUPPORTED) return fail(ctx, rc, "this (method, model, dimension) combination is not compiled in");
+    if (rc == CGP_E_HIP) return fail(ctx, rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return rc;
+}
 #endif                         // __HIPCC_RTC__
 
 }  // namespace cgp

@@ -579,12 +579,12 @@ inline int lane4_smoother_period(int64_t T) {
     return (T * p * 128 * 64 <= kOobMaxBytes) ? p : 1;
 }
 template <class Step>
-inline hipError_t launch_lane4_smoother(const SmootherIO& io, const ModelArgs& ma, hipStream_t stream) {
+inline hipError_t launch_lane4_smoother(const SmootherIO& io, int lane_buffers, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return hipSuccess;
     if (!lane4_smoother_fits(io)) return hipErrorInvalidValue;
     // covariance rows requested one step ahead (default) or, cgp_debug_set(CGP_DBG_LANE_BUFFERS, 3), two: measured at 262 144 x 500 on MI355X, no
     // gain -- full rows 8.2 -> 8.2 ms, the marginal alone 4.91 -> 4.86, E[g] alone 8.95 -> 8.85: the prefetch depth is not what limits the kernel
-    const bool three = io.lane_buffers == 3;
+    const bool three = lane_buffers == 3;
     if (io.sel.comp >= 0) {
         // selected outputs: trials grouped by the phase of their [B][T] rows against the flushed blocks (16 or 8 doubles)
         const int nsel = (io.sel.mean ? 1 : 0) + (io.sel.var ? 1 : 0) + (io.sel.expect ? 1 : 0);

@@ -1,7 +1,9 @@
-// cgp_route.hpp -- which kernel a cgp_filter / cgp_smoother call runs.  Host code without a HIP call or a device access: the C-ABI
-// (cgp_api.hip) asks route_filter / route_smoother before it enqueues anything, and a host program can ask them too
-// (tests/route_probe.hip).  Each kernel's admission predicate is stated once, here, and serves the route functions and the guard of
-// the kernel's launcher alike.  Included by cgp_kernels.hpp, behind the types it needs.
+// cgp_route.hpp -- which kernel a cgp_filter / cgp_smoother call runs, and its whole launch plan: the refusals that depend on the kernel,
+// the segments of the time-split forms (with burn-in: both entries; exact: walk_split_policy and walk_segments for the cooperative walks,
+// whose launcher only adds the occupancy it has to ask the runtime for) and how a smoother's selected outputs get written.  Host code
+// without a HIP call or a device access: the C-ABI (cgp_api.hip) asks route_filter / route_smoother before it enqueues anything, and a
+// host program can ask them too (tests/route_probe.hip).  Each kernel's admission predicate is stated once, here, and serves the route
+// functions and the guard of the kernel's launcher alike.  Included by cgp_kernels.hpp, behind the types it needs.
 #pragma once
 #include "cgp_kernels.hpp"
 #ifndef __HIPCC_RTC__          // host code (the run-time-compiled models include these headers)
@@ -292,16 +294,70 @@ inline bool writes_selection(SmootherRoute r) {
 }
 // the kernels that know the segments of a time-split launch with burn-in (cgp_smoother_time_split)
 inline bool knows_segments(SmootherRoute r) { return r == SmootherRoute::kCdSgp4Mfma || r == SmootherRoute::kCdEks4Mfma; }
+// the cooperative walks, whose launcher (launch_walk_smoother, cgp_coop8.hpp) knows the exact time split of the discrete smoothers
+inline bool splits_exactly(SmootherRoute r) {
+    return r == SmootherRoute::kWalk4Linear || r == SmootherRoute::kWalk4Harm || r == SmootherRoute::kCoop8Linear || r == SmootherRoute::kCoop8Harm;
+}
 struct SmootherQuery {
     int method;
     const cgp_model* model;          // checked (check_model)
     const cgp_sigma* sigma;          // or NULL
-    const SmootherIO* io;
+    const SmootherIO* io;            // mfs, Pfs, B, T
     const ModelArgs* ma;
     uint32_t flags;
     int num_cus;
+    int walk_cap = 0;                // the context's CGP_DBG_WALK_SEGMENTS: 0 = choose, 1 = no exact split, n = at most n segments
+    int64_t segments = 1;            // requested (cgp_smoother_time_split); 1: none
+    int64_t burn_in = 0;
+    bool want_sel = false;           // cgp_smoother_select: selected outputs are wanted ...
+    bool null_rows = false;          // ... and mss or Pss is NULL
 };
-struct SmootherDecision { SmootherRoute route; bool wave; };
+enum class SmootherSelect { kNone, kKernel, kGather };      // selected outputs: none, written by the kernel, gathered from the full rows (smooth_select_kernel)
+struct SmootherDecision {
+    int rc = CGP_OK;                 // or the refusal and its message
+    const char* message = nullptr;
+    SmootherRoute route = SmootherRoute::kNone;
+    bool wave = true;
+    SmootherSelect select = SmootherSelect::kNone;
+    WalkSplit split;                 // the exact time split of the cooperative walks (walk_segments); off on every other route
+    int bsegs = 1, chunks_per_bseg = 0, burn_chunks = 0;      // time split with burn-in, as SmootherIO has them; bsegs <= 1: nothing is split
+};
+
+// ---- the exact time split of the discrete wave-per-trial smoothers
+// Whether a launch splits: when the batch leaves two thirds of the SIMDs idle, or on request (CGP_TIME_SPLIT, which also lets a
+// segment be a single tile).  `walk_cap` caps the number of segments of a context (tuning aid).
+inline WalkSplit walk_split_policy(const cgp_model& model, uint32_t flags, int64_t B, int num_cus, int walk_cap) {
+    const bool forced = (flags & CGP_TIME_SPLIT) != 0;
+    // Not by default for the LINEAR model (rts): its F is the caller's, and composing the affine maps of hundreds of steps
+    // (C = Pf - G Pp G^T, A <- G A) is only as accurate as those products are well conditioned -- 1e-11 of the whole-record
+    // walk for the chirp family's gains (d = 4 ... 8, every parameter set of the tests), but 1e-7 for a random F at d = 6,
+    // where partial products of the gains grow in directions the true carry never excites.  The split is exact in exact
+    // arithmetic either way; for a linear model it is the caller's choice (CGP_TIME_SPLIT).
+    const bool own_model = model.model_id != CGP_M_LINEAR;
+    WalkSplit s;
+    if ((flags & CGP_NO_TIME_SPLIT) || (!forced && (!own_model || 3 * B > (int64_t)num_cus * 4))) s.cap = 1;      // measured: x3 at B = 125, x1.6 at 250, x0.9 at 500
+    else s.cap = walk_cap > 1 ? walk_cap : (walk_cap == 1 ? 1 : 0);
+    s.min_tiles = forced ? 1 : 4;
+    return s;
+}
+// Wavefronts per trial and 64-step tiles per wavefront: as many as keep every workgroup resident at once (`blocks_per_cu`: what the
+// occupancy query says a CU holds of the split kernel -- registers, the LDS records plus the staged sigma-point set; 0: unknown, taken
+// as 4; at most 8 count), each with at least split.min_tiles tiles, none of them empty.  {1, 0}: one wave per trial.
+struct WalkSegments { int segs, tiles_per_seg; };
+inline WalkSegments walk_segments(WalkSplit split, int64_t B, int64_t T, int num_cus, int blocks_per_cu) {
+    if (split.cap == 1) return {1, 0};
+    const int64_t tiles = (T - 1 + 63) / 64;
+    int64_t per_cu = blocks_per_cu > 0 ? blocks_per_cu : 4;
+    if (per_cu > 8) per_cu = 8;
+    int64_t segs = ((int64_t)num_cus * per_cu) / (B > 0 ? B : 1);
+    if (split.cap > 1 && segs > split.cap) segs = split.cap;
+    const int64_t min_tiles = split.min_tiles > 0 ? split.min_tiles : 1;
+    if (segs > tiles / min_tiles) segs = tiles / min_tiles;
+    if (segs > 64) segs = 64;
+    if (segs < 2) return {1, 0};
+    const int64_t tiles_per_seg = (tiles + segs - 1) / segs;
+    return {(int)((tiles + tiles_per_seg - 1) / tiles_per_seg), (int)tiles_per_seg};      // no empty segments
+}
 
 inline WaveCandidate<SmootherRoute> smoother_wave_candidate(const SmootherQuery& q) {
     const cgp_model& m = *q.model;
@@ -363,8 +419,31 @@ inline SmootherDecision route_smoother(const SmootherQuery& q) {
     const SmootherRoute lane = smoother_lane_candidate(q);
     const ShapeLimit limit = lane == SmootherRoute::kLane4 ? wave.limit_lane4 : wave.limit;
     SmootherDecision d;
+    auto refuse = [&d](int rc, const char* message) { d.rc = rc; d.message = message; return d; };
     d.wave = choose_wave(q.num_cus, q.io->B, q.flags, limit, sig ? q.sigma : nullptr);
     d.route = d.wave ? wave.route : lane;
+    if (q.want_sel) {
+        if (writes_selection(d.route)) d.select = SmootherSelect::kKernel;
+        else if (q.null_rows)
+            return refuse(CGP_E_UNSUPPORTED, "this (method, model, launch shape) writes selected outputs from its full rows only: pass mss and Pss as well");
+        else d.select = SmootherSelect::kGather;
+    }
+    // ---- time-split with burn-in (cgp_smoother_time_split): the continuous-discrete smoothers on the d = 4 matrix-core kernels, segments of
+    // whole 64-step chunks; a record of one chunk, or one that leaves a single segment, is not split
+    if (q.segments > 1) {
+        if (q.burn_in < 0) return refuse(CGP_E_ARG, "burn_in must be >= 0");
+        if (q.want_sel) return refuse(CGP_E_UNSUPPORTED, "cgp_smoother_time_split writes full rows only");
+        if (!knows_segments(d.route))
+            return refuse(CGP_E_UNSUPPORTED, "time-split smoothers with burn-in are built for cd_eks and cd_sgp_smoother on the d = 4 chirp / La Scala SDE (matrix-core "
+                                             "kernels; standard sigma set); the discrete smoothers split exactly (CGP_TIME_SPLIT)");
+        const int64_t chunks = (q.io->T - 1 + 63) / 64;
+        if (chunks >= 2) {
+            const int64_t cps = (chunks + q.segments - 1) / q.segments;
+            const int64_t segs = (chunks + cps - 1) / cps;
+            if (segs > 1) { d.bsegs = (int)segs; d.chunks_per_bseg = (int)cps; d.burn_chunks = (int)((q.burn_in + 63) / 64); }
+        }
+    }
+    if (splits_exactly(d.route)) d.split = walk_split_policy(*q.model, q.flags, q.io->B, q.num_cus, q.walk_cap);
     return d;
 }
 

@@ -197,8 +197,7 @@ inline int tangent_launch(cgp_ctx* ctx, Launch launch) {
     DeviceScope on_device(ctx->device);
     if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
     std::lock_guard<std::recursive_mutex> launches(ctx->launch_mutex);
-    if (launch() != hipSuccess) return fail(ctx, CGP_E_HIP, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return CGP_OK;
+    return launch_result(ctx, hip_rc(launch()));
 }
 
 #ifndef CGP_TANGENT4_IO_ONLY      // the sigma-point units take TangentIO and not a second copy of this kernel

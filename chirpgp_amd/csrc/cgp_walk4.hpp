@@ -241,12 +241,12 @@ __global__ void __launch_bounds__(64) walk4_smoother_kernel(SmootherIO io, Model
 }
 
 template <class Elem>
-inline hipError_t launch_walk4_smoother(const SmootherIO& io, const ModelArgs& ma, hipStream_t stream) {
+inline hipError_t launch_walk4_smoother(const SmootherIO& io, const SmootherLaunch& host, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return hipSuccess;
     if (!walk4_smoother_ok(io.T, ma)) return hipErrorInvalidValue;
     return launch_walk_smoother<Elem, walk4_smoother_kernel<Elem, kWalkWhole, false>, walk4_smoother_kernel<Elem, kWalkWhole, true>,
                                 walk4_smoother_kernel<Elem, kWalkCompose, false>, walk4_smoother_kernel<Elem, kWalkApply, false>,
-                                walk4_smoother_kernel<Elem, kWalkApply, true>>(io, ma, stream, kWalkMapDoubles);
+                                walk4_smoother_kernel<Elem, kWalkApply, true>>(io, host, ma, stream, kWalkMapDoubles);
 }
 
 }  // namespace cgp

@@ -2,8 +2,9 @@
 `probe_line`) and by whoever replays the list on a GPU to record the kernels a build launches.
 
 A case: id, entry ('filter' | 'filter_split' | 'smoother' | 'smoother_split' | 'select'), method and model by name, the sigma-point set by
-kind, B, T, flags, requested segments, the byte offset of the record pointers from a 16-byte boundary, num_cus, and for 'select' whether
-mss / Pss are NULL.  `run`: a 256-CU GPU can replay the case cheaply (the others -- another CU count, records of gigabytes, a constructed
+kind, B, T, flags, requested segments, the byte offset of the record pointers from a 16-byte boundary, num_cus, for 'select' whether
+mss / Pss are NULL, and for the smoothers' plan what the occupancy query of the walks' launcher would say (blocks_per_cu, 0: it failed), the
+context's CGP_DBG_WALK_SEGMENTS value (walk_cap) and the burn-in of a 'smoother_split'.  `run`: a 256-CU GPU can replay the case cheaply (the others -- another CU count, records of gigabytes, a constructed
 sigma-point set -- have their expected route derived by reading the dispatch code, "derived" in tests/golden/routes.json)."""
 
 WAVE, THREAD, SEQUENTIAL_SCAN, GENERIC, LITERAL_SIGMA_SUM, DPP = 0x2, 0x4, 0x8, 0x10, 0x40, 0x80
@@ -48,10 +49,12 @@ def sigma_shape(kind, model):
 CASES = []
 
 
-def case(id, entry, method, model, sigma=None, B=4, T=128, flags=0, segments=1, align=0, num_cus=256, null_rows=False, run=True):
+def case(id, entry, method, model, sigma=None, B=4, T=128, flags=0, segments=1, align=0, num_cus=256, null_rows=False, run=True,
+         blocks_per_cu=4, walk_cap=0, burn_in=0):
     assert id not in {c['id'] for c in CASES}, id
     CASES.append(dict(id=id, entry=entry, method=method, model=model, sigma=sigma, B=B, T=T, flags=flags, segments=segments, align=align,
-                      num_cus=num_cus, null_rows=null_rows, run=run and num_cus == 256 and sigma != 'g33'))
+                      num_cus=num_cus, null_rows=null_rows, run=run and num_cus == 256 and sigma != 'g33',
+                      blocks_per_cu=blocks_per_cu, walk_cap=walk_cap, burn_in=burn_in))
 
 
 def methods_of(model):
@@ -154,13 +157,45 @@ for _id, _entry, _m, _model, _B, _flags, _row in EDGES:
     for _dT in (-1, 0, 1):
         case(f'edge-{_id}-{_dT:+d}', _entry, _m, _model, default_sigma(_m, _model), B=_B, T=KOOB // _row + _dT, flags=_flags, run=False)
 
+# ---- the smoothers' launch plan, one case each way across every edge of it (never run: their answers are worked out by hand from the code
+#      that decided them before route_smoother did -- smoother_impl, walk_segments and launch_walk_smoother at the parent of these cases)
+# The exact split of the walks (eks on the chirp model unless said; T = 577 is nine 64-step tiles, T = 3201 fifty).
+for _cus, _B in ((256, 341), (256, 342), (8, 10), (8, 11)):                # splits while 3 B <= 4 num_cus
+    case(f'plan-cutoff-cu{_cus}-B{_B}', 'smoother', 'eks', 'chirp', B=_B, T=577, num_cus=_cus, run=False)
+case('plan-linear4-none', 'smoother', 'eks', 'linear4', T=577, run=False)                 # the caller's F: not by default ...
+case('plan-linear4-split', 'smoother', 'eks', 'linear4', T=577, flags=TIME_SPLIT, run=False)              # ... but on request
+case('plan-split-nosplit', 'smoother', 'eks', 'chirp', T=577, flags=TIME_SPLIT | NO_TIME_SPLIT, run=False)
+case('plan-cap1', 'smoother', 'eks', 'chirp', T=577, walk_cap=1, run=False)
+case('plan-cap0', 'smoother', 'eks', 'chirp', T=577, run=False)                           # (what plan-cap1 switches off)
+case('plan-cap5', 'smoother', 'eks', 'chirp', B=125, T=3201, walk_cap=5, run=False)       # a cap that binds: 8 segments without it
+case('plan-quoted', 'smoother', 'eks', 'chirp', B=125, T=3201, run=False)                 # the shape of the cut-off's measurement: 8 x 7 tiles
+for _T in (4097, 8193):                                                    # 64 and 128 tiles, one each on request: 64 segments at the most
+    case(f'plan-ceiling-T{_T}', 'smoother', 'eks', 'chirp', T=_T, flags=TIME_SPLIT, run=False)
+for _per_cu in (0, 2, 8, 9):                                               # the occupancy query: 0 is taken as 4, more than 8 as 8
+    case(f'plan-percu{_per_cu}', 'smoother', 'eks', 'chirp', B=250, T=3201, blocks_per_cu=_per_cu, run=False)
+for _T in (449, 513):                                                      # 7 and 8 tiles: four tiles a segment unless forced
+    case(f'plan-mintiles-T{_T}', 'smoother', 'eks', 'chirp', T=_T, run=False)
+case('plan-mintiles-T449-split', 'smoother', 'eks', 'chirp', T=449, flags=TIME_SPLIT, run=False)
+case('plan-no-empty', 'smoother', 'eks', 'chirp', T=577, flags=TIME_SPLIT, walk_cap=4, run=False)     # 9 tiles on 4 segments: 3 each, so 3 segments
+case('plan-coop8', 'smoother', 'sgp', 'harm2', 'cub', B=125, T=3201, run=False)           # the tile-layout walk takes the same plan
+case('plan-lane4', 'smoother', 'eks', 'chirp', B=125, T=3201, flags=THREAD | TIME_SPLIT, run=False)   # no walk, no exact split
+# The split with burn-in (cd_eks on the chirp SDE): whole 64-step chunks of the T - 1 backward steps, no empty segment.
+for _T, _segments in ((64, 2), (65, 2), (66, 2), (129, 2), (257, 10), (321, 3), (321, 4)):
+    case(f'plan-burn-T{_T}-s{_segments}', 'smoother_split', 'cd_eks', 'chirp_sde1', T=_T, segments=_segments, run=False)
+for _burn_in in (1, 64, 65, -1):
+    case(f'plan-burn-in{_burn_in}', 'smoother_split', 'cd_eks', 'chirp_sde1', T=257, segments=2, burn_in=_burn_in, run=False)
+case('plan-burn-two-wrongs', 'smoother_split', 'eks', 'chirp', T=257, segments=2, burn_in=-1, run=False)      # the burn-in is checked first
+# Selected outputs with full rows: written by the kernels that can, gathered behind the others.
+case('plan-sel-rows-walk4', 'select', 'eks', 'chirp', run=False)
+case('plan-sel-rows-generic', 'select', 'eks', 'linear3', run=False)
+
 
 def probe_line(c):
     """One line of the probe's input: entry, method, model_id, d, n_harm, then the sigma set (s, n_groups, grouped, flags; s = 0: none), then
-    B, T, flags, segments, align, num_cus, null_rows."""
+    B, T, flags, segments, align, num_cus, null_rows, blocks_per_cu, walk_cap, burn_in (the last three: 4, 0, 0 where a case has none)."""
     model_id, d, n_harm, _ = MODELS[c['model']]
     s, n_groups, grouped, sflags = sigma_shape(c['sigma'], c['model']) or (0, 0, False, 0)
     method = (SMOOTHERS if c['entry'] in ('smoother', 'smoother_split', 'select') else FILTERS)[c['method']]
     fields = (c['entry'], method, model_id, d, n_harm, s, n_groups, int(grouped), sflags, c['B'], c['T'], c['flags'], c['segments'], c['align'],
-              c['num_cus'], int(c['null_rows']))
+              c['num_cus'], int(c['null_rows']), c.get('blocks_per_cu', 4), c.get('walk_cap', 0), c.get('burn_in', 0))
     return ' '.join(str(f) for f in fields)

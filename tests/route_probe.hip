@@ -1,6 +1,8 @@
 // Host program behind tests/test_routes.py: asks the library's own route functions (chirpgp_amd/csrc/cgp_route.hpp) which kernel each
 // launch of tests/route_cases.py would take.  Built with `hipcc --cuda-host-only`; opens no device and launches nothing.
-// stdin: one case a line (route_cases.probe_line); stdout: "<route> wave=<0|1> segs=<n>" or "refused: <why>" a line.
+// stdin: one case a line (route_cases.probe_line); stdout a line: "refused: <the library's message>", for a filter "<route> wave=<0|1>
+// segs=<n>", for a smoother the whole plan -- "<route> wave=<0|1> segs=<n> tiles=<per segment> bsegs=<n> chunks=<per segment>
+// burn=<chunks> sel=<none|kernel|gather>": the exact split of the walks, the split with burn-in, how selected outputs get written.
 #include <cstdio>
 #include <cstring>
 #include "../chirpgp_amd/csrc/cgp_kernels.hpp"
@@ -51,14 +53,23 @@ static const char* name(SmootherRoute r) {
     return "?";
 }
 
+static const char* name(SmootherSelect s) {
+    switch (s) {
+    case SmootherSelect::kNone: return "none";
+    case SmootherSelect::kKernel: return "kernel";
+    case SmootherSelect::kGather: return "gather";
+    }
+    return "?";
+}
+
 int main() {
     alignas(16) static double memory[64];      // what the pointers of a case point at: never read, only their alignment counts
     char entry[32];
-    int method, model_id, d, n_harm, s, n_groups, grouped, align, num_cus, null_rows;
+    int method, model_id, d, n_harm, s, n_groups, grouped, align, num_cus, null_rows, blocks_per_cu, walk_cap;
     unsigned sflags, flags;
-    long long B, T, segments;
-    while (scanf("%31s %d %d %d %d %d %d %d %u %lld %lld %u %lld %d %d %d", entry, &method, &model_id, &d, &n_harm, &s, &n_groups, &grouped, &sflags,
-                 &B, &T, &flags, &segments, &align, &num_cus, &null_rows) == 16) {
+    long long B, T, segments, burn_in;
+    while (scanf("%31s %d %d %d %d %d %d %d %u %lld %lld %u %lld %d %d %d %d %d %lld", entry, &method, &model_id, &d, &n_harm, &s, &n_groups, &grouped, &sflags,
+                 &B, &T, &flags, &segments, &align, &num_cus, &null_rows, &blocks_per_cu, &walk_cap, &burn_in) == 19) {
         const double* rows = (const double*)((const char*)memory + align);
         static const int group_start[1] = {0};
         cgp_model model;
@@ -79,11 +90,16 @@ int main() {
         } else {
             SmootherIO io{};
             io.mfs = rows; io.Pfs = rows; io.B = B; io.T = T; io.flags = flags;
-            const SmootherDecision r = route_smoother({method, &model, sg, &io, &ma, flags, num_cus});
-            // the two refusals cgp_smoother_select / cgp_smoother_time_split read off the route
-            if (!strcmp(entry, "select") && null_rows && !writes_selection(r.route)) printf("refused: select needs full rows\n");
-            else if (!strcmp(entry, "smoother_split") && segments > 1 && !knows_segments(r.route)) printf("refused: no segments\n");
-            else printf("%s wave=%d segs=1\n", name(r.route), (int)r.wave);
+            SmootherQuery q{method, &model, sg, &io, &ma, flags, num_cus};
+            q.walk_cap = walk_cap;
+            q.segments = segments; q.burn_in = burn_in;
+            q.want_sel = !strcmp(entry, "select"); q.null_rows = null_rows != 0;
+            const SmootherDecision r = route_smoother(q);
+            if (r.rc != CGP_OK) { printf("refused: %s\n", r.message); continue; }
+            // the exact split as the walks' launcher works it out, with the case's answer in place of the occupancy query
+            const WalkSegments w = walk_segments(r.split, B, T, num_cus, blocks_per_cu);
+            printf("%s wave=%d segs=%d tiles=%d bsegs=%d chunks=%d burn=%d sel=%s\n", name(r.route), (int)r.wave, w.segs, w.tiles_per_seg,
+                   r.bsegs, r.chunks_per_bseg, r.burn_chunks, name(r.select));
         }
     }
     return 0;

@@ -1,6 +1,9 @@
 """Which kernel a cgp_filter / cgp_smoother launch takes is pinned: the library's route functions (csrc/cgp_route.hpp), asked through the
 host program tests/route_probe.hip, answer every case of tests/route_cases.py as tests/golden/routes.json records it.
 
+A smoother's line is its whole launch plan: behind the route and the shape the segments of the exact split and their tiles, the
+segments of the split with burn-in, and how selected outputs get written; a refusal is the library's own message.
+
 The golden file: per case the route, and for the cases a 256-CU GPU replays cheaply the kernels the commit BEFORE the route functions
 existed launched (one kernel-trace run of the case list on an MI355X); the others ("derived": another CU count, records of gigabytes, a
 constructed sigma-point set) have their route read off that commit's dispatch code.  KERNELS ties each route name to the kernel names
@@ -59,23 +62,30 @@ KERNELS = {
 }
 # launches beside the routed kernel: the fix-up passes of the time-split entries
 AUXILIARY = r'cgp::(filter_split_fixup_kernel|smoother_split_fixup_kernel)\('
-# the probe's words for the two refusals that cgp_smoother_select / cgp_smoother_time_split read off the route -> the library's message
-SMOOTHER_REFUSALS = {'select needs full rows': 'writes selected outputs from its full rows only',
-                     'no segments': 'time-split smoothers with burn-in are built for'}
+# a smoother's line behind its route and shape: the plan (tests/route_probe.hip)
+PLAN = r' tiles=(?P<tiles>\d+) bsegs=(?P<bsegs>\d+) chunks=\d+ burn=\d+ sel=(?P<sel>none|kernel|gather)'
 
 
 def kernel_pattern(route_line):
-    """'<route> wave=<w> segs=<n>' -> the compiled pattern of the kernel that route launches."""
-    name, wave = re.fullmatch(r'(\w+) wave=([01]) segs=\d+', route_line).groups()
+    """'<route> wave=<w> segs=<n>[ <a smoother's plan>]' -> the compiled pattern of the kernel that route launches."""
+    name, wave = re.fullmatch(r'(\w+) wave=([01]) segs=\d+(?:%s)?' % PLAN, route_line).group(1, 2)
     pattern = KERNELS[name]
     return re.compile(pattern if isinstance(pattern, str) else pattern[wave == '0'])
 
 
 def kernels_fit(route_line, kernels):
-    """The traced launches of a case are the route's kernel (once, or the compose + apply passes of a time-split walk) and fix-up passes."""
+    """The traced launches of a case are the route's kernel and fix-up passes.  A filter's kernel runs once or twice; a smoother's as its
+    plan says: twice -- the compose and apply passes of the exact split -- where segs > 1, else once, and with the fix-up pass of the
+    split with burn-in exactly where bsegs > 1."""
     pat = kernel_pattern(route_line)
     main = [k for k in kernels if not re.search(AUXILIARY, k)]
-    return 1 <= len(main) <= 2 and all(pat.search(k) for k in main)
+    plan = re.search(r' segs=(?P<segs>\d+)' + PLAN + '$', route_line)
+    if plan:
+        fixups = [k for k in kernels if 'smoother_split_fixup_kernel' in k]
+        counts_fit = len(main) == (2 if int(plan['segs']) > 1 else 1) and len(fixups) == (1 if int(plan['bsegs']) > 1 else 0)
+    else:
+        counts_fit = 1 <= len(main) <= 2
+    return counts_fit and all(pat.search(k) for k in main)
 
 
 @pytest.fixture(scope='module')
@@ -109,11 +119,7 @@ def test_routes_are_the_recorded_ones(golden, probed):
     wrong = []
     for c in rc.CASES:
         want, got = golden[c['id']]['route'], probed[c['id']]
-        if got.startswith('refused: ') and got[9:] in SMOOTHER_REFUSALS:
-            ok = want.startswith('refused: ') and SMOOTHER_REFUSALS[got[9:]] in want
-        else:
-            ok = got == want
-        if not ok:
+        if got != want:
             wrong.append(f"{c['id']}: {got!r}, recorded {want!r}")
     assert not wrong, f'{len(wrong)} of {len(rc.CASES)} routes differ:\n' + '\n'.join(wrong[:40])
 
