@@ -61,7 +61,7 @@ class CgpSampleOut(C.Structure):
 EXPORTS = ('cgp_version', 'cgp_create', 'cgp_destroy', 'cgp_last_error', 'cgp_filter', 'cgp_smoother',
            'cgp_gaussian_expectation', 'cgp_debug_math', 'cgp_simulate', 'cgp_add_noise', 'cgp_debug_philox',
            'cgp_debug_set', 'cgp_debug_counters', 'cgp_gaussian_expectation_fn', 'cgp_filter_time_split', 'cgp_squared_error_sums',
-           'cgp_reserve_workspace', 'cgp_release_workspace', 'cgp_source_hash', 'cgp_smoother_select', 'cgp_ekf_nll_grad', 'cgp_sgp_nll_grad', 'cgp_ekf_nll_fisher', 'cgp_sgp_nll_fisher', 'cgp_model_from_source', 'cgp_custom_model_destroy',
+           'cgp_reserve_workspace', 'cgp_release_workspace', 'cgp_source_hash', 'cgp_smoother_select', 'cgp_ekf_nll_grad', 'cgp_sgp_nll_grad', 'cgp_ekf_nll_fisher', 'cgp_sgp_nll_fisher', 'cgp_cd_ekf_nll_grad', 'cgp_model_from_source', 'cgp_custom_model_destroy',
            'cgp_filter_custom', 'cgp_smoother_custom', 'cgp_smoother_time_split', 'cgp_smoother_sample')
 
 _lib = None
@@ -119,6 +119,8 @@ def load_library():
         lib.cgp_sgp_nll_fisher.restype = C.c_int
         lib.cgp_sgp_nll_fisher.argtypes = [_vp, C.POINTER(CgpModel), C.POINTER(CgpSigma), C.POINTER(CgpInit), C.c_double, _vp, C.c_int64, C.c_int64,
                                            _vp, C.c_int64, C.c_int64, _vp, C.c_int32, _vp, _vp, _vp, C.c_uint32, _vp]
+        lib.cgp_cd_ekf_nll_grad.restype = C.c_int
+        lib.cgp_cd_ekf_nll_grad.argtypes = lib.cgp_ekf_nll_grad.argtypes
         lib.cgp_model_from_source.restype = C.c_int
         lib.cgp_model_from_source.argtypes = [_vp, C.c_int, C.c_int32, C.c_char_p, C.c_char_p, C.POINTER(_vp)]
         lib.cgp_custom_model_destroy.restype = None
@@ -592,6 +594,7 @@ def run_smoother_custom(spec, gamma, dt, mfs, Pfs, flags=0, sgps=None):
 
 
 DIR_DOUBLES = 24        # include/chirpgp_hip.h: CGP_DIR_DOUBLES
+CD_DIR_DOUBLES = 27     # include/chirpgp_hip.h: CGP_CD_DIR_DOUBLES
 FISHER_MAX_DIR = 16     # include/chirpgp_hip.h: CGP_FISHER_MAX_DIR
 
 
@@ -622,15 +625,24 @@ def run_sgp_nll_fisher(spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_recor
     return _run_nll_grad(spec, _need_sigma(sgps, 'cgp_sgp_nll_fisher'), True, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing)
 
 
+def run_cd_ekf_nll_grad(spec, gamma, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None, missing=None):
+    """cgp_cd_ekf_nll_grad: the continuous-discrete EKF's final NLL and its derivative along `dirs` (B, n_dir, 27) -- forward tangents
+    through the RK4 stages and the update, one launch.  `spec` the drift's descriptor, `gamma` = b b^T (4, 4) or (B, 4, 4); everything
+    else, and the results, as run_ekf_nll_grad."""
+    if gamma is None:
+        raise ValueError('cgp_cd_ekf_nll_grad needs gamma = b b^T')
+    return _run_nll_grad(spec, None, False, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing, gamma=gamma)
+
+
 def _need_sigma(sgps, entry):
     if sgps is None:
         raise ValueError(f'{entry} needs a sigma-point set')
     return sgps
 
 
-def _run_nll_grad(spec, sgps, fisher, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing=None):
-    """The four tangent entry points: the sigma-point filter's with `sgps`, the EKF's with None; `fisher`: the matrix as a third output;
-    `missing`: as run_filter's, through _missing_flag."""
+def _run_nll_grad(spec, sgps, fisher, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing=None, gamma=None):
+    """The tangent entry points: the sigma-point filter's with `sgps`, the EKF's with None, the continuous-discrete EKF's with `gamma`
+    (b b^T; directions of 27 doubles, not 24); `fisher`: the matrix as a third output; `missing`: as run_filter's, through _missing_flag."""
     gaps = _missing_flag(missing)
     torch = _torch()
     ys_d = dev(ys)
@@ -640,19 +652,20 @@ def _run_nll_grad(spec, sgps, fisher, H, Xi, m0, P0, dt, ys, dirs, trials_per_re
     rep, idx_h, B = _record_addressing(int(ys_d.shape[0]), trials_per_record, record_index)
     d = _check_dimension(spec)
     dirs_h = np.ascontiguousarray(np.asarray(dirs, dtype=np.float64))
-    if dirs_h.ndim != 3 or dirs_h.shape[0] != B or dirs_h.shape[2] != DIR_DOUBLES:
-        raise ValueError(f'dirs must be ({B}, n_dir, {DIR_DOUBLES}); got {dirs_h.shape}')
+    per_dir = DIR_DOUBLES if gamma is None else CD_DIR_DOUBLES
+    if dirs_h.ndim != 3 or dirs_h.shape[0] != B or dirs_h.shape[2] != per_dir:
+        raise ValueError(f'dirs must be ({B}, n_dir, {per_dir}); got {dirs_h.shape}')
     n_dir = int(dirs_h.shape[1])
     with torch.cuda.device(ys_d.device):
         ctx = context(ys_d.device.index)
         idx_d = _index_const(idx_h) if idx_h is not None else None
         keep = [ys_d, idx_d]
-        model = _model_struct(spec, None, B, keep)
+        model = _model_struct(spec, gamma, B, keep)
         init = _init_struct(H, Xi, m0, P0, d, B, keep)
         dirs_d = dev(dirs_h, ys_d.device.index)
         opts = dict(dtype=torch.float64, device=ys_d.device)
         outs = [torch.empty((B,), **opts), torch.empty((B, n_dir), **opts)] + ([torch.empty((B, n_dir, n_dir), **opts)] if fisher else [])
-        entry = f'cgp_{"ekf" if sgps is None else "sgp"}_nll_{"fisher" if fisher else "grad"}'
+        entry = f'cgp_{"ekf" if sgps is None else "sgp"}_nll_{"fisher" if fisher else "grad"}' if gamma is None else 'cgp_cd_ekf_nll_grad'
         sig = [] if sgps is None else [C.byref(_sigma_struct(sgps, d, keep, None))]
         rc = _timed('filter', lambda: getattr(load_library(), entry)(ctx, C.byref(model), *sig, C.byref(init), float(dt), _ptr(ys_d), T, rep, _ptr(idx_d),
                                                                      B, T, _ptr(dirs_d), n_dir, *(_ptr(o) for o in outs), gaps, _stream()))

@@ -120,11 +120,12 @@ CGP_DEV TangentUpdate tangent_update(const double (&h)[4], double Xi, double dXi
     return u;
 }
 
-// ---- the host side the four entry points share (cgp_inst_tangent4.hip, cgp_inst_tangent4_sgp.hip): each is tangent_args, then its own
+// ---- the host side the tangent entry points share (cgp_inst_tangent4.hip, cgp_inst_tangent4_sgp.hip, cgp_inst_tangent4_cd.hip): each is tangent_args, then its own
 // limit, then tangent_launch of its kernel.
 struct TangentCall {
     const char* entry;                   // the entry point's name, for its messages
     bool sgp, fisher;                    // takes a sigma-point set (sigma-point sets beyond the LDS stage are refused) / writes the matrix
+    bool cd = false;                     // the continuous-discrete form (cgp_tangent4_cd.hpp): the d = 4 chirp / La Scala SDE with its gamma
 };
 
 // The header's name of one flag bit, for the message that refuses it
@@ -159,9 +160,16 @@ inline int tangent_args(cgp_ctx* ctx, TangentCall call, const cgp_model* model, 
     if (call.fisher && n_dir > kFisherMaxDir)      // a row of the matrix lives in registers, and the matrix couples all the directions of a launch
         return fail(ctx, CGP_E_UNSUPPORTED, entry + " takes all directions in one launch: n_dir must be <= CGP_FISHER_MAX_DIR (16)");
     if (!model || !model->params) return fail(ctx, CGP_E_ARG, "model or model.params is NULL");
-    const bool chirp = model->model_id == CGP_M_HARMONIC_LCD && model->n_harm == 1 && model->n_params == 5;
-    const bool lascala = model->model_id == CGP_M_LASCALA_LCD && model->n_params == 2;
-    if ((!chirp && !lascala) || model->d != 4) return fail(ctx, CGP_E_UNSUPPORTED, entry + " is built for the d = 4 chirp and La Scala LCD models");
+    if (call.cd) {
+        const bool sde = model->model_id == CGP_M_HARMONIC_SDE && model->n_harm == 1 && model->n_params == 3;
+        if (!sde || model->d != 4 || !model->gamma)
+            return fail(ctx, CGP_E_UNSUPPORTED, entry + " is built for the d = 4 chirp and La Scala SDE (CGP_M_HARMONIC_SDE, n_harm = 1) with model.gamma set");
+        if (model->gamma_stride != 0 && model->gamma_stride < 16) return fail(ctx, CGP_E_ARG, "model.gamma_stride < d * d");
+    } else {
+        const bool chirp = model->model_id == CGP_M_HARMONIC_LCD && model->n_harm == 1 && model->n_params == 5;
+        const bool lascala = model->model_id == CGP_M_LASCALA_LCD && model->n_params == 2;
+        if ((!chirp && !lascala) || model->d != 4) return fail(ctx, CGP_E_UNSUPPORTED, entry + " is built for the d = 4 chirp and La Scala LCD models");
+    }
     if (model->param_stride != 0 && model->param_stride < model->n_params) return fail(ctx, CGP_E_ARG, "model.param_stride < n_params");
     if (call.sgp) {
         if (!sigma) return fail(ctx, CGP_E_ARG, "sigma is NULL");

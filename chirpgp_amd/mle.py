@@ -13,7 +13,7 @@ import numpy as np
 from chirpgp_amd import filters_smoothers as fs
 from chirpgp_amd import models as M
 
-__all__ = ['batched_nll', 'make_objective', 'fit', 'fit_many', 'grid_search', 'value_and_grad', 'tangent_directions', 'has_exact_gradient',
+__all__ = ['batched_nll', 'make_objective', 'fit', 'fit_many', 'grid_search', 'value_and_grad', 'tangent_directions', 'tangent_directions_cd', 'has_exact_gradient',
            'value_grad_fisher', 'covariance_from_fisher', 'standard_errors', 'scoring_step', 'fit_scoring']
 
 
@@ -165,6 +165,49 @@ def tangent_directions(build, thetas, dt, Xi, h=1e-30):
     return out
 
 
+def _chirp_constants_cd(p, Xi):
+    """The 27 constants of the CONTINUOUS model a tangent direction of cgp_cd_ekf_nll_grad differentiates (include/chirpgp_hip.h:
+    CGP_CD_DIR_DOUBLES), as functions of the chirp builder's parameters lam, b, delta, ell, sigma, m0_v (models.py:437-459, 76-119):
+    lam | gam = sqrt(3) / ell | gamma = b b^T = diag(b^2, b^2, 0, 4 sigma^2 gam^3), packed | Xi | m0 | P0, packed -- complex-safe,
+    vectorised over a trailing axis: p (6, G) -> (27, G).  Products and powers only: nothing cancels, for any parameters."""
+    lam, b, delta, ell, sigma, m0_v = p
+    gam = np.sqrt(3.) / ell
+    zero = 0. * lam
+    Gam = [b ** 2, zero, b ** 2, zero, zero, zero, zero, zero, zero, 4. * sigma ** 2 * gam ** 3]
+    P0 = [delta, zero, delta, zero, zero, sigma ** 2, zero, zero, zero, gam ** 2 * sigma ** 2]
+    return np.stack([lam, gam, *Gam, Xi + zero, zero, zero, m0_v, zero, *P0])
+
+
+def _lascala_constants_cd(p, Xi):
+    """models.py:497-519, 181-261: delta, ell, sigma, m0_v; no damping, no chirp noise."""
+    delta, ell, sigma, m0_v = p
+    zero = 0. * delta
+    return _chirp_constants_cd([zero, zero, delta, ell, sigma, m0_v], Xi)
+
+
+def _constants_cd_of(build):
+    return {M.build_chirp_model: _chirp_constants_cd, M.build_lascala_model: _lascala_constants_cd}.get(build)
+
+
+def tangent_directions_cd(build, thetas, dt, Xi, h=1e-30):
+    """tangent_directions for the continuous-discrete EKF (cgp_cd_ekf_nll_grad): d (constants of the continuous model) / d theta_k for every
+    row of thetas (G, P) -> (G, P, 27), by complex step on _chirp_constants_cd / _lascala_constants_cd times sigmoid(theta).  The SDE's
+    constants do not depend on dt (the kernel's RK4 stages take it as it is); the argument keeps the two functions' signatures alike.
+    Every entry is within 1e-12 of the derivative taken in 100-digit arithmetic (tests/test_cd_gradient_host.py)."""
+    consts = _constants_cd_of(build)
+    thetas = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
+    G, P = thetas.shape
+    out = np.empty((G, P, 27))
+    with np.errstate(all='ignore'):
+        params = np.logaddexp(0., thetas).T                      # (P, G): g(theta) to rounding, as in tangent_directions
+        dg = 1.0 / (1.0 + np.exp(-thetas))
+        for k in range(P):
+            pc = params.astype(np.complex128)
+            pc[k] += 1j * h
+            out[:, k, :] = (np.imag(consts(pc, float(Xi))) / h).T * dg[:, k, None]
+    return out
+
+
 def _sigma_dim(sgps):
     xi = getattr(sgps, 'xi', None)
     return None if xi is None or np.ndim(xi) != 2 else int(np.shape(xi)[1])
@@ -172,10 +215,11 @@ def _sigma_dim(sgps):
 
 def has_exact_gradient(method, build, Xi, sgps=None):
     """The in-kernel tangent gradient exists on the d = 4 chirp and La Scala models with a scalar Xi for the discrete EKF
-    (cgp_ekf_nll_grad) and for the sigma-point filter with a d = 4 sigma-point set ``sgps`` (cgp_sgp_nll_grad)."""
+    (cgp_ekf_nll_grad), for the continuous-discrete EKF (cgp_cd_ekf_nll_grad) and for the sigma-point filter with a d = 4 sigma-point
+    set ``sgps`` (cgp_sgp_nll_grad)."""
     if _constants_of(build) is None or np.ndim(Xi) != 0:
         return False
-    if method == 'ekf':
+    if method in ('ekf', 'cd_ekf'):
         return True
     return method == 'sgp_filter' and _sigma_dim(sgps) == 4
 
@@ -205,8 +249,18 @@ def _exact_with_gaps(exact, missing):
 
 
 def _exact_unsupported():
-    return ValueError('exact=True: the tangent kernels are built for the discrete EKF and the sigma-point filter (with a d = 4 sigma-point '
-                      'set, sgps=) on build_chirp_model / build_lascala_model with a scalar Xi')
+    return ValueError('exact=True: the tangent kernels are built for the discrete EKF, the continuous-discrete EKF and the sigma-point filter '
+                      '(with a d = 4 sigma-point set, sgps=) on build_chirp_model / build_lascala_model with a scalar Xi')
+
+
+def _has_fisher_form(method):
+    """The Fisher forms (cgp_ekf_nll_fisher, cgp_sgp_nll_fisher) exist for the discrete filters only."""
+    return method != 'cd_ekf'
+
+
+def _fisher_unsupported(method):
+    return ValueError(f'the tangent kernel of {method!r} writes value and gradient only: its Fisher form is not built '
+                      '(value_grad_fisher, standard_errors and fit_scoring take the discrete EKF and the sigma-point filter)')
 
 
 def _tangent_launch(fisher, build, thetas, ys, Xi, dt, record_index, method, sgps, missing=None):
@@ -215,10 +269,16 @@ def _tangent_launch(fisher, build, thetas, ys, Xi, dt, record_index, method, sgp
     from chirpgp_amd import _engine as E
     if not has_exact_gradient(method, build, Xi, sgps):
         raise _exact_unsupported()
+    if fisher and not _has_fisher_form(method):
+        raise _fisher_unsupported(method)
     thetas = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
     rows = _rows_per_record(thetas.shape[0], ys, record_index)
     with np.errstate(all='ignore'):
         drift, disp, disc, m0, P0, H = build(M.g(thetas))
+    if method == 'cd_ekf':
+        out = E.run_cd_ekf_nll_grad(drift, disp.outer(), H, Xi, m0, P0, dt, ys, tangent_directions_cd(build, thetas, dt, Xi),
+                                    trials_per_record=rows, record_index=record_index, missing=missing)
+        return tuple(o.cpu().numpy() for o in out)
     dirs = tangent_directions(build, thetas, dt, Xi)
     if method == 'sgp_filter':
         out = (E.run_sgp_nll_fisher if fisher else E.run_sgp_nll_grad)(disc, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=rows, record_index=record_index,
@@ -231,8 +291,9 @@ def _tangent_launch(fisher, build, thetas, ys, Xi, dt, record_index, method, sgp
 
 def value_and_grad(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf', sgps=None, missing=None):
     """Objective and its EXACT gradient (forward tangents through the scan) at every row of thetas (G, P), in ONE launch: the EKF's
-    (method='ekf', cgp_ekf_nll_grad: G P lanes) or the sigma-point filter's (method='sgp_filter' with a d = 4 SigmaPoints ``sgps``,
-    cgp_sgp_nll_grad: G wavefronts).  ys (T,) or (R, T) shared out evenly over the rows as in batched_nll.  -> (nll (G,), grad (G, P)).
+    (method='ekf', cgp_ekf_nll_grad: G P lanes), the continuous-discrete EKF's (method='cd_ekf', cgp_cd_ekf_nll_grad: G P lanes, the
+    tangent carried through the four RK4 stages of every step) or the sigma-point filter's (method='sgp_filter' with a d = 4 SigmaPoints
+    ``sgps``, cgp_sgp_nll_grad: G wavefronts).  ys (T,) or (R, T) shared out evenly over the rows as in batched_nll.  -> (nll (G,), grad (G, P)).
     ``missing='skip'``: NaN samples of the records are gaps, as in batched_nll -- the likelihood of the observed samples alone and its
     exact gradient; a record of NaN only gives 0 and a zero gradient."""
     return _tangent_launch(False, build, thetas, ys, Xi, dt, record_index, method, sgps, missing)
@@ -330,6 +391,8 @@ def fit_scoring(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=100,
     from chirpgp_amd import _engine as E
     if not has_exact_gradient(method, build, Xi, sgps):
         raise _exact_unsupported()
+    if not _has_fisher_form(method):
+        raise _fisher_unsupported(method)
     E._missing_flag(missing)                           # a misspelt value fails here, before anything is copied
     yss = E.dev(yss)
     if yss.ndim == 1:
@@ -380,7 +443,8 @@ def fit_scoring(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=100,
 
 def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=None, *, missing=None, **build_kw):
     """-> fun(theta) returning (nll, gradient): value and central differences from one batched launch of 2 P + 1 filter passes, or --
-    ``exact=True``, the discrete EKF or the sigma-point filter (with a d = 4 ``sgps``) on the chirp / La Scala models -- value and EXACT
+    ``exact=True``, the discrete EKF, the continuous-discrete EKF ('cd_ekf') or the sigma-point filter (with a d = 4 ``sgps``) on the chirp /
+    La Scala models -- value and EXACT
     gradient from one launch of a tangent kernel (cgp_ekf_nll_grad: within 8e-13 of the gradient's scale against 100-digit arithmetic where
     the differences carry 2e-7; slower for a single record, see EXACT_FROM_RECORDS; cgp_sgp_nll_grad).  exact=None takes the tangent kernel
     for the EKF from EXACT_FROM_RECORDS records only and never for the sigma-point filter.  ``missing='skip'`` (a record with gaps):

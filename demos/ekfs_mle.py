@@ -3,8 +3,8 @@
     python demos/ekfs_mle.py [--method ekf|sgp_filter|cd_ekf] [--T 3141] [--seed 555] [--exact] [--stderr]
 
 --exact: the objective's gradient from a tangent kernel (forward tangents through the scan, what jax.value_and_grad gives the
-reference, demos/ekfs_mle.py:43-48) instead of 13-probe central differences: the EKF's (cgp_ekf_nll_grad) or, with --method sgp_filter,
-the sigma-point filter's (cgp_sgp_nll_grad).  cd_ekf has none.  The estimate E[g(V)] rides in the smoother launch.
+reference, demos/ekfs_mle.py:43-48) instead of 13-probe central differences: the EKF's (cgp_ekf_nll_grad), with --method sgp_filter the sigma-point filter's
+(cgp_sgp_nll_grad), with --method cd_ekf the continuous-discrete EKF's (cgp_cd_ekf_nll_grad).  The estimate E[g(V)] rides in the smoother launch.
 --stderr: the estimates with their standard errors, from the Fisher information of the filter's innovations at the optimum (one more
 launch: cgp_ekf_nll_fisher / cgp_sgp_nll_fisher, mle.standard_errors); "flat" where the information is singular.  Methods ekf, sgp_filter.
 """
@@ -30,7 +30,7 @@ def main():
     ap.add_argument('--method', default='ekf', choices=['ekf', 'sgp_filter', 'cd_ekf'])
     ap.add_argument('--T', type=int, default=3141)
     ap.add_argument('--seed', type=int, default=555)
-    ap.add_argument('--exact', action='store_true', help='exact gradients (methods ekf and sgp_filter)')
+    ap.add_argument('--exact', action='store_true', help='exact gradients from the tangent kernels')
     ap.add_argument('--stderr', action='store_true', help='standard errors of the estimates (methods ekf and sgp_filter)')
     args = ap.parse_args()
     if args.stderr and args.method == 'cd_ekf':
@@ -47,7 +47,7 @@ def main():
         ys = gen_chirp(ts, mag, true_phase_func) + math.sqrt(Xi) * rng.standard_normal(T)
         t0 = time.time()
         opt_params, res = mle.fit(args.method, build_chirp_model, [0.1, 0.1, 0.1, 1., 1., 7.], ys, Xi, dt, sgps=sgps,
-                                  exact=True if (args.exact and args.method in ('ekf', 'sgp_filter')) else None)
+                                  exact=True if args.exact else None)
         drift, dispersion, m_and_cov, m0, P0, H = build_chirp_model(opt_params)
         if args.method == 'ekf':
             mfs, Pfs, _ = fs.ekf(m_and_cov, H, Xi, m0, P0, dt, ys)

@@ -22,6 +22,7 @@
  *                                                                      of rts / eks / sgp_smoother by backward simulation on the smoother's own affine maps
  *   cgp_ekf_nll_grad                                                   value_and_grad of ekf(...)[-1][-1] through the scan, demos/ekfs_mle.py:43-51
  *   cgp_sgp_nll_grad                                                   value_and_grad of sgp_filter(...)[-1][-1] through the scan, demos/ghfs_mle.py:53-56
+ *   cgp_cd_ekf_nll_grad                                                value_and_grad of cd_ekf(...)[-1][-1] through the scan, demos/cd_ekfs_mle.py
  *   cgp_ekf_nll_fisher / cgp_sgp_nll_fisher                            (no counterpart: the reference's jobs report point estimates only)
  *   cgp_model_from_source, cgp_filter_custom, cgp_smoother_custom      ekf / eks / cd_ekf / cd_eks on ANY model (the reference traces any callable:
  *                                                                      filters_smoothers.py:255, 342, 382, 425; test/test_ekfs.py:11-62), compiled at run time
@@ -168,7 +169,7 @@ typedef struct cgp_init {
                                         composed maps are exact in exact arithmetic but only as accurate as products of the caller's gains
                                         are well conditioned (1e-11 of the one-wave walk for the chirp models, 1e-7 seen for a random F)   */
 #define CGP_NO_TIME_SPLIT     0x1000u /* ... never                                                                                      */
-#define CGP_SKIP_MISSING      0x2000u /* filters (cgp_filter, cgp_filter_custom) and the four gradient / Fisher entry points: a NaN measurement is
+#define CGP_SKIP_MISSING      0x2000u /* filters (cgp_filter, cgp_filter_custom) and the gradient / Fisher entry points: a NaN measurement is
                                          a missing sample, not poison -- see cgp_filter, cgp_ekf_nll_grad */
 #define CGP_SIM_FIXED_X0      0x20u /* cgp_simulate: x_0 = m0 exactly, P0 unused (simulate_sde_init, simulate_lgssm)       */
 
@@ -211,7 +212,7 @@ const char* cgp_last_error(const cgp_ctx* ctx);
  * matrix-core kernels of ekf, sgp_filter, cd_ekf and cd_sgp_filter on the d = 4 chirp / La Scala models; every other specialised kernel
  * (kf at d = 4, d = 6 / 8, ekf_for_kpt's tile layout, the DPP variants, the four-trials-per-wavefront EKF, the large-batch lane kernels)
  * hands a flagged call to the generic kernel in the launch shape the call has.  cgp_filter_time_split refuses the flag (CGP_E_UNSUPPORTED): a burn-in that starts inside a gap has no
- * junction to compare.  The gradient and Fisher entries (cgp_ekf_nll_grad, cgp_sgp_nll_grad, cgp_ekf_nll_fisher, cgp_sgp_nll_fisher) take
+ * junction to compare.  The gradient and Fisher entries (cgp_ekf_nll_grad, cgp_sgp_nll_grad, cgp_cd_ekf_nll_grad, cgp_ekf_nll_fisher, cgp_sgp_nll_fisher) take
  * this flag and no other: a gap then adds exactly nothing to nll, grad and fisher -- see there. */
 int cgp_filter(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init,
                double dt, const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index,
@@ -287,6 +288,27 @@ int cgp_ekf_nll_fisher(cgp_ctx* ctx, const cgp_model* model, const cgp_init* ini
 int cgp_sgp_nll_fisher(cgp_ctx* ctx, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init, double dt,
                        const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
                        const double* dirs, int32_t n_dir, double* nll, double* grad, double* fisher, uint32_t flags, void* stream);
+
+/* The continuous-discrete EKF's final negative log-likelihood AND its exact gradient in one launch: forward tangents of (m, P, nll)
+ * carried through the four RK4 stages (quadratures.py:34-54) of cd_ekf's moment ODE dm/dt = a(m), dP/dt = J P + P J^T + gamma
+ * (filters_smoothers.py:352-397) and through the update -- the reference differentiates cd_ekf(...)[-1][-1] through the scan
+ * (demos/cd_ekfs_mle.py, tetralith/jobs/cd_ekfs_mle.py).  Models: CGP_M_HARMONIC_SDE with n_harm = 1, d = 4, n_params = 3 and
+ * cgp_model.gamma set (the chirp SDE; lam = 0 and a gamma without chirp noise is La Scala's); anything else is CGP_E_UNSUPPORTED.
+ * A direction is CGP_CD_DIR_DOUBLES doubles: the derivative, along one coordinate of the caller's parametrisation, of the CONTINUOUS
+ * model's constants
+ *     lam | gam (= sqrt(3) / ell) | gamma = b b^T (10: packed lower triangle 00 10 11 20 21 22 30 31 32 33) | Xi | m0 (4) |
+ *     P0 (10: packed lower triangle)
+ * computed by the caller from its model builder (chirpgp_amd/mle.py: tangent_directions_cd, by complex step); the derivative through the
+ * state-dependent part of the drift and its Jacobian (softplus frequency, its first and second derivative) is taken by the kernel; dt
+ * carries no tangent.  dirs: [B][n_dir][CGP_CD_DIR_DOUBLES] (device), nll: [B], grad: [B][n_dir].  Records, per-trial operands
+ * (param_stride, gamma_stride, the strides of cgp_init), T = 0 (nll = 0, grad = 0) and a diverged filter (NaN in nll and in every grad
+ * entry of that trial) as in cgp_ekf_nll_grad.  One lane per (trial, direction); B n_dir < 2^37.
+ * flags: 0 or CGP_SKIP_MISSING with the meaning it has in cgp_ekf_nll_grad (a NaN measurement is a gap: the RK4 prediction is the step's
+ * filtering result along every direction and nothing is added to nll and grad); any other bit is CGP_E_ARG, with the bit's name. */
+#define CGP_CD_DIR_DOUBLES 27
+int cgp_cd_ekf_nll_grad(cgp_ctx* ctx, const cgp_model* model, const cgp_init* init, double dt,
+                        const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
+                        const double* dirs, int32_t n_dir, double* nll, double* grad, uint32_t flags, void* stream);
 
 /* ---- models compiled at run time ------------------------------------------------------------------------------------------
  * The reference's filters take any JAX-traceable callable (filters_smoothers.py:255, 304, 382, 425); the enumerated models above are the
