@@ -387,6 +387,13 @@ def _nonlinear_coord(spec):
     return int(spec.d) - 2 if int(spec.model_id) in (M_HARMONIC_LCD, M_LASCALA_LCD, M_HARMONIC_SDE) else None
 
 
+def _new_output(shape, device, name=None):
+    """Every array a kernel writes its results into is created here and nowhere else, so that a test can substitute the allocator
+    (tests/guard_bands.py: outputs embedded in guard bands).  `name`: the array's name in include/chirpgp_hip.h, for such a test's reports."""
+    torch = _torch()
+    return torch.empty(shape, dtype=torch.float64, device=device)
+
+
 def _out(t, like_numpy, squeeze):
     if squeeze:
         t = t[0]
@@ -476,15 +483,14 @@ def run_filter(method, spec, sgps, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=
         model = _model_struct(spec, gamma, B, keep)
         sig = _sigma_struct(sgps, d, keep, _nonlinear_coord(spec))
         init = _init_struct(H, Xi, m0, P0, d, B, keep)
-        opts = dict(dtype=torch.float64, device=ys_d.device)
-        mfs = torch.empty((B, T, d), **opts) if want[0] else None
-        Pfs = torch.empty((B, T, d, d), **opts) if want[1] else None
-        nll = (torch.empty((B,) if nll_final_only else (B, T), **opts)) if want[2] else None
+        mfs = _new_output((B, T, d), ys_d.device, 'mfs') if want[0] else None
+        Pfs = _new_output((B, T, d, d), ys_d.device, 'Pfs') if want[1] else None
+        nll = _new_output((B,) if nll_final_only else (B, T), ys_d.device, 'nll') if want[2] else None
         fl = int(flags) | (NLL_FINAL_ONLY if nll_final_only else 0) | gaps
         lib, st = load_library(), _stream()
         if time_split is not None:
             segments, burn_in = (int(v) for v in time_split)
-            err = torch.empty((B,), **opts)
+            err = _new_output((B,), ys_d.device, 'junction_err')
             rc = _timed('filter', lambda: lib.cgp_filter_time_split(ctx, int(method), C.byref(model), C.byref(sig) if sig is not None else None,
                                                                     C.byref(init), float(dt), _ptr(ys_d), T, rep, _ptr(idx_d), B, T,
                                                                     _ptr(mfs), _ptr(Pfs), _ptr(nll), fl, segments, burn_in, _ptr(err), st))
@@ -556,10 +562,9 @@ def run_filter_custom(spec, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=False, 
         params, pstride, g, gstride = _model_operands(spec, gamma, B, keep)
         sig = _sigma_struct(sgps, d, keep, None)
         init = _init_struct(H, Xi, m0, P0, d, B, keep)
-        opts = dict(dtype=torch.float64, device=ys_d.device)
-        mfs = torch.empty((B, T, d), **opts) if want[0] else None
-        Pfs = torch.empty((B, T, d, d), **opts) if want[1] else None
-        nll = (torch.empty((B,) if nll_final_only else (B, T), **opts)) if want[2] else None
+        mfs = _new_output((B, T, d), ys_d.device, 'mfs') if want[0] else None
+        Pfs = _new_output((B, T, d, d), ys_d.device, 'Pfs') if want[1] else None
+        nll = _new_output((B,) if nll_final_only else (B, T), ys_d.device, 'nll') if want[2] else None
         fl = int(flags) | (NLL_FINAL_ONLY if nll_final_only else 0) | gaps
         rc = _timed('filter', lambda: load_library().cgp_filter_custom(ctx, handle, C.byref(sig) if sig is not None else None, _ptr(params), pstride, _ptr(g), gstride, C.byref(init), float(dt),
                                                                        _ptr(ys_d), T, 1, None, B, T, _ptr(mfs), _ptr(Pfs), _ptr(nll), fl, _stream()))
@@ -586,7 +591,7 @@ def run_smoother_custom(spec, gamma, dt, mfs, Pfs, flags=0, sgps=None):
         keep = [m, P]
         params, pstride, g, gstride = _model_operands(spec, gamma, B, keep)
         sig = _sigma_struct(sgps, d, keep, None)
-        mss, Pss = torch.empty_like(m), torch.empty_like(P)
+        mss, Pss = _new_output(tuple(m.shape), m.device, 'mss'), _new_output(tuple(P.shape), P.device, 'Pss')
         rc = _timed('smoother', lambda: load_library().cgp_smoother_custom(ctx, handle, C.byref(sig) if sig is not None else None, _ptr(params), pstride, _ptr(g), gstride, float(dt), _ptr(m), _ptr(P),
                                                                            B, T, _ptr(mss), _ptr(Pss), int(flags), _stream()))
         _check(ctx, rc, 'cgp_smoother_custom')
@@ -651,10 +656,11 @@ def _run_nll_grad(spec, sgps, fisher, H, Xi, m0, P0, dt, ys, dirs, trials_per_re
     T = int(ys_d.shape[1])
     rep, idx_h, B = _record_addressing(int(ys_d.shape[0]), trials_per_record, record_index)
     d = _check_dimension(spec)
-    dirs_h = np.ascontiguousarray(np.asarray(dirs, dtype=np.float64))
+    # (directions already on the device go over as they are, like ys)
+    dirs_h = dirs if _is_torch(dirs) else np.ascontiguousarray(np.asarray(dirs, dtype=np.float64))
     per_dir = DIR_DOUBLES if gamma is None else CD_DIR_DOUBLES
     if dirs_h.ndim != 3 or dirs_h.shape[0] != B or dirs_h.shape[2] != per_dir:
-        raise ValueError(f'dirs must be ({B}, n_dir, {per_dir}); got {dirs_h.shape}')
+        raise ValueError(f'dirs must be ({B}, n_dir, {per_dir}); got {tuple(dirs_h.shape)}')
     n_dir = int(dirs_h.shape[1])
     with torch.cuda.device(ys_d.device):
         ctx = context(ys_d.device.index)
@@ -663,8 +669,8 @@ def _run_nll_grad(spec, sgps, fisher, H, Xi, m0, P0, dt, ys, dirs, trials_per_re
         model = _model_struct(spec, gamma, B, keep)
         init = _init_struct(H, Xi, m0, P0, d, B, keep)
         dirs_d = dev(dirs_h, ys_d.device.index)
-        opts = dict(dtype=torch.float64, device=ys_d.device)
-        outs = [torch.empty((B,), **opts), torch.empty((B, n_dir), **opts)] + ([torch.empty((B, n_dir, n_dir), **opts)] if fisher else [])
+        outs = ([_new_output((B,), ys_d.device, 'nll'), _new_output((B, n_dir), ys_d.device, 'grad')]
+                + ([_new_output((B, n_dir, n_dir), ys_d.device, 'fisher')] if fisher else []))
         entry = f'cgp_{"ekf" if sgps is None else "sgp"}_nll_{"fisher" if fisher else "grad"}' if gamma is None else 'cgp_cd_ekf_nll_grad'
         sig = [] if sgps is None else [C.byref(_sigma_struct(sgps, d, keep, None))]
         rc = _timed('filter', lambda: getattr(load_library(), entry)(ctx, C.byref(model), *sig, C.byref(init), float(dt), _ptr(ys_d), T, rep, _ptr(idx_d),
@@ -728,8 +734,8 @@ def run_smoother(method, spec, sgps, gamma, dt, mfs, Pfs, flags=0, want=(True, T
             if select is not None:
                 raise ValueError('time_split writes full rows only')
             segments, burn_in = (int(v) for v in time_split)
-            mss, Pss = torch.empty_like(m), torch.empty_like(P)
-            err = torch.empty((B,), dtype=torch.float64, device=m.device)
+            mss, Pss = _new_output(tuple(m.shape), m.device, 'mss'), _new_output(tuple(P.shape), P.device, 'Pss')
+            err = _new_output((B,), m.device, 'junction_err')
             rc = _timed('smoother', lambda: lib.cgp_smoother_time_split(ctx, int(method), C.byref(model), sig_ref, float(dt), _ptr(m), _ptr(P), B, T,
                                                                         _ptr(mss), _ptr(Pss), int(flags), segments, burn_in, _ptr(err), st))
             _check(ctx, rc, 'cgp_smoother_time_split')
@@ -743,7 +749,7 @@ def run_smoother(method, spec, sgps, gamma, dt, mfs, Pfs, flags=0, want=(True, T
             res = (_out(mss, like_numpy, squeeze), _out(Pss, like_numpy, squeeze))
             return res + (junction,) if return_junction_error else res
         if select is None:
-            mss, Pss = torch.empty_like(m), torch.empty_like(P)
+            mss, Pss = _new_output(tuple(m.shape), m.device, 'mss'), _new_output(tuple(P.shape), P.device, 'Pss')
             rc = _timed('smoother', lambda: lib.cgp_smoother(ctx, int(method), C.byref(model), sig_ref,
                                                              float(dt), _ptr(m), _ptr(P), B, T, _ptr(mss), _ptr(Pss), int(flags), st))
             _check(ctx, rc, 'cgp_smoother')
@@ -761,31 +767,30 @@ def run_smoother(method, spec, sgps, gamma, dt, mfs, Pfs, flags=0, want=(True, T
             raise ValueError(f'select: expect must be one of {sorted(_FUNCS)} (an enumerated integrand: a Python callable cannot run in a kernel)')
         want_e = func is not None and func is not False
         order = int(select.get('order', 10))
-        opts = dict(dtype=torch.float64, device=m.device)
         o = CgpSmoothOut()
         o.comp, o.func, o.order = comp, (_FUNCS[str(func)] if want_e else 0), order
         sel = {}
         for key, field in (('mean', 'comp_mean'), ('var', 'comp_var')):
             if select.get(key, False):
-                sel[key] = torch.empty((B, T), **opts)
+                sel[key] = _new_output((B, T), m.device, field)
                 setattr(o, field, _ptr(sel[key]))
         if want_e:
             xi, w = _gh_rule(order)
             xi_d, w_d = dev_const(xi), dev_const(w)
             keep += [xi_d, w_d]
-            sel['expect'] = torch.empty((B, T), **opts)
+            sel['expect'] = _new_output((B, T), m.device, 'expect')
             o.expect, o.xi, o.w = _ptr(sel['expect']), _ptr(xi_d), _ptr(w_d)
         if not sel:
             raise ValueError('select asks for none of mean / var / expect')
-        mss = torch.empty_like(m) if want[0] else None
-        Pss = torch.empty_like(P) if want[1] else None
+        mss = _new_output(tuple(m.shape), m.device, 'mss') if want[0] else None
+        Pss = _new_output(tuple(P.shape), P.device, 'Pss') if want[1] else None
         o.mss, o.Pss = _ptr(mss), _ptr(Pss)
         rc = _timed('smoother', lambda: lib.cgp_smoother_select(ctx, int(method), C.byref(model), sig_ref, float(dt), _ptr(m), _ptr(P), B, T,
                                                                 C.byref(o), int(flags), st))
         if rc == E_UNSUPPORTED and (mss is None or Pss is None):
             # a kernel that can only gather the selection from its full rows: give it (temporary) rows
-            tm = mss if mss is not None else torch.empty_like(m)
-            tP = Pss if Pss is not None else torch.empty_like(P)
+            tm = mss if mss is not None else _new_output(tuple(m.shape), m.device, 'mss (temporary)')
+            tP = Pss if Pss is not None else _new_output(tuple(P.shape), P.device, 'Pss (temporary)')
             o.mss, o.Pss = _ptr(tm), _ptr(tP)
             rc = _timed('smoother', lambda: lib.cgp_smoother_select(ctx, int(method), C.byref(model), sig_ref, float(dt), _ptr(m), _ptr(P), B, T,
                                                                     C.byref(o), int(flags), st))
@@ -849,9 +854,8 @@ def run_smoother_sample(method, spec, sgps, dt, mfs, Pfs, n_samples, seed=0, tri
             keep.append(z)
         model = _model_struct(spec, None, B, keep)
         sig = _sigma_struct(sgps, d, keep, _nonlinear_coord(spec))
-        opts = dict(dtype=torch.float64, device=m.device)
-        paths = torch.empty((B, S, T, d), **opts) if want_paths else None
-        comp_paths = torch.empty((B, S, T), **opts) if select is not None else None
+        paths = _new_output((B, S, T, d), m.device, 'paths') if want_paths else None
+        comp_paths = _new_output((B, S, T), m.device, 'comp_paths') if select is not None else None
         o.paths, o.comp_paths = _ptr(paths), _ptr(comp_paths)
         rc = _timed('sample', lambda: load_library().cgp_smoother_sample(ctx, int(method), C.byref(model), C.byref(sig) if sig is not None else None, float(dt),
                                                                          _ptr(m), _ptr(P), B, T, S, int(seed), int(trial0), int(sample0), _ptr(z),
@@ -873,7 +877,7 @@ def gaussian_expectation(ms, chol_Ps, xi, w, func=FN_SOFTPLUS):
     with torch.cuda.device(m.device):
         ctx = context(m.device.index)
         xi_d, w_d = dev(xi).reshape(-1), dev(w).reshape(-1)
-        out = torch.empty_like(m)
+        out = _new_output(tuple(m.shape), m.device, 'out')
         rc = load_library().cgp_gaussian_expectation_fn(ctx, int(func), _ptr(m), _ptr(s), m.numel(), 1, _ptr(xi_d), _ptr(w_d), xi_d.numel(),
                                                         _ptr(out), _stream())
         _check(ctx, rc, 'cgp_gaussian_expectation_fn')
@@ -936,9 +940,9 @@ def run_simulate(spec, H, Xi, m0, P0, dt, T, seed, B, trial0=0, want=(True, True
         keep = []
         model = _model_struct(spec, None, B, keep)
         init = _init_struct(H if want[1] else None, Xi if want[1] else None, m0, P0, d, B, keep)
-        opts = dict(dtype=torch.float64, device=torch.device('cuda', torch.cuda.current_device() if device is None else device))
-        xs = torch.empty((B, T, d), **opts) if want[0] else None
-        ys = torch.empty((B, T), **opts) if want[1] else None
+        on = torch.device('cuda', torch.cuda.current_device() if device is None else device)
+        xs = _new_output((B, T, d), on, 'xs') if want[0] else None
+        ys = _new_output((B, T), on, 'ys') if want[1] else None
         lib, st = load_library(), _stream()
         fl = int(flags) | (SIM_FIXED_X0 if P0 is None else 0)
         rc = _timed('simulate', lambda: lib.cgp_simulate(ctx, C.byref(model), C.byref(init), float(dt), int(seed) & (2 ** 64 - 1),
@@ -962,7 +966,7 @@ def add_noise(clean, Xi, seed, B, trial0=0):
         if Xit.numel() not in (1, B):
             raise ValueError('Xi must be a scalar or have one entry per trial')
         ctx = context(c.device.index)
-        ys = torch.empty((int(B), T), dtype=torch.float64, device=c.device)
+        ys = _new_output((int(B), T), c.device, 'ys')
         rc = _timed('add_noise', lambda: load_library().cgp_add_noise(ctx, _ptr(c), stride, _ptr(Xit), 1 if Xit.numel() > 1 else 0,
                                                                       int(seed) & (2 ** 64 - 1), int(trial0), int(B), T, _ptr(ys), _stream()))
         _check(ctx, rc, 'cgp_add_noise')

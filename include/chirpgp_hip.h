@@ -38,6 +38,12 @@
  *   - every array pointer is a DEVICE pointer owned by the caller (e.g. torch.Tensor.data_ptr()); float64,
  *     C-contiguous, batch-major: ys [B][T], mfs [B][T][d], Pfs [B][T][d][d], nll [B][T];
  *   - the library allocates nothing the caller sees and never frees caller memory; outputs are fully overwritten;
+ *   - every array needs the 8-byte alignment of a double and no more: outputs may sit anywhere (a kernel that stores two
+ *     doubles at a time takes care of it), and an input off a 16-byte boundary only moves a launch to another kernel
+ *     (the one-lane-per-trial kernels at d = 4 want 16-byte aligned ys, mfs, Pfs: cgp_route.hpp);
+ *   - nothing outside the stated extents is written, and nothing outside an input's is read: an output a call does not
+ *     ask for (a NULL pointer) is not touched, a refused call writes nothing at all (tests/test_gpu_guard_bands.py runs
+ *     every kernel between guard bands, in both alignments);
  *   - calls enqueue work on `stream` (a hipStream_t, NULL = default stream) and return without synchronising;
  *   - return value 0 = success, negative = CGP_E_* (message via cgp_last_error);
  *   - numerical breakdown (non-PD covariance in a Cholesky) is NOT an error: NaN is written where the
