@@ -62,7 +62,10 @@ EXPORTS = ('cgp_version', 'cgp_create', 'cgp_destroy', 'cgp_last_error', 'cgp_fi
            'cgp_gaussian_expectation', 'cgp_debug_math', 'cgp_simulate', 'cgp_add_noise', 'cgp_debug_philox',
            'cgp_debug_set', 'cgp_debug_counters', 'cgp_gaussian_expectation_fn', 'cgp_filter_time_split', 'cgp_squared_error_sums',
            'cgp_reserve_workspace', 'cgp_release_workspace', 'cgp_source_hash', 'cgp_smoother_select', 'cgp_ekf_nll_grad', 'cgp_sgp_nll_grad', 'cgp_ekf_nll_fisher', 'cgp_sgp_nll_fisher', 'cgp_cd_ekf_nll_grad', 'cgp_model_from_source', 'cgp_custom_model_destroy',
-           'cgp_filter_custom', 'cgp_smoother_custom', 'cgp_smoother_time_split', 'cgp_smoother_sample')
+           'cgp_filter_custom', 'cgp_smoother_custom', 'cgp_smoother_time_split', 'cgp_smoother_sample', 'cgp_pcrlb_sums')
+# tests/test_abi.py finds the header's names as cgp_[a-z_]+ and compares them with EXPORTS: a name with a digit is invisible to it and is
+# kept here (tests/test_pcrlb_host.py compares EXPORTS_ALL with the header, digits included)
+EXPORTS_ALL = EXPORTS + ('cgp_simulate_x0',)
 
 _lib = None
 _lock = threading.Lock()
@@ -136,6 +139,10 @@ def load_library():
         lib.cgp_gaussian_expectation_fn.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, C.c_int32, _vp, _vp]
         lib.cgp_squared_error_sums.restype = C.c_int
         lib.cgp_squared_error_sums.argtypes = [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _vp, _vp]
+        lib.cgp_pcrlb_sums.restype = C.c_int
+        lib.cgp_pcrlb_sums.argtypes = [_vp, C.POINTER(CgpModel), C.c_double, _vp, _vp, C.c_int64, C.c_int64, _vp, C.c_uint32, _vp]
+        lib.cgp_simulate_x0.restype = C.c_int
+        lib.cgp_simulate_x0.argtypes = [_vp, C.POINTER(CgpModel), C.POINTER(CgpInit), C.c_uint64, C.c_int64, C.c_int64, _vp, _vp]
         lib.cgp_debug_math.restype = C.c_int
         lib.cgp_debug_math.argtypes = [_vp, C.c_int, _vp, C.c_int64, _vp, _vp, _vp]
         lib.cgp_simulate.restype = C.c_int
@@ -1044,3 +1051,60 @@ def squared_error_sums(a, r, comps, sums=None):
             rc = load_library().cgp_squared_error_sums(ctx, _ptr(a[lo:hi]), _ptr(r[lo:hi]), hi - lo, T, d, arr, len(comps), _ptr(sums), _stream())
             _check(ctx, rc, 'cgp_squared_error_sums')
     return sums
+
+
+def pcrlb_rows(d):
+    """K = d (d + 1) / 2 + d d: the rows of cgp_pcrlb_sums' output (packed lower triangle of D11, then D12 row-major)."""
+    return d * (d + 1) // 2 + d * d
+
+
+def run_pcrlb_sums(spec, dt, x0, xs, sums=None, flags=0):
+    """cgp_pcrlb_sums: the Monte-Carlo sums of the posterior Cramer-Rao recursion's D11 and D12 blocks over the trials of x0 (B, d) and
+    xs (B, T, d), added into the (K, T) device tensor `sums` (a fresh zeroed one unless passed) -- include/chirpgp_hip.h."""
+    torch = _torch()
+    d = _check_dimension(spec)
+    xs = dev(xs)
+    x0 = dev(x0, xs.device.index)
+    if x0.device != xs.device:
+        x0 = x0.to(xs.device)
+    if xs.ndim != 3 or xs.shape[2] != d or tuple(x0.shape) != (xs.shape[0], d):
+        raise ValueError(f'xs must be (B, T, {d}) and x0 (B, {d}); got {tuple(xs.shape)}, {tuple(x0.shape)}')
+    B, T = int(xs.shape[0]), int(xs.shape[1])
+    K = pcrlb_rows(d)
+    with torch.cuda.device(xs.device):
+        ctx = context(xs.device.index)
+        if sums is None:
+            sums = _new_output((K, T), xs.device, 'sums').zero_()
+        elif (not _is_torch(sums) or tuple(sums.shape) != (K, T) or not sums.is_contiguous() or sums.dtype != torch.float64
+              or not sums.is_cuda or sums.device != xs.device):
+            # the kernel adds float64 atomically through the raw pointer: anything else is a wrong result or a fault
+            raise ValueError(f'sums must be a contiguous float64 ({K}, {T}) tensor on {xs.device}')
+        keep = []
+        model = _model_struct(spec, None, 1, keep)
+        lib = load_library()
+        for lo in range(0, max(B, 1), 65535 * 512):                    # the kernel's grid limit: slabs of 512 trials
+            hi = min(B, lo + 65535 * 512)
+            rc = _timed('pcrlb_sums', lambda: lib.cgp_pcrlb_sums(ctx, C.byref(model), float(dt), _ptr(x0[lo:hi]), _ptr(xs[lo:hi]), hi - lo, T,
+                                                                 _ptr(sums), int(flags), _stream()))
+            _check(ctx, rc, 'cgp_pcrlb_sums')
+    return sums
+
+
+def run_simulate_x0(d, m0, P0, seed, B, trial0=0, device=None):
+    """cgp_simulate_x0: the (B, d) initial samples x_0 = m0 + chol(P0) z that run_simulate draws for trials trial0 .. trial0 + B - 1."""
+    torch = _torch()
+    d, B = int(d), int(B)
+    if not 1 <= d <= 8:
+        raise NotImplementedError(f'state dimension {d} outside 1..8 is not compiled into cgp_simulate_x0')
+    with torch.cuda.device(torch.cuda.current_device() if device is None else device):
+        ctx = context(device)
+        keep = []
+        model = CgpModel()
+        model.model_id, model.d = M_LINEAR, d
+        init = _init_struct(None, None, m0, P0, d, B, keep)
+        on = torch.device('cuda', torch.cuda.current_device() if device is None else device)
+        x0 = _new_output((B, d), on, 'x0')
+        rc = _timed('simulate_x0', lambda: load_library().cgp_simulate_x0(ctx, C.byref(model), C.byref(init), int(seed) & (2 ** 64 - 1), int(trial0), B,
+                                                                          _ptr(x0), _stream()))
+        _check(ctx, rc, 'cgp_simulate_x0')
+        return x0

@@ -6,6 +6,7 @@
 #include "cgp_kernels.hpp"
 #include "cgp_ctx.hpp"
 #include "cgp_sample4.hpp"
+#include "cgp_pcrlb.hpp"
 
 namespace cgp {
 
@@ -697,6 +698,45 @@ int cgp_squared_error_sums(cgp_ctx* ctx, const double* a, const double* r, int64
     if (slabs > 65535) return fail(ctx, CGP_E_ARG, "more than 65535 x 512 trials in one call: reduce chunk by chunk");
     hipLaunchKernelGGL(squared_error_sums_kernel, dim3((unsigned)((T + 63) / 64), (unsigned)slabs), dim3(256), 0, (hipStream_t)stream, a, r, B, T, (int)d, ec, sums);
     return hipGetLastError() == hipSuccess ? CGP_OK : fail(ctx, CGP_E_HIP, "kernel launch failed");
+}
+
+int cgp_pcrlb_sums(cgp_ctx* ctx, const cgp_model* model, double dt, const double* x0, const double* xs, int64_t B, int64_t T,
+                   double* sums, uint32_t flags, void* stream) {
+    if (!ctx) return CGP_E_ARG;
+    if (B < 0 || T < 0) return fail(ctx, CGP_E_ARG, "negative B or T");
+    if (flags) {
+        const uint32_t bit = flags & (~flags + 1u);                        // the lowest bit set
+        char hex[16];
+        snprintf(hex, sizeof hex, "0x%x", (unsigned)bit);
+        return fail(ctx, CGP_E_ARG, std::string("cgp_pcrlb_sums takes no flag: bit ") + hex + " (" + sample_flag_name(bit) + ") is set");
+    }
+    if (B == 0 || T == 0) return CGP_OK;                                   // nothing to add
+    if (!model || !model->params) return fail(ctx, CGP_E_ARG, "model or model.params is NULL");
+    if (!x0 || !xs || !sums) return fail(ctx, CGP_E_ARG, "NULL pointer: x0, xs and sums are all needed");
+    if (model->model_id == CGP_M_LASCALA_LCD)
+        return fail(ctx, CGP_E_UNSUPPORTED, "cgp_pcrlb_sums: the transition of CGP_M_LASCALA_LCD has a singular Sigma and so no density to differentiate");
+    if (model->model_id != CGP_M_LINEAR && model->model_id != CGP_M_HARMONIC_LCD)
+        return fail(ctx, CGP_E_UNSUPPORTED, "cgp_pcrlb_sums takes CGP_M_LINEAR and CGP_M_HARMONIC_LCD: a Gaussian transition with a constant Sigma and a linear measurement");
+    if (const int rc = check_model(ctx, model, false, false, nullptr)) return rc;
+    if (model->param_stride != 0) return fail(ctx, CGP_E_ARG, "cgp_pcrlb_sums: model.param_stride must be 0 (the expectation is over the samples of ONE model)");
+    const int key = model->model_id == CGP_M_LINEAR ? model->d : model->n_harm;
+    if (model->d > 8) return fail(ctx, CGP_E_UNSUPPORTED, "cgp_pcrlb_sums is compiled for d <= 8 (CGP_M_HARMONIC_LCD: n_harm <= 3)");
+    DeviceScope on_device(ctx->device);
+    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
+    if ((B + kPcrlbSlab - 1) / kPcrlbSlab > 65535) return fail(ctx, CGP_E_ARG, "more than 65535 x 512 trials in one call: accumulate chunk by chunk");
+    PcrlbIO io;
+    io.x0 = x0; io.xs = xs; io.B = B; io.T = T; io.sums = sums;
+    ModelArgs ma;
+    ma.params = model->params; ma.param_stride = 0;
+    ma.gamma = nullptr; ma.gamma_stride = 0;
+    ma.model_id = model->model_id;
+    ma.sg.xi = nullptr; ma.sg.w = nullptr; ma.sg.s = 0; ma.sg.group_start = nullptr; ma.sg.n_groups = 0;
+    ma.sg.lds_xi = 0; ma.sg.lds_w = 0; ma.sg.lds_gs = 0; ma.sg.flags = 0;
+    ma.dt = dt;
+    const int rc = dispatch_pcrlb(model->model_id, key, io, ma, (hipStream_t)stream);
+    if (rc == CGP_E_UNSUPPORTED) return fail(ctx, rc, "cgp_pcrlb_sums: this (model, dimension) combination is not compiled in");
+    if (rc == CGP_E_HIP) return fail(ctx, rc, "kernel launch failed");
+    return rc;
 }
 
 int cgp_debug_math(cgp_ctx* ctx, int op, const double* x, int64_t n, double* out0, double* out1, void* stream) {

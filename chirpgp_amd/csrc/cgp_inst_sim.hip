@@ -1,4 +1,4 @@
-// Input side of the path: cgp_simulate, cgp_add_noise and the Philox test hook.
+// Input side of the path: cgp_simulate, cgp_simulate_x0, cgp_add_noise and the Philox test hook.
 #include "cgp_simulate.hpp"
 #include "cgp_ctx.hpp"
 
@@ -20,6 +20,28 @@ int dispatch_simulate(int model_id, int key, bool wave, const SimIO& io, const M
     case 1: return launch_simulate<HarmonicLCD<1>>(wave, io, ma, st);
     case 2: return launch_simulate<HarmonicLCD<2>>(wave, io, ma, st);
     case 3: return launch_simulate<HarmonicLCD<3>>(wave, io, ma, st);
+    default: return CGP_E_UNSUPPORTED;
+    }
+}
+
+template <int D>
+static int launch_x0(const double* m0, int64_t m0_stride, const double* P0, int64_t P0_stride, uint64_t seed, int64_t trial0, int64_t B,
+                     double* x0, hipStream_t st) {
+    hipLaunchKernelGGL((simulate_x0_kernel<D>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, m0, m0_stride, P0, P0_stride, seed, trial0, B, x0);
+    return hip_rc(hipGetLastError());
+}
+
+int dispatch_simulate_x0(int d, const double* m0, int64_t m0_stride, const double* P0, int64_t P0_stride, uint64_t seed, int64_t trial0,
+                         int64_t B, double* x0, hipStream_t st) {
+    switch (d) {
+    case 1: return launch_x0<1>(m0, m0_stride, P0, P0_stride, seed, trial0, B, x0, st);
+    case 2: return launch_x0<2>(m0, m0_stride, P0, P0_stride, seed, trial0, B, x0, st);
+    case 3: return launch_x0<3>(m0, m0_stride, P0, P0_stride, seed, trial0, B, x0, st);
+    case 4: return launch_x0<4>(m0, m0_stride, P0, P0_stride, seed, trial0, B, x0, st);
+    case 5: return launch_x0<5>(m0, m0_stride, P0, P0_stride, seed, trial0, B, x0, st);
+    case 6: return launch_x0<6>(m0, m0_stride, P0, P0_stride, seed, trial0, B, x0, st);
+    case 7: return launch_x0<7>(m0, m0_stride, P0, P0_stride, seed, trial0, B, x0, st);
+    case 8: return launch_x0<8>(m0, m0_stride, P0, P0_stride, seed, trial0, B, x0, st);
     default: return CGP_E_UNSUPPORTED;
     }
 }
@@ -77,6 +99,21 @@ int cgp_simulate(cgp_ctx* ctx, const cgp_model* model, const cgp_init* init, dou
     const int rc = dispatch_simulate(model->model_id, key, wave, io, ma, (hipStream_t)stream);
     if (rc == CGP_E_UNSUPPORTED) return fail(ctx, rc, "this (model, dimension) combination is not compiled in");
     if (rc == CGP_E_HIP) return fail(ctx, rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+int cgp_simulate_x0(cgp_ctx* ctx, const cgp_model* model, const cgp_init* init, uint64_t seed, int64_t trial0, int64_t B, double* x0, void* stream) {
+    if (!ctx) return CGP_E_ARG;
+    if (B < 0 || trial0 < 0) return fail(ctx, CGP_E_ARG, "negative B or trial0");
+    if (B == 0) return CGP_OK;
+    if (!model) return fail(ctx, CGP_E_ARG, "model is NULL (its d is the state dimension)");
+    if (!init || !init->m0 || !init->P0) return fail(ctx, CGP_E_ARG, "init.m0 / P0 must be set");
+    if (!x0) return fail(ctx, CGP_E_ARG, "x0 is NULL");
+    if (model->d < 1 || model->d > 8) return fail(ctx, CGP_E_UNSUPPORTED, "cgp_simulate_x0: state dimension outside 1..8");
+    DeviceScope on_device(ctx->device);
+    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
+    const int rc = dispatch_simulate_x0(model->d, init->m0, init->m0_stride, init->P0, init->P0_stride, seed, trial0, B, x0, (hipStream_t)stream);
+    if (rc == CGP_E_HIP) return fail(ctx, rc, "kernel launch failed");
     return rc;
 }
 

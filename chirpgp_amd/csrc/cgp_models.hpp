@@ -376,6 +376,30 @@ template <int NH> struct HarmonicLCD {
         Pp(3, 2) = fma(MM[3], C00, fma(MM[4], C10, fma(MM[5], C11, MS[1])));
         Pp(3, 3) = fma(MM[6], C00, fma(MM[7], C10, fma(MM[8], C11, MS[2])));
     }
+    // The second-order term of the posterior Cramer-Rao sums (cgp_pcrlb.hpp, where the entries are written out): sum_i w_i Hess f_i(u) with
+    // w = Sigma^-1 (x - f(u)), of which only the pairs' part (x - f) / q counts -- Hess f_i = 0 for the Matern rows.  hv[j] = its entry
+    // (j, IV), j < 2 NH; hvv = its entry (IV, IV); every other entry is zero.  Also out, the pieces of J it shares: (c, s) = rho (cos, sin)
+    // (theta_k) and jv = d f / d u_v.  Full-accuracy softplus and sin / cos: simulated frequency states sit in no lean regime.
+    CGP_DEV void hessian_contract(const Vec<D>& u, const Vec<D>& x, double inv_q, double (&c)[NH], double (&s)[NH], double (&jv)[2 * NH],
+                                  double (&hv)[2 * NH], double& hvv) const {
+        double sp, dsp;
+        softplus_pair(u.v[IV], sp, dsp);
+        rotations((kTwoPi * sp) * fs, c, s);
+        const double d1 = ((kTwoPi * fs) * dt) * dsp, d2 = d1 * (1.0 - dsp);      // theta_0' and theta_0'': g'' = g' (1 - g')
+        hvv = 0.0;
+        CGP_UNROLL for (int k = 0; k < NH; k++) {
+            const double u0 = u.v[2 * k], u1 = u.v[2 * k + 1];
+            const double f0 = fma(c[k], u0, -(s[k] * u1)), f1 = fma(s[k], u0, c[k] * u1);
+            const double th1 = (double)(k + 1) * d1, th2 = (double)(k + 1) * d2;
+            jv[2 * k] = -(th1 * f1);
+            jv[2 * k + 1] = th1 * f0;
+            const double w0 = inv_q * (x.v[2 * k] - f0), w1 = inv_q * (x.v[2 * k + 1] - f1);
+            hv[2 * k] = th1 * fma(c[k], w1, -(s[k] * w0));
+            hv[2 * k + 1] = -(th1 * fma(c[k], w0, s[k] * w1));
+            const double t11 = th1 * th1;
+            hvv = fma(w0, -fma(th2, f1, t11 * f0), fma(w1, fma(th2, f0, -(t11 * f1)), hvv));
+        }
+    }
     CGP_DEV void add_sigma(Sym<D>& S, double w) const {
         CGP_UNROLL for (int i = 0; i < IV; i++) S(i, i) = fma(w, q, S(i, i));
         S(IV, IV) = fma(w, MS[0], S(IV, IV));

@@ -243,6 +243,25 @@ inline int launch_simulate(bool wave, const SimIO& io, const ModelArgs& ma, hipS
     return hip_rc(hipGetLastError());
 }
 
+// x_0 = m0 + chol(P0) z of trials trial0 .. trial0 + B - 1, with the operations of SimSetup::init: one thread per trial
+template <int D>
+__global__ void __launch_bounds__(256) simulate_x0_kernel(const double* __restrict__ m0, int64_t m0_stride, const double* __restrict__ P0,
+                                                          int64_t P0_stride, uint64_t seed, int64_t trial0, int64_t B, double* __restrict__ x0) {
+    const int64_t trial = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (trial >= B) return;
+    Vec<D> x, inv;
+    Sym<D> P, L;
+    load_vec<D>(m0 + trial * m0_stride, x);
+    load_sym<D>(P0 + trial * P0_stride, P);
+    cholesky<D>(P, L, inv);
+    double z[D + (D & 1)];
+    draw_state_noise<D>(seed, (uint64_t)(trial0 + trial), 0u, kStreamInit, z);
+    add_lower_matvec<D>(L, z, x);
+    CGP_UNROLL for (int i = 0; i < D; i++) x0[trial * D + i] = x.v[i];
+}
+
 int dispatch_simulate(int model_id, int key, bool wave, const SimIO&, const ModelArgs&, hipStream_t);
+int dispatch_simulate_x0(int d, const double* m0, int64_t m0_stride, const double* P0, int64_t P0_stride, uint64_t seed, int64_t trial0,
+                         int64_t B, double* x0, hipStream_t);
 
 }  // namespace cgp

@@ -17,7 +17,7 @@ __all__ = ['g', 'g_inv', 'DiscreteModel', 'DriftModel', 'Dispersion', 'Measureme
            'linear_cond_m_cov', 'linear_sde',
            'model_chirp', 'model_harmonic_chirp', 'model_lascala',
            'disc_chirp_lcd', 'disc_harmonic_chirp_lcd', 'disc_model_lascala_lcd', 'disc_m32',
-           'build_chirp_model', 'build_harmonic_chirp_model', 'build_lascala_model', 'build_kpt_chirp_model']
+           'build_chirp_model', 'build_harmonic_chirp_model', 'build_lascala_model', 'build_kpt_chirp_model', 'posterior_cramer_rao']
 
 # model ids of include/chirpgp_hip.h
 M_LINEAR, M_HARMONIC_LCD, M_LASCALA_LCD, M_LINEAR_SDE, M_HARMONIC_SDE, M_KPT = range(6)
@@ -413,3 +413,25 @@ def build_kpt_chirp_model(params, fs, num_harmonics=1):
     F[-1, 0] = 1.
     Sigma = _diag_rows([(2 * math.pi * q1 / fs) ** 2] + [q2] * n + [0.])
     return F, Sigma, m0, P0, MeasurementKPT(n)
+
+
+def posterior_cramer_rao(xss, yss, j0, cond_m_cov, H, Xi, dt):
+    """models.py:583-644: the information matrices J_1 .. J_T (T, d, d) of the posterior Cramer-Rao bound by Monte Carlo; their
+    inverses bound any estimator's error covariance.  xss (T + 1, N, d) with the initial samples first, yss (T, N): the reference's
+    time-major arrays (NumPy or device tensors).  The reference's two log-density callables are replaced by this package's
+    descriptor convention: the transition is N(mean, cov) of ``cond_m_cov`` (a discrete descriptor; a Python callable is a
+    TypeError) and the measurement is y = H . x + N(0, Xi).  yss is checked for its shape only: the Hessian of a linear
+    measurement's log-density does not depend on y.  The sums over the N samples run on the device (chirpgp_amd/crlb.py)."""
+    from chirpgp_amd import crlb, _engine as E
+    spec = crlb._descriptor(cond_m_cov, dt)
+    if xss.ndim != 3 or xss.shape[0] < 1 or xss.shape[2] != spec.d:
+        raise ValueError(f'xss must be (T + 1, N, {spec.d}); got {tuple(xss.shape)}')
+    T, N = int(xss.shape[0]) - 1, int(xss.shape[1])
+    if tuple(yss.shape) != (T, N):
+        raise ValueError(f'yss must be (T, N) = ({T}, {N}); got {tuple(yss.shape)}')
+    if E._is_torch(xss):
+        x = xss.transpose(0, 1)
+    else:
+        x = np.swapaxes(np.asarray(xss, dtype=np.float64), 0, 1)
+    sums = crlb.sums(spec, dt, x[:, 0], x[:, 1:])          # E.dev makes the trial-major copies contiguous
+    return crlb.recursion(sums, N, j0, spec, H, Xi, dt)

@@ -9,7 +9,7 @@ whatever the batch or the number of ranks."""
 import numpy as np
 import scipy.linalg
 
-__all__ = ['rmse', 'lti_sde_to_disc', 'simulate_lgssm', 'simulate_sde', 'simulate_sde_init', 'simulate_measurements']
+__all__ = ['rmse', 'lti_sde_to_disc', 'simulate_lgssm', 'simulate_sde', 'simulate_sde_init', 'simulate_measurements', 'simulate_initial']
 
 
 def rmse(x1, x2, reduce_sum=True):
@@ -60,6 +60,15 @@ def simulate_sde(m_and_cov, m0, P0, dt, T, key, const_diag_cov=False, batch=None
 def simulate_sde_init(m_and_cov, x0, dt, T, key, const_diag_cov=False, batch=None, trial0=0):
     """simulate_sde from a given x0 (tools.py:173-194)."""
     return _sim(m_and_cov, None, None, x0, None, dt, T, key, batch, trial0, (True, False))[0]
+
+
+def simulate_initial(m0, P0, key, batch, trial0=0):
+    """The initial samples x0 ~ N(m0, P0) that simulate_sde / simulate_measurements draw for trials trial0 .. trial0 + batch - 1 with
+    this key and do not return (they return x_1 .. x_T): (batch, d) on the device.  The posterior Cramer-Rao recursion's first
+    step pairs them with x_1 (``xss[:-1]`` in models.py:643)."""
+    from chirpgp_amd import _engine as E
+    d = int(np.asarray(m0).shape[-1]) if not E._is_torch(m0) else int(m0.shape[-1])
+    return E.run_simulate_x0(d, m0, P0, key, int(batch), trial0=trial0)
 
 
 def simulate_measurements(m_and_cov, H, Xi, m0, P0, dt, T, key, batch=None, trial0=0, states=True):

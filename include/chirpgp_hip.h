@@ -31,6 +31,8 @@
  *                                                                      state + measurement simulation of
  *                                                                      tetralith/jobs/crlb_ekf.py:39-58
  *   cgp_add_noise                                                      y = chirp + sqrt(Xi) N(0, 1), demos/ekfs_mle.py:33-35
+ *   cgp_pcrlb_sums                                                     posterior_cramer_rao models.py:583-644: the Monte-Carlo sums of its Hessian blocks
+ *   cgp_simulate_x0                                                    the initial samples of cgp_simulate (xss[0] of posterior_cramer_rao)
  *
  * The leading batch axis B is the reference's jax.vmap(..., in_axes=0) over ys (tetralith/jobs/crlb_ekf.py:68-72).
  *
@@ -470,6 +472,21 @@ int cgp_gaussian_expectation_fn(cgp_ctx* ctx, int func, const double* ms, const 
 int cgp_squared_error_sums(cgp_ctx* ctx, const double* a, const double* r, int64_t B, int64_t T, int32_t d,
                            const int32_t* comps, int32_t n, double* sums, void* stream);
 
+/* Monte-Carlo sums of the posterior Cramer-Rao bound (models.py:583-644, posterior_cramer_rao; the mathematics is written out in
+ * csrc/cgp_pcrlb.hpp).  For the pair x_s = (t == 0 ? x0[b] : xs[b][t-1]), x_t = xs[b][t] of every trial b and step t (0-based):
+ *     rows 0 .. d (d + 1) / 2 - 1 of sums:  the packed lower triangle (00 10 11 20 21 22 ..., as CGP_CD_DIR_DOUBLES documents it) of
+ *                                           J^T P J - sum_i w_i Hess m_i(x_s),   P = Sigma^-1, J = dm/dx at x_s, w = P (x_t - m(x_s));
+ *     the next d d rows:                    -J^T P, row-major [s][t];
+ * each summed over b into sums[row][t].  x0: [B][d], xs: [B][T][d], sums: [K][T] with K = d (d + 1) / 2 + d d (all device), ACCUMULATED
+ * into like cgp_squared_error_sums: zero it, call once per chunk of trials, all-reduce over ranks, divide by the trial count; the
+ * recursion over t is d x d host work.  An entry that does not depend on the sample is added as (trials) x (its value).
+ * Models: CGP_M_LINEAR (d <= 8) and CGP_M_HARMONIC_LCD (n_harm <= 3); anything else is CGP_E_UNSUPPORTED -- CGP_M_LASCALA_LCD because its
+ * Sigma is singular.  model.param_stride != 0, a NULL pointer and any flag bit (named in the message) are CGP_E_ARG; B == 0 or T == 0
+ * writes nothing.  A Sigma whose Cholesky breaks down (b = 0) gives NaN sums; a NaN in xs[b][t] makes every row of steps t and t + 1
+ * NaN and no other step.  The sums depend on the arrival order of the atomics in their last bits. */
+int cgp_pcrlb_sums(cgp_ctx* ctx, const cgp_model* model, double dt, const double* x0, const double* xs, int64_t B, int64_t T,
+                   double* sums, uint32_t flags, void* stream);
+
 /* ---- input side: Monte-Carlo data generated in HBM ------------------------------------
  * Random numbers are counter-based (Philox4x32-10 keyed by `seed`, counter = (global trial number, index, stream),
  * Box-Muller), so a trial's draws do not depend on B, on the launch shape or on how the batch is sharded over ranks:
@@ -482,6 +499,11 @@ int cgp_squared_error_sums(cgp_ctx* ctx, const double* a, const double* r, int64
  * flags: CGP_SIM_FIXED_X0, CGP_WAVE_PER_TRIAL, CGP_THREAD_PER_TRIAL. */
 int cgp_simulate(cgp_ctx* ctx, const cgp_model* model, const cgp_init* init, double dt, uint64_t seed, int64_t trial0,
                  int64_t B, int64_t T, double* xs, double* ys, uint32_t flags, void* stream);
+
+/* The x_0 = m0 + chol(P0) z that cgp_simulate draws for trials trial0 .. trial0 + B - 1 with this seed (cgp_simulate returns x_1 .. x_T
+ * only; cgp_pcrlb_sums' first step needs the initial samples).  model is read for its d (1 .. 8) alone; x0: [B][d] (device). */
+int cgp_simulate_x0(cgp_ctx* ctx, const cgp_model* model, const cgp_init* init, uint64_t seed, int64_t trial0, int64_t B, double* x0,
+                    void* stream);
 
 /* ys[b][k] = clean[b * clean_stride + k] + sqrt(Xi[b * Xi_stride]) e_{b,k}   (clean_stride = 0: one clean record shared
  * by all trials).  e is the measurement-noise stream of cgp_simulate. */
