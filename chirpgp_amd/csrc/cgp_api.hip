@@ -1,4 +1,6 @@
-// cgp_api.hip -- the C-ABI of include/chirpgp_hip.h: argument checks, the route (cgp_route.hpp), dispatch.
+// cgp_api.hip -- the C-ABI of include/chirpgp_hip.h.  Every entry point that launches is three steps: the null-context check, its
+// prepare_ function (cgp_args.hpp: argument checks, the route of cgp_route.hpp, the launch description -- nothing is enqueued before
+// that verdict) and launch_on (cgp_kernels.hpp) with what it enqueues: workspace, dispatch by route, fix-up and gather launches.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -9,34 +11,6 @@
 #include "cgp_pcrlb.hpp"
 
 namespace cgp {
-
-static int check_model(cgp_ctx* ctx, const cgp_model* m, bool sde, bool need_sigma, const cgp_sigma* sg) {
-    if (!m || !m->params) return fail(ctx, CGP_E_ARG, "model or model.params is NULL");
-    // dimensions above 8 are compiled in for the harmonic LCD model alone (4 and 5 harmonics: d = 10, 12)
-    const int max_d = (m->model_id == CGP_M_HARMONIC_LCD) ? CGP_MAX_D : 8;
-    if (m->d < 1 || m->d > max_d) return fail(ctx, CGP_E_UNSUPPORTED, "state dimension outside 1.." + std::to_string(max_d) + " for this model");
-    int want_params = -1, want_d = m->d;
-    switch (m->model_id) {
-    case CGP_M_LINEAR: case CGP_M_KPT: want_params = 2 * m->d * m->d; if (m->model_id == CGP_M_KPT) want_d = m->n_harm + 2; break;
-    case CGP_M_HARMONIC_LCD: want_params = 5; want_d = 2 * m->n_harm + 2; break;
-    case CGP_M_LASCALA_LCD: want_params = 2; want_d = 4; break;
-    case CGP_M_LINEAR_SDE: want_params = m->d * m->d; break;
-    case CGP_M_HARMONIC_SDE: want_params = 3; want_d = 2 * m->n_harm + 2; break;
-    default: return fail(ctx, CGP_E_ARG, "unknown model_id");
-    }
-    if (m->n_params != want_params) return fail(ctx, CGP_E_ARG, "model.n_params does not match model_id / d");
-    if (m->d != want_d) return fail(ctx, CGP_E_ARG, "model.d does not match model_id / n_harm");
-    if (m->param_stride != 0 && m->param_stride < m->n_params) return fail(ctx, CGP_E_ARG, "model.param_stride < n_params");
-    const bool is_sde = m->model_id == CGP_M_LINEAR_SDE || m->model_id == CGP_M_HARMONIC_SDE;
-    if (sde != is_sde) return fail(ctx, CGP_E_ARG, sde ? "continuous-discrete methods need an SDE model" : "discrete methods need a discrete (cond_m_cov) model");
-    if (sde && !m->gamma) return fail(ctx, CGP_E_ARG, "SDE methods need model.gamma = b b^T");
-    if (need_sigma) {
-        if (!sg || !sg->xi || !sg->w || sg->s < 1) return fail(ctx, CGP_E_ARG, "sigma-point methods need a cgp_sigma");
-        if (sg->d != m->d) return fail(ctx, CGP_E_ARG, "cgp_sigma.d != model.d");
-        if (sg->group_start && (sg->n_groups < 1 || sg->n_groups > sg->s)) return fail(ctx, CGP_E_ARG, "cgp_sigma.n_groups outside 1..s");
-    }
-    return CGP_OK;
-}
 
 template <int FN>
 __global__ void __launch_bounds__(256) gaussian_expectation_kernel(const double* __restrict__ ms, const double* __restrict__ sd,
@@ -61,7 +35,6 @@ __global__ void __launch_bounds__(256) gaussian_expectation_kernel(const double*
 // cgp_squared_error_sums: lane = time step (64 consecutive steps of a trial are one contiguous 64 d doubles), the four wavefronts of a
 // workgroup take every fourth trial of its slab of 512; per-thread sums, then LDS across the wavefronts and one float64 atomic per
 // (component, moment, step) and slab.  Reads every byte of a and r once: HBM-bound.
-struct ErrComps { int c[8]; int n; };
 __global__ void __launch_bounds__(256) squared_error_sums_kernel(const double* __restrict__ a, const double* __restrict__ r, int64_t B, int64_t T, int d,
                                                                  ErrComps comps, double* __restrict__ sums) {
     __shared__ double part[4][16][64];
@@ -102,13 +75,6 @@ __global__ void __launch_bounds__(256) smooth_select_kernel(const double* __rest
     __syncthreads();
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         sel_write(sel, ghrule, i, mss[i * d + sel.comp], Pss[i * d * d + sel.comp * (d + 1)]);
-}
-// the selected outputs of a cgp_smooth_out as the kernels take them: in their SmootherIO, or as the argument of smooth_select_kernel
-static SmoothSel smooth_sel(const cgp_smooth_out& out) {
-    SmoothSel sel;
-    sel.comp = out.comp; sel.func = out.func; sel.order = out.order;
-    sel.mean = out.comp_mean; sel.var = out.comp_var; sel.expect = out.expect; sel.xi = out.xi; sel.w = out.w;
-    return sel;
 }
 
 // Scales of the debug ops that evaluate a form with its scales folded into the coefficients (ops 14 / 15): neither is a power of two, so a
@@ -362,70 +328,33 @@ const char* cgp_last_error(const cgp_ctx* ctx) {
     return e.ctx == ctx ? e.msg.c_str() : "";
 }
 
-static int filter_impl(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init,
-                       double dt, const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index,
-                       int64_t B, int64_t T, double* mfs, double* Pfs, double* nll, uint32_t flags, void* stream,
-                       int64_t segments, int64_t burn_in, double* junction_err) {
-    if (!ctx) return CGP_E_ARG;
-    if (B < 0 || T < 0) return fail(ctx, CGP_E_ARG, "negative B or T");
-    if (B == 0 || T == 0) return CGP_OK;
-    if (!ys) return fail(ctx, CGP_E_ARG, "ys is NULL");
-    if (ys_stride < 0) return fail(ctx, CGP_E_ARG, "ys_stride must be >= 0 (T for dense [B][T] records, 0 for one shared record)");
-    if (ys_repeat < 1) return fail(ctx, CGP_E_ARG, "ys_repeat must be >= 1");
-    if (!init || !init->Xi || !init->m0 || !init->P0) return fail(ctx, CGP_E_ARG, "init.Xi / m0 / P0 must be set");
-    if (method != CGP_F_EKF_KPT && !init->H) return fail(ctx, CGP_E_ARG, "init.H must be set");
-    const bool sde = method == CGP_F_CD_EKF || method == CGP_F_CD_SGP;
-    const bool sig = method == CGP_F_SGP || method == CGP_F_CD_SGP;
-    if (method < CGP_F_EKF || method > CGP_F_EKF_KPT) return fail(ctx, CGP_E_ARG, "unknown filter method");
-    int rc = check_model(ctx, model, sde, sig, sigma);
-    if (rc != CGP_OK) return rc;
-    if ((method == CGP_F_EKF_KPT) != (model->model_id == CGP_M_KPT)) return fail(ctx, CGP_E_ARG, "CGP_F_EKF_KPT goes with CGP_M_KPT only");
-    DeviceScope on_device(ctx->device);
-    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
-    // One call's launches are enqueued as a unit: the per-stream scratch of the time-split forms (memset, kernel, fix-up) is protected by
-    // stream order only if two host threads that share this context AND a stream cannot interleave their launches.
-    std::lock_guard<std::recursive_mutex> launches(ctx->launch_mutex);
+}  // extern "C"
 
-    FilterIO io;
-    io.H = init->H; io.H_stride = init->H_stride;
-    io.Xi = init->Xi; io.Xi_stride = init->Xi_stride;
-    io.m0 = init->m0; io.m0_stride = init->m0_stride;
-    io.P0 = init->P0; io.P0_stride = init->P0_stride;
-    io.ys = ys; io.ys_stride = ys_stride; io.ys_repeat = ys_repeat; io.ys_index = ys_index; io.B = B; io.T = T; io.mfs = mfs; io.Pfs = Pfs; io.nll = nll; io.flags = flags;
-    io.counters = ctx->counters;
-    const ModelArgs ma = model_args(model, sigma, dt, flags);
-    const bool split = segments > 1;
-    if (split) {
-        if (burn_in < 0) return fail(ctx, CGP_E_ARG, "burn_in must be >= 0");
-        if (!junction_err) return fail(ctx, CGP_E_ARG, "junction_err must be set: a time-split filter is only as good as its junctions");
+// The enqueue half of cgp_filter / cgp_filter_time_split: the workspace of the segment records and its NaN fill, the routed kernel, the
+// fix-up pass (or, where nothing was split, a junction_err of zeros).
+static Verdict enqueue_filter(cgp_ctx* ctx, const FilterCall& c, FilterPlan& p, hipStream_t st) {
+    FilterIO& io = p.io;
+    const ModelArgs& ma = p.ma;
+    const FilterDecision& route = p.route;
+    const cgp_model* model = c.model;
+    if (io.segs > 1) {
+        const size_t seg_doubles = (size_t)io.seg_stride * (size_t)io.B * (size_t)io.segs;
+        double* seg_ws = (double*)ctx_workspace(ctx, st, sizeof(double) * seg_doubles);
+        if (!seg_ws) return {CGP_E_HIP, "no workspace for the segment records (allocation failed, or the buffer would grow inside a graph capture: cgp_reserve_workspace first)"};
+        // NaN-filled: a kernel that ignored the segments would show as junction_err = inf, not as garbage
+        if (hipMemsetAsync(seg_ws, 0xFF, sizeof(double) * seg_doubles, st) != hipSuccess) return {CGP_E_HIP, "hipMemsetAsync of the segment records failed"};
+        io.seg_state = seg_ws;
     }
-    const FilterDecision route = route_filter({method, model, sigma, &io, &ma, flags, segments, ctx->num_cus});
-    if (route.rc != CGP_OK) return fail(ctx, route.rc, route.message);
-    const bool wave = route.wave;
-    hipStream_t st = (hipStream_t)stream;
-    io.flags = route.flags;
-    if (split) {
-        // time-split with burn-in (cgp_filter_time_split): segments of whole 64-step chunks, one wavefront each
-        io.segs = route.segs; io.seg_len = route.seg_len; io.burn_in = (burn_in + 63) / 64 * 64;
-        io.seg_stride = seg_layout(model->d).stride;
-        if (io.segs > 1) {
-            const size_t seg_doubles = (size_t)io.seg_stride * (size_t)B * (size_t)io.segs;
-            double* seg_ws = (double*)ctx_workspace(ctx, st, sizeof(double) * seg_doubles);
-            if (!seg_ws) return fail(ctx, CGP_E_HIP, "no workspace for the segment records (allocation failed, or the buffer would grow inside a graph capture: cgp_reserve_workspace first)");
-            // NaN-filled: a kernel that ignored the segments would show as junction_err = inf, not as garbage
-            if (hipMemsetAsync(seg_ws, 0xFF, sizeof(double) * seg_doubles, st) != hipSuccess) return fail(ctx, CGP_E_HIP, "hipMemsetAsync of the segment records failed");
-            io.seg_state = seg_ws;
-        }
-    }
+    int rc = CGP_OK;
     switch (route.route) {
     case FilterRoute::kGenericWave:
     case FilterRoute::kGenericLane:
         switch (model->model_id) {
-        case CGP_M_LINEAR:       rc = dispatch_filter_disc_linear(method, model->d, wave, io, ma, st); break;
+        case CGP_M_LINEAR:       rc = dispatch_filter_disc_linear(c.method, model->d, route.wave, io, ma, st); break;
         case CGP_M_HARMONIC_LCD:
-        case CGP_M_LASCALA_LCD:  rc = dispatch_filter_disc_harm(method, model->n_harm, wave, io, ma, st); break;
-        case CGP_M_LINEAR_SDE:   rc = dispatch_filter_sde_linear(method, model->d, wave, io, ma, st); break;
-        case CGP_M_HARMONIC_SDE: rc = dispatch_filter_sde_harm(method, model->n_harm, wave, io, ma, st); break;
+        case CGP_M_LASCALA_LCD:  rc = dispatch_filter_disc_harm(c.method, model->n_harm, route.wave, io, ma, st); break;
+        case CGP_M_LINEAR_SDE:   rc = dispatch_filter_sde_linear(c.method, model->d, route.wave, io, ma, st); break;
+        case CGP_M_HARMONIC_SDE: rc = dispatch_filter_sde_harm(c.method, model->n_harm, route.wave, io, ma, st); break;
         default: rc = CGP_E_ARG;
         }
         break;
@@ -437,7 +366,7 @@ static int filter_impl(cgp_ctx* ctx, int method, const cgp_model* model, const c
     case FilterRoute::kSgp4Mfma:    rc = route.gaps ? dispatch_filter_mfma4_sgp_gaps(io, ma, st) : dispatch_filter_mfma4_sgp(io, ma, st); break;
     case FilterRoute::kSgp4Coop:    rc = dispatch_filter_coop4_sgp(io, ma, st); break;
     case FilterRoute::kLane4Ekf:
-    case FilterRoute::kLane4Sgp:    rc = dispatch_filter_lane4(method, io, ma, st); break;
+    case FilterRoute::kLane4Sgp:    rc = dispatch_filter_lane4(c.method, io, ma, st); break;
     case FilterRoute::kEkf8Coop:    rc = dispatch_filter_coop8_ekf(model->n_harm, io, ma, st); break;
     case FilterRoute::kSgp8Coop:    rc = dispatch_filter_coop8_sgp(model->n_harm, io, ma, st); break;
     case FilterRoute::kCdEkf4Mfma:  rc = route.gaps ? dispatch_filter_mfma4_cdekf_gaps(io, ma, st) : dispatch_filter_mfma4_cdekf(io, ma, st); break;
@@ -445,85 +374,32 @@ static int filter_impl(cgp_ctx* ctx, int method, const cgp_model* model, const c
     case FilterRoute::kCdSgp4Mfma:  rc = route.gaps ? dispatch_filter_mfma4_cdsgp_gaps(io, ma, st) : dispatch_filter_mfma4_cdsgp(io, ma, st); break;
     case FilterRoute::kCdSgp4Coop:  rc = dispatch_filter_coop4_cdsgp(io, ma, st); break;
     case FilterRoute::kKpt8Coop:    rc = dispatch_filter_kpt8(model->n_harm, io, ma, st); break;
-    case FilterRoute::kGenericKpt:  rc = dispatch_filter_kpt(model->n_harm, wave, io, ma, st); break;
+    case FilterRoute::kGenericKpt:  rc = dispatch_filter_kpt(model->n_harm, route.wave, io, ma, st); break;
     }
-    if (split) {
-        if (rc == CGP_OK) {
-            if (io.segs > 1) hipLaunchKernelGGL(filter_split_fixup_kernel, dim3((unsigned)B), dim3(64), 0, st, io, model->d, junction_err);
-            else if (hipMemsetAsync(junction_err, 0, sizeof(double) * (size_t)B, st) != hipSuccess) rc = CGP_E_HIP;
-        }
+    if (rc == CGP_OK && c.junction_err) {
+        if (io.segs > 1) {
+            hipLaunchKernelGGL(filter_split_fixup_kernel, dim3((unsigned)io.B), dim3(64), 0, st, io, model->d, c.junction_err);
+            rc = hip_rc(hipGetLastError());
+        } else rc = hip_rc(hipMemsetAsync(c.junction_err, 0, sizeof(double) * (size_t)io.B, st));      // nothing was split: no junction, no mismatch
     }
-    return launch_result(ctx, rc);
+    return rc;
 }
 
-int cgp_filter(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init,
-               double dt, const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index,
-               int64_t B, int64_t T, double* mfs, double* Pfs, double* nll, uint32_t flags, void* stream) {
-    return filter_impl(ctx, method, model, sigma, init, dt, ys, ys_stride, ys_repeat, ys_index, B, T, mfs, Pfs, nll, flags, stream, 1, 0, nullptr);
-}
-
-int cgp_filter_time_split(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init,
-                          double dt, const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index,
-                          int64_t B, int64_t T, double* mfs, double* Pfs, double* nll, uint32_t flags,
-                          int64_t segments, int64_t burn_in, double* junction_err, void* stream) {
-    if (ctx && segments < 1) return fail(ctx, CGP_E_ARG, "segments must be >= 1");
-    if (ctx && (flags & CGP_SKIP_MISSING))
-        return fail(ctx, CGP_E_UNSUPPORTED, "CGP_SKIP_MISSING goes with cgp_filter and cgp_filter_custom only: a time-split filter's burn-in that starts "
-                                            "inside a gap has no junction to compare");
-    if (ctx && segments == 1 && junction_err && B > 0) {                 // nothing is split: no junction, no mismatch
-        DeviceScope on_device(ctx->device);
-        if (!on_device.ok || hipMemsetAsync(junction_err, 0, sizeof(double) * (size_t)B, (hipStream_t)stream) != hipSuccess) return fail(ctx, CGP_E_HIP, "hipMemsetAsync failed");
-    }
-    return filter_impl(ctx, method, model, sigma, init, dt, ys, ys_stride, ys_repeat, ys_index, B, T, mfs, Pfs, nll, flags, stream, segments, burn_in, junction_err);
-}
-
-static int smoother_impl(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, double dt,
-                         const double* mfs, const double* Pfs, int64_t B, int64_t T, const cgp_smooth_out* out,
-                         uint32_t flags, void* stream, int64_t segments = 1, int64_t burn_in = 0, double* junction_err = nullptr) {
-    if (!ctx) return CGP_E_ARG;
-    if (B < 0 || T < 0) return fail(ctx, CGP_E_ARG, "negative B or T");
-    if (B == 0 || T == 0) return CGP_OK;
-    if (!out) return fail(ctx, CGP_E_ARG, "out is NULL");
-    double* const mss = out->mss;
-    double* const Pss = out->Pss;
-    const bool want_sel = out->comp_mean || out->comp_var || out->expect;
-    if (!mfs || !Pfs) return fail(ctx, CGP_E_ARG, "mfs / Pfs must be set");
-    if (!want_sel && (!mss || !Pss)) return fail(ctx, CGP_E_ARG, "mfs / Pfs / mss / Pss must be set");
-    if (want_sel) {
-        if (!model || out->comp < 0 || out->comp >= model->d) return fail(ctx, CGP_E_ARG, "cgp_smooth_out.comp outside 0..d-1");
-        if (out->expect && (out->func < CGP_FN_SOFTPLUS || out->func > CGP_FN_SQUARE || out->order < 1 || out->order > kGhMaxOrder || !out->xi || !out->w))
-            return fail(ctx, CGP_E_ARG, "cgp_smooth_out.expect needs func, 1 <= order <= 32, xi and w");
-    }
-    if (method < CGP_S_EKS || method > CGP_S_CD_SGP) return fail(ctx, CGP_E_ARG, "unknown smoother method");
-    const bool sde = method == CGP_S_CD_EKS || method == CGP_S_CD_SGP;
-    const bool sig = method == CGP_S_SGP || method == CGP_S_CD_SGP;
-    int rc = check_model(ctx, model, sde, sig, sigma);
-    if (rc != CGP_OK) return rc;
-    if (model->model_id == CGP_M_KPT) return fail(ctx, CGP_E_ARG, "the KPT model has no smoother in the reference");
-    DeviceScope on_device(ctx->device);
-    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
-    std::lock_guard<std::recursive_mutex> launches(ctx->launch_mutex);        // (see filter_impl: compose + apply of one call stay together)
-
-    SmootherIO io;
-    io.mfs = mfs; io.Pfs = Pfs; io.B = B; io.T = T; io.mss = mss; io.Pss = Pss; io.flags = flags;
-    const ModelArgs ma = model_args(model, sigma, dt, flags);
-    // the whole plan -- kernel, launch shape, segments, how the selected outputs get written -- decided before anything is enqueued
-    SmootherQuery query{method, model, sigma, &io, &ma, flags, ctx->num_cus};
-    query.walk_cap = ctx->walk_segments;
-    query.segments = segments; query.burn_in = burn_in;
-    query.want_sel = want_sel; query.null_rows = !mss || !Pss;
-    const SmootherDecision plan = route_smoother(query);
-    if (plan.rc != CGP_OK) return fail(ctx, plan.rc, plan.message);
+// The enqueue half of cgp_smoother / cgp_smoother_select / cgp_smoother_time_split: the workspace of the junction states, the routed kernel,
+// the fix-up pass (or a junction_err of zeros), the gather launch of selected outputs.
+static Verdict enqueue_smoother(cgp_ctx* ctx, const SmootherCall& c, SmootherPlan& p, hipStream_t st) {
+    SmootherIO& io = p.io;
+    const ModelArgs& ma = p.ma;
+    const SmootherDecision& plan = p.route;
+    const cgp_model* model = c.model;
+    const int method = c.method;
     const bool wave = plan.wave;
-    hipStream_t st = (hipStream_t)stream;
     const SmootherLaunch host{ctx, ctx->num_cus, plan.split, ctx->lane_buffers};
-    if (plan.select == SmootherSelect::kKernel) io.sel = smooth_sel(*out);
     if (plan.bsegs > 1) {
-        // time-split with burn-in (cgp_smoother_time_split): one wavefront per (trial, segment), their states at the junctions for the fix-up pass
-        io.bsegs = plan.bsegs; io.chunks_per_bseg = plan.chunks_per_bseg; io.burn_chunks = plan.burn_chunks;
-        io.junction = (double*)ctx_workspace(ctx, st, sizeof(double) * SmootherIO::kJunctionDoubles * (size_t)B * (size_t)plan.bsegs);
-        if (!io.junction) return fail(ctx, CGP_E_HIP, "no workspace for the junction states (allocation failed, or the buffer would grow inside a graph capture: cgp_reserve_workspace first)");
+        io.junction = (double*)ctx_workspace(ctx, st, sizeof(double) * SmootherIO::kJunctionDoubles * (size_t)io.B * (size_t)plan.bsegs);
+        if (!io.junction) return {CGP_E_HIP, "no workspace for the junction states (allocation failed, or the buffer would grow inside a graph capture: cgp_reserve_workspace first)"};
     }
+    int rc = CGP_OK;
     switch (plan.route) {
     case SmootherRoute::kCoop8Linear: rc = dispatch_smoother_coop8_linear(method, model->d, io, host, ma, st); break;
     case SmootherRoute::kWalk4Linear: rc = dispatch_smoother_walk4_linear(method, io, host, ma, st); break;
@@ -540,64 +416,74 @@ static int smoother_impl(cgp_ctx* ctx, int method, const cgp_model* model, const
     case SmootherRoute::kSdeHarm:     rc = dispatch_smoother_sde_harm(method, model->n_harm, wave, io, ma, st); break;
     case SmootherRoute::kNone:        rc = CGP_E_ARG; break;
     }
-    if (rc == CGP_OK && junction_err) {
+    if (rc == CGP_OK && c.junction_err) {
         if (io.bsegs > 1) {
-            hipLaunchKernelGGL(smoother_split_fixup_kernel, dim3((unsigned)B), dim3(64), 0, st, io, junction_err);
+            hipLaunchKernelGGL(smoother_split_fixup_kernel, dim3((unsigned)io.B), dim3(64), 0, st, io, c.junction_err);
             rc = hip_rc(hipGetLastError());
-        } else if (hipMemsetAsync(junction_err, 0, sizeof(double) * (size_t)B, st) != hipSuccess) rc = CGP_E_HIP;      // nothing was split: no junction, no mismatch
+        } else rc = hip_rc(hipMemsetAsync(c.junction_err, 0, sizeof(double) * (size_t)io.B, st));      // nothing was split: no junction, no mismatch
     }
     if (rc == CGP_OK && plan.select == SmootherSelect::kGather) {
-        const int64_t n = B * T, blocks = (n + 255) / 256;
-        hipLaunchKernelGGL(smooth_select_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, mss, Pss, n, model->d, smooth_sel(*out));
-        if (hipGetLastError() != hipSuccess) rc = CGP_E_HIP;
+        const int64_t n = io.B * io.T, blocks = (n + 255) / 256;
+        hipLaunchKernelGGL(smooth_select_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, io.mss, io.Pss, n, model->d, p.sel);
+        rc = hip_rc(hipGetLastError());
     }
-    return launch_result(ctx, rc);
+    return rc;
+}
+
+static int filter_entry(cgp_ctx* ctx, const FilterCall& call, void* stream) {
+    if (!ctx) return CGP_E_ARG;
+    FilterPlan plan;
+    const Verdict prepared = prepare_filter(call, host_of(ctx), plan);
+    return launch_on(ctx, prepared, kLaunchLocked, [&]() -> Verdict { return enqueue_filter(ctx, call, plan, (hipStream_t)stream); });
+}
+static int smoother_entry(cgp_ctx* ctx, const SmootherCall& call, void* stream) {
+    if (!ctx) return CGP_E_ARG;
+    SmootherPlan plan;
+    const Verdict prepared = prepare_smoother(call, host_of(ctx), plan);
+    return launch_on(ctx, prepared, kLaunchLocked, [&]() -> Verdict { return enqueue_smoother(ctx, call, plan, (hipStream_t)stream); });
+}
+// cgp_smoother and cgp_smoother_time_split write full rows: a cgp_smooth_out with nothing selected
+static cgp_smooth_out full_rows(double* mss, double* Pss) {
+    cgp_smooth_out out;
+    memset(&out, 0, sizeof(out));
+    out.mss = mss; out.Pss = Pss; out.comp = -1;
+    return out;
+}
+
+extern "C" {
+
+int cgp_filter(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init,
+               double dt, const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index,
+               int64_t B, int64_t T, double* mfs, double* Pfs, double* nll, uint32_t flags, void* stream) {
+    return filter_entry(ctx, {method, model, sigma, init, dt, ys, ys_stride, ys_repeat, ys_index, B, T, mfs, Pfs, nll, flags}, stream);
+}
+
+int cgp_filter_time_split(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init,
+                          double dt, const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index,
+                          int64_t B, int64_t T, double* mfs, double* Pfs, double* nll, uint32_t flags,
+                          int64_t segments, int64_t burn_in, double* junction_err, void* stream) {
+    return filter_entry(ctx, {method, model, sigma, init, dt, ys, ys_stride, ys_repeat, ys_index, B, T, mfs, Pfs, nll, flags, true, segments, burn_in, junction_err},
+                        stream);
 }
 
 int cgp_smoother(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, double dt,
                  const double* mfs, const double* Pfs, int64_t B, int64_t T, double* mss, double* Pss,
                  uint32_t flags, void* stream) {
-    cgp_smooth_out out;
-    memset(&out, 0, sizeof(out));
-    out.mss = mss; out.Pss = Pss; out.comp = -1;
-    return smoother_impl(ctx, method, model, sigma, dt, mfs, Pfs, B, T, &out, flags, stream);
+    const cgp_smooth_out out = full_rows(mss, Pss);
+    return smoother_entry(ctx, {method, model, sigma, dt, mfs, Pfs, B, T, &out, flags}, stream);
 }
 
 int cgp_smoother_time_split(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, double dt,
                             const double* mfs, const double* Pfs, int64_t B, int64_t T, double* mss, double* Pss,
                             uint32_t flags, int64_t segments, int64_t burn_in, double* junction_err, void* stream) {
-    if (ctx && segments < 1) return fail(ctx, CGP_E_ARG, "segments must be >= 1");
-    if (ctx && !junction_err) return fail(ctx, CGP_E_ARG, "junction_err must be set");
-    cgp_smooth_out out;
-    memset(&out, 0, sizeof(out));
-    out.mss = mss; out.Pss = Pss; out.comp = -1;
-    return smoother_impl(ctx, method, model, sigma, dt, mfs, Pfs, B, T, &out, flags, stream, segments, burn_in, junction_err);
+    const cgp_smooth_out out = full_rows(mss, Pss);
+    return smoother_entry(ctx, {method, model, sigma, dt, mfs, Pfs, B, T, &out, flags, true, segments, burn_in, junction_err}, stream);
 }
 
 int cgp_smoother_select(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, double dt,
                         const double* mfs, const double* Pfs, int64_t B, int64_t T, const cgp_smooth_out* out,
                         uint32_t flags, void* stream) {
-    return smoother_impl(ctx, method, model, sigma, dt, mfs, Pfs, B, T, out, flags, stream);
-}
-
-// The header's name of a flag bit that cgp_smoother_sample refuses (it takes none)
-static const char* sample_flag_name(uint32_t bit) {
-    switch (bit) {
-    case CGP_NLL_FINAL_ONLY: return "CGP_NLL_FINAL_ONLY";
-    case CGP_WAVE_PER_TRIAL: return "CGP_WAVE_PER_TRIAL";
-    case CGP_THREAD_PER_TRIAL: return "CGP_THREAD_PER_TRIAL";
-    case CGP_SEQUENTIAL_SCAN: return "CGP_SEQUENTIAL_SCAN";
-    case CGP_GENERIC_KERNEL: return "CGP_GENERIC_KERNEL";
-    case CGP_SIM_FIXED_X0: return "CGP_SIM_FIXED_X0";
-    case CGP_LITERAL_SIGMA_SUM: return "CGP_LITERAL_SIGMA_SUM";
-    case CGP_DPP_KERNEL: return "CGP_DPP_KERNEL";
-    case CGP_FOUR_TRIALS_PER_WAVE: return "CGP_FOUR_TRIALS_PER_WAVE";
-    case CGP_ONE_TRIAL_PER_WAVE: return "CGP_ONE_TRIAL_PER_WAVE";
-    case CGP_TIME_SPLIT: return "CGP_TIME_SPLIT";
-    case CGP_NO_TIME_SPLIT: return "CGP_NO_TIME_SPLIT";
-    case CGP_SKIP_MISSING: return "CGP_SKIP_MISSING";
-    default: return "no flag of chirpgp_hip.h";
-    }
+    return smoother_entry(ctx, {method, model, sigma, dt, mfs, Pfs, B, T, out, flags}, stream);
 }
 
 int cgp_smoother_sample(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, double dt,
@@ -605,53 +491,10 @@ int cgp_smoother_sample(cgp_ctx* ctx, int method, const cgp_model* model, const 
                         uint64_t seed, int64_t trial0, int64_t sample0, const double* normals,
                         const cgp_sample_out* out, uint32_t flags, void* stream) {
     if (!ctx) return CGP_E_ARG;
-    if (B < 0 || T < 0 || S < 0) return fail(ctx, CGP_E_ARG, "negative B, T or S");
-    if (flags) {
-        const uint32_t bit = flags & (~flags + 1u);                        // the lowest bit set
-        char hex[16];
-        snprintf(hex, sizeof hex, "0x%x", (unsigned)bit);
-        return fail(ctx, CGP_E_ARG, std::string("cgp_smoother_sample takes no flag: bit ") + hex + " (" + sample_flag_name(bit) + ") is set");
-    }
-    if (B == 0 || T == 0 || S == 0) return CGP_OK;                        // nothing to write
-    if (!out || (!out->paths && !out->comp_paths)) return fail(ctx, CGP_E_ARG, "cgp_sample_out.paths and comp_paths are both NULL: nothing to write");
-    if (method < CGP_S_EKS || method > CGP_S_CD_SGP) return fail(ctx, CGP_E_ARG, "unknown smoother method");
-    if (method == CGP_S_CD_EKS || method == CGP_S_CD_SGP)
-        return fail(ctx, CGP_E_UNSUPPORTED, "cgp_smoother_sample walks the discrete smoothers' affine maps (rts, eks, sgp_smoother): a continuous-discrete "
-                                            "smoother's backward ODE is not such a map");
-    const bool sig = method == CGP_S_SGP;
-    int rc = check_model(ctx, model, false, sig, sigma);
-    if (rc != CGP_OK) return rc;
-    const bool lcd = (model->model_id == CGP_M_HARMONIC_LCD && model->n_harm == 1) || model->model_id == CGP_M_LASCALA_LCD;
-    const bool built = model->d == 4 && (lcd || (model->model_id == CGP_M_LINEAR && method == CGP_S_EKS));
-    if (!built)
-        return fail(ctx, CGP_E_UNSUPPORTED, "cgp_smoother_sample is built for d = 4: rts on CGP_M_LINEAR, eks and sgp_smoother on CGP_M_HARMONIC_LCD with n_harm = 1 "
-                                            "and CGP_M_LASCALA_LCD");
-    if (sig && SigmaSet::stage_bytes(sigma->s, 4, 0, false) > (size_t)kSigLdsMaxBytes)
-        return fail(ctx, CGP_E_UNSUPPORTED, "the sigma-point set does not fit the LDS stage of cgp_smoother_sample");
-    if (out->comp_paths) {
-        if (out->comp < 0 || out->comp >= model->d) return fail(ctx, CGP_E_ARG, "cgp_sample_out.comp outside 0..d-1");
-        if (out->func < CGP_FN_SOFTPLUS || out->func > CGP_FN_SQUARE) return fail(ctx, CGP_E_ARG, "cgp_sample_out.func is no CGP_FN_*");
-    }
-    const uint64_t two32 = (uint64_t)1 << 32;
-    if (B > 0x7FFFFFFF) return fail(ctx, CGP_E_ARG, "B must be < 2^31 (one workgroup column per trial)");
-    if (!normals) {                                                        // the counter's words: (trial, sample, index)
-        if (trial0 < 0 || sample0 < 0) return fail(ctx, CGP_E_ARG, "negative trial0 or sample0");
-        if ((uint64_t)trial0 + (uint64_t)B > two32) return fail(ctx, CGP_E_ARG, "trial0 + B must be <= 2^32 (the trial is one word of the Philox counter)");
-        if ((uint64_t)sample0 + (uint64_t)S > two32) return fail(ctx, CGP_E_ARG, "sample0 + S must be <= 2^32 (the sample is one word of the Philox counter)");
-        if ((uint64_t)T > two32 / 2) return fail(ctx, CGP_E_ARG, "T * ceil(d / 2) must be <= 2^32 (the pair index is one word of the Philox counter)");
-    }
-    if (!mfs || !Pfs) return fail(ctx, CGP_E_ARG, "mfs / Pfs must be set");
-    DeviceScope on_device(ctx->device);
-    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
-    std::lock_guard<std::recursive_mutex> launches(ctx->launch_mutex);
-    SampleIO io;
-    io.mfs = mfs; io.Pfs = Pfs; io.normals = normals; io.B = B; io.T = T; io.S = S;
-    io.seed = seed; io.trial0 = (uint64_t)trial0; io.sample0 = (uint64_t)sample0;
-    io.paths = out->paths; io.comp_paths = out->comp_paths; io.comp = out->comp_paths ? out->comp : 0; io.func = out->func;
-    // the literal per-point sums: the kernel takes no groups, so a grouped set is staged without its group table
-    ModelArgs ma = model_args(model, sig ? sigma : nullptr, dt, CGP_LITERAL_SIGMA_SUM);
-    ma.sg.group_start = nullptr; ma.sg.n_groups = 0;
-    return launch_result(ctx, dispatch_sample4(method, model->model_id, io, ma, (hipStream_t)stream));
+    SampleIO io{};
+    ModelArgs ma;
+    const Verdict prepared = prepare_smoother_sample(method, model, sigma, dt, mfs, Pfs, B, T, S, seed, trial0, sample0, normals, out, flags, io, ma);
+    return launch_on(ctx, prepared, kLaunchLocked, [&]() -> Verdict { return dispatch_sample4(method, model->model_id, io, ma, (hipStream_t)stream); });
 }
 
 int cgp_gaussian_expectation(cgp_ctx* ctx, const double* ms, const double* sd, int64_t n, int64_t in_stride,
@@ -662,95 +505,52 @@ int cgp_gaussian_expectation(cgp_ctx* ctx, const double* ms, const double* sd, i
 int cgp_gaussian_expectation_fn(cgp_ctx* ctx, int func, const double* ms, const double* sd, int64_t n, int64_t in_stride,
                                 const double* xi, const double* w, int32_t order, double* out, void* stream) {
     if (!ctx) return CGP_E_ARG;
-    if (func < CGP_FN_SOFTPLUS || func > CGP_FN_SQUARE) return fail(ctx, CGP_E_ARG, "unknown integrand");
-    if (n < 0 || order < 1) return fail(ctx, CGP_E_ARG, "bad n or order");
-    if (n == 0) return CGP_OK;
-    if (!ms || !sd || !xi || !w || !out) return fail(ctx, CGP_E_ARG, "NULL pointer");
-    DeviceScope on_device(ctx->device);
-    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
-    const int64_t blocks = (n + 255) / 256;
-    const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048);
-    hipStream_t st = (hipStream_t)stream;
-    switch (func) {
-    case CGP_FN_EXP:      hipLaunchKernelGGL(gaussian_expectation_kernel<CGP_FN_EXP>, dim3(grid), dim3(256), 0, st, ms, sd, n, in_stride, xi, w, order, out); break;
-    case CGP_FN_IDENTITY: hipLaunchKernelGGL(gaussian_expectation_kernel<CGP_FN_IDENTITY>, dim3(grid), dim3(256), 0, st, ms, sd, n, in_stride, xi, w, order, out); break;
-    case CGP_FN_SQUARE:   hipLaunchKernelGGL(gaussian_expectation_kernel<CGP_FN_SQUARE>, dim3(grid), dim3(256), 0, st, ms, sd, n, in_stride, xi, w, order, out); break;
-    default:              hipLaunchKernelGGL(gaussian_expectation_kernel<CGP_FN_SOFTPLUS>, dim3(grid), dim3(256), 0, st, ms, sd, n, in_stride, xi, w, order, out); break;
-    }
-    return hipGetLastError() == hipSuccess ? CGP_OK : fail(ctx, CGP_E_HIP, "kernel launch failed");
+    return launch_on(ctx, prepare_gaussian_expectation(func, ms, sd, n, xi, w, order, out), kLaunchUnlocked, [&]() -> Verdict {
+        const int64_t blocks = (n + 255) / 256;
+        const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048);
+        hipStream_t st = (hipStream_t)stream;
+        switch (func) {
+        case CGP_FN_EXP:      hipLaunchKernelGGL(gaussian_expectation_kernel<CGP_FN_EXP>, dim3(grid), dim3(256), 0, st, ms, sd, n, in_stride, xi, w, order, out); break;
+        case CGP_FN_IDENTITY: hipLaunchKernelGGL(gaussian_expectation_kernel<CGP_FN_IDENTITY>, dim3(grid), dim3(256), 0, st, ms, sd, n, in_stride, xi, w, order, out); break;
+        case CGP_FN_SQUARE:   hipLaunchKernelGGL(gaussian_expectation_kernel<CGP_FN_SQUARE>, dim3(grid), dim3(256), 0, st, ms, sd, n, in_stride, xi, w, order, out); break;
+        default:              hipLaunchKernelGGL(gaussian_expectation_kernel<CGP_FN_SOFTPLUS>, dim3(grid), dim3(256), 0, st, ms, sd, n, in_stride, xi, w, order, out); break;
+        }
+        return hip_rc(hipGetLastError());
+    });
 }
 
 int cgp_squared_error_sums(cgp_ctx* ctx, const double* a, const double* r, int64_t B, int64_t T, int32_t d,
                            const int32_t* comps, int32_t n, double* sums, void* stream) {
     if (!ctx) return CGP_E_ARG;
-    if (B < 0 || T < 0 || d < 1 || n < 1 || n > 8) return fail(ctx, CGP_E_ARG, "bad B, T, d or n (1 <= n <= 8)");
-    if (B == 0 || T == 0) return CGP_OK;
-    if (!a || !r || !comps || !sums) return fail(ctx, CGP_E_ARG, "NULL pointer");
-    ErrComps ec;
-    ec.n = n;
-    for (int i = 0; i < 8; i++) {
-        ec.c[i] = i < n ? comps[i] : 0;
-        if (ec.c[i] < 0 || ec.c[i] >= d) return fail(ctx, CGP_E_ARG, "component outside 0..d-1");
-    }
-    DeviceScope on_device(ctx->device);
-    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
-    const int64_t slabs = (B + 511) / 512;
-    if (slabs > 65535) return fail(ctx, CGP_E_ARG, "more than 65535 x 512 trials in one call: reduce chunk by chunk");
-    hipLaunchKernelGGL(squared_error_sums_kernel, dim3((unsigned)((T + 63) / 64), (unsigned)slabs), dim3(256), 0, (hipStream_t)stream, a, r, B, T, (int)d, ec, sums);
-    return hipGetLastError() == hipSuccess ? CGP_OK : fail(ctx, CGP_E_HIP, "kernel launch failed");
+    ErrComps ec{};
+    return launch_on(ctx, prepare_squared_error_sums(a, r, B, T, d, comps, n, sums, ec), kLaunchUnlocked, [&]() -> Verdict {
+        hipLaunchKernelGGL(squared_error_sums_kernel, dim3((unsigned)((T + 63) / 64), (unsigned)((B + 511) / 512)), dim3(256), 0, (hipStream_t)stream, a, r, B, T,
+                           (int)d, ec, sums);
+        return hip_rc(hipGetLastError());
+    });
 }
 
 int cgp_pcrlb_sums(cgp_ctx* ctx, const cgp_model* model, double dt, const double* x0, const double* xs, int64_t B, int64_t T,
                    double* sums, uint32_t flags, void* stream) {
     if (!ctx) return CGP_E_ARG;
-    if (B < 0 || T < 0) return fail(ctx, CGP_E_ARG, "negative B or T");
-    if (flags) {
-        const uint32_t bit = flags & (~flags + 1u);                        // the lowest bit set
-        char hex[16];
-        snprintf(hex, sizeof hex, "0x%x", (unsigned)bit);
-        return fail(ctx, CGP_E_ARG, std::string("cgp_pcrlb_sums takes no flag: bit ") + hex + " (" + sample_flag_name(bit) + ") is set");
-    }
-    if (B == 0 || T == 0) return CGP_OK;                                   // nothing to add
-    if (!model || !model->params) return fail(ctx, CGP_E_ARG, "model or model.params is NULL");
-    if (!x0 || !xs || !sums) return fail(ctx, CGP_E_ARG, "NULL pointer: x0, xs and sums are all needed");
-    if (model->model_id == CGP_M_LASCALA_LCD)
-        return fail(ctx, CGP_E_UNSUPPORTED, "cgp_pcrlb_sums: the transition of CGP_M_LASCALA_LCD has a singular Sigma and so no density to differentiate");
-    if (model->model_id != CGP_M_LINEAR && model->model_id != CGP_M_HARMONIC_LCD)
-        return fail(ctx, CGP_E_UNSUPPORTED, "cgp_pcrlb_sums takes CGP_M_LINEAR and CGP_M_HARMONIC_LCD: a Gaussian transition with a constant Sigma and a linear measurement");
-    if (const int rc = check_model(ctx, model, false, false, nullptr)) return rc;
-    if (model->param_stride != 0) return fail(ctx, CGP_E_ARG, "cgp_pcrlb_sums: model.param_stride must be 0 (the expectation is over the samples of ONE model)");
-    const int key = model->model_id == CGP_M_LINEAR ? model->d : model->n_harm;
-    if (model->d > 8) return fail(ctx, CGP_E_UNSUPPORTED, "cgp_pcrlb_sums is compiled for d <= 8 (CGP_M_HARMONIC_LCD: n_harm <= 3)");
-    DeviceScope on_device(ctx->device);
-    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
-    if ((B + kPcrlbSlab - 1) / kPcrlbSlab > 65535) return fail(ctx, CGP_E_ARG, "more than 65535 x 512 trials in one call: accumulate chunk by chunk");
-    PcrlbIO io;
-    io.x0 = x0; io.xs = xs; io.B = B; io.T = T; io.sums = sums;
+    PcrlbIO io{};
     ModelArgs ma;
-    ma.params = model->params; ma.param_stride = 0;
-    ma.gamma = nullptr; ma.gamma_stride = 0;
-    ma.model_id = model->model_id;
-    ma.sg.xi = nullptr; ma.sg.w = nullptr; ma.sg.s = 0; ma.sg.group_start = nullptr; ma.sg.n_groups = 0;
-    ma.sg.lds_xi = 0; ma.sg.lds_w = 0; ma.sg.lds_gs = 0; ma.sg.flags = 0;
-    ma.dt = dt;
-    const int rc = dispatch_pcrlb(model->model_id, key, io, ma, (hipStream_t)stream);
-    if (rc == CGP_E_UNSUPPORTED) return fail(ctx, rc, "cgp_pcrlb_sums: this (model, dimension) combination is not compiled in");
-    if (rc == CGP_E_HIP) return fail(ctx, rc, "kernel launch failed");
-    return rc;
+    int key = 0;
+    return launch_on(ctx, prepare_pcrlb_sums(model, dt, x0, xs, B, T, sums, flags, io, ma, key), kLaunchUnlocked, [&]() -> Verdict {
+        const int rc = dispatch_pcrlb(model->model_id, key, io, ma, (hipStream_t)stream);
+        if (rc == CGP_E_UNSUPPORTED) return {rc, "cgp_pcrlb_sums: this (model, dimension) combination is not compiled in"};
+        return rc;
+    });
 }
 
 int cgp_debug_math(cgp_ctx* ctx, int op, const double* x, int64_t n, double* out0, double* out1, void* stream) {
     if (!ctx) return CGP_E_ARG;
-    if (n < 0 || op < 0 || op > 25) return fail(ctx, CGP_E_ARG, "bad op or n");
-    if ((op == 22 || op == 23 || op == 25) && (n & 1)) return fail(ctx, CGP_E_ARG, "a two-argument op takes an even number of inputs");
-    if (n == 0) return CGP_OK;
-    if (!x || !out0) return fail(ctx, CGP_E_ARG, "NULL pointer");
-    DeviceScope on_device(ctx->device);
-    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
-    const int64_t blocks = (n + 255) / 256;
-    if (op == 5 || op == 6 || op == 8 || op == 16 || op == 17) hipLaunchKernelGGL(debug_math_uniform_kernel, dim3((unsigned)(n < 4096 ? n : 4096)), dim3(64), 0, (hipStream_t)stream, op, x, n, out0, out1);
-    else hipLaunchKernelGGL(debug_math_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, (hipStream_t)stream, op, x, n, out0, out1);
-    return hipGetLastError() == hipSuccess ? CGP_OK : fail(ctx, CGP_E_HIP, "kernel launch failed");
+    return launch_on(ctx, prepare_debug_math(op, x, n, out0), kLaunchUnlocked, [&]() -> Verdict {
+        const int64_t blocks = (n + 255) / 256;
+        if (op == 5 || op == 6 || op == 8 || op == 16 || op == 17) hipLaunchKernelGGL(debug_math_uniform_kernel, dim3((unsigned)(n < 4096 ? n : 4096)), dim3(64), 0, (hipStream_t)stream, op, x, n, out0, out1);
+        else hipLaunchKernelGGL(debug_math_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, (hipStream_t)stream, op, x, n, out0, out1);
+        return hip_rc(hipGetLastError());
+    });
 }
 
 }  // extern "C"

@@ -219,6 +219,61 @@ struct SmootherIO {
 static_assert(__builtin_offsetof(SmootherIO, segs) == 52 && __builtin_offsetof(SmootherIO, tiles_per_seg) == 64 && __builtin_offsetof(SmootherIO, ws) == 72,
               "the walks' arguments moved: compare their register use (tools/resusage.py) before and after");
 
+// ---- the arguments of the other kernel families, next to the filters' and smoothers': the pure half of their entry points (cgp_args.hpp) fills them
+// the tangent kernels (cgp_tangent4.hpp, cgp_tangent4_sigma.hpp, cgp_tangent4_cd.hpp)
+struct TangentIO {
+    const double* __restrict__ H;  int64_t H_stride;
+    const double* __restrict__ Xi; int64_t Xi_stride;
+    const double* __restrict__ m0; int64_t m0_stride;
+    const double* __restrict__ P0; int64_t P0_stride;
+    const double* __restrict__ ys; int64_t ys_stride, ys_repeat; const int32_t* __restrict__ ys_index;
+    const double* __restrict__ dirs;     // [B][n_dir][kDirDoubles]
+    int64_t B, T;
+    int n_dir;
+    double* __restrict__ nll;            // [B]
+    double* __restrict__ grad;           // [B][n_dir]
+    double* __restrict__ fisher;         // [B][n_dir][n_dir]: the Fisher forms only (NULL otherwise)
+    __device__ __forceinline__ const double* record(int64_t trial) const {
+        int64_t g = trial;
+        if (ys_repeat > 1) g = (int64_t)((uint64_t)trial / (uint64_t)ys_repeat);
+        if (ys_index) g = ys_index[g];
+        return ys + g * ys_stride;
+    }
+};
+// cgp_simulate (cgp_simulate.hpp)
+struct SimIO {
+    const double* __restrict__ H;  int64_t H_stride;
+    const double* __restrict__ Xi; int64_t Xi_stride;
+    const double* __restrict__ m0; int64_t m0_stride;
+    const double* __restrict__ P0; int64_t P0_stride;
+    uint64_t seed;
+    int64_t trial0;
+    int64_t B, T;
+    double* __restrict__ xs;
+    double* __restrict__ ys;
+    uint32_t vec_ok;       // bit 0: xs rows may be stored as 16-byte chunks, bit 1: ys rows
+    uint32_t flags;
+};
+// cgp_smoother_sample (cgp_sample4.hpp)
+struct SampleIO {
+    const double* __restrict__ mfs;               // [B][T][4]
+    const double* __restrict__ Pfs;               // [B][T][4][4]
+    const double* __restrict__ normals;           // [B][S][T][4] or NULL: the Philox stream
+    int64_t B, T, S;
+    uint64_t seed, trial0, sample0;
+    double* __restrict__ paths;                   // [B][S][T][4] or NULL
+    double* __restrict__ comp_paths;              // [B][S][T] or NULL
+    int comp, func;
+};
+// cgp_pcrlb_sums (cgp_pcrlb.hpp)
+constexpr int kPcrlbSlab = 512;        // trials per workgroup: the atomics stay at 8 K / 512 bytes per trial-step
+struct PcrlbIO {
+    const double* __restrict__ x0;     // [B][d]
+    const double* __restrict__ xs;     // [B][T][d]
+    int64_t B, T;
+    double* __restrict__ sums;         // [d (d + 1) / 2 + d d][T], accumulated into
+};
+
 // Dynamic LDS (sized by the launch): the staged sigma-point set.  The static LDS in front of it (the 17 152-byte
 // reduction buffer) is a multiple of 16 bytes, so the base stays 16-byte aligned (cdna_hip_programming.md G17).
 CGP_DEV double* dyn_lds() {
@@ -228,19 +283,9 @@ CGP_DEV double* dyn_lds() {
 inline size_t sigma_lds_bytes(const ModelArgs& ma, int d) {
     return ma.sg.xi ? SigmaSet::stage_bytes(ma.sg.s, d, ma.sg.n_groups, ma.sg.group_start != nullptr) : 0;
 }
-// The kernels' view of the caller's model and sigma-point set (sg NULL: none; CGP_LITERAL_SIGMA_SUM: the set without its assertions)
-inline ModelArgs model_args(const cgp_model* m, const cgp_sigma* sg, double dt, uint32_t flags) {
-    ModelArgs a;
-    a.params = m->params; a.param_stride = m->param_stride;
-    a.gamma = m->gamma; a.gamma_stride = m->gamma_stride;
-    a.model_id = m->model_id;
-    a.sg.xi = sg ? sg->xi : nullptr; a.sg.w = sg ? sg->w : nullptr; a.sg.s = sg ? sg->s : 0;
-    a.sg.group_start = sg ? sg->group_start : nullptr; a.sg.n_groups = (sg && sg->group_start) ? sg->n_groups : 0;
-    a.sg.lds_xi = 0; a.sg.lds_w = 0; a.sg.lds_gs = 0; a.sg.lds_tab = 0;
-    a.sg.flags = (sg && !(flags & CGP_LITERAL_SIGMA_SUM)) ? sg->flags : 0u;
-    a.dt = dt;
-    return a;
-}
+// (the kernels' view of the caller's model and sigma-point set: model_args, cgp_args.hpp)
+// The argument structs travel by value, and the run-time-compiled models compare their sizes with this build's after loading (cgp_rtc.hip)
+static_assert(sizeof(ModelArgs) == 104 && sizeof(FilterIO) == 192 && sizeof(SmootherIO) == 144, "the kernels' argument structs changed size");
 
 // Linear scalar measurement y = H x + noise (every filter but ekf_for_kpt).
 template <int D> struct LinearMeasurement {
@@ -770,8 +815,33 @@ inline int launch_result(cgp_ctx* ctx, int rc) {
     if (rc == CGP_E_HIP) return fail(ctx, rc, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
     return rc;
 }
+// What the pure half of an entry point (prepare_..., cgp_args.hpp) says of a call, and what its enqueue half ends in: a code with the
+// message of a refusal (a literal, or text that outlives the call), "nothing to do", or go on -- launch, or go by the code alone.
+struct Verdict {
+    int rc;
+    const char* message;
+    bool empty;                   // an empty batch or record: CGP_OK without a launch
+    Verdict(int rc_ = CGP_OK, const char* message_ = nullptr, bool empty_ = false) : rc(rc_), message(message_), empty(empty_) {}
+};
+// The second half of every entry point.  A refusal leaves its message in the context, an empty call is CGP_OK; otherwise enqueue() runs
+// on the context's device and its Verdict is what the entry returns: its own message, or launch_result's for its code.  `locked`: under the
+// context's launch lock -- one call's launches are enqueued as a unit, since the per-stream scratch of the time-split forms (memset, kernel,
+// fix-up) is protected by stream order only if two host threads that share this context AND a stream cannot interleave their launches.
+constexpr bool kLaunchLocked = true, kLaunchUnlocked = false;
+template <class Enqueue>
+inline int launch_on(cgp_ctx* ctx, const Verdict& prepared, bool locked, Enqueue enqueue) {
+    if (prepared.rc != CGP_OK) return fail(ctx, prepared.rc, prepared.message ? prepared.message : "");
+    if (prepared.empty) return CGP_OK;
+    DeviceScope on_device(ctx->device);
+    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
+    std::unique_lock<std::recursive_mutex> launches(ctx->launch_mutex, std::defer_lock);
+    if (locked) launches.lock();
+    const Verdict done = enqueue();
+    return done.message ? fail(ctx, done.rc, done.message) : launch_result(ctx, done.rc);
+}
 #endif                         // __HIPCC_RTC__
 
 }  // namespace cgp
 
 #include "cgp_route.hpp"       // which of them a call runs, and the admission predicates their launchers guard with
+#include "cgp_args.hpp"        // the pure half of every entry point: checks, the route, the launch description

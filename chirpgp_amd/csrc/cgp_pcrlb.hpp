@@ -37,14 +37,7 @@
 
 namespace cgp {
 
-struct PcrlbIO {
-    const double* __restrict__ x0;     // [B][d]
-    const double* __restrict__ xs;     // [B][T][d]
-    int64_t B, T;
-    double* __restrict__ sums;         // [d (d + 1) / 2 + d d][T], accumulated into
-};
 
-constexpr int kPcrlbSlab = 512;        // trials per workgroup: the atomics stay at 8 K / 512 bytes per trial-step
 constexpr int kPcrlbGroup = 8;         // accumulator rows combined per pass through the LDS buffer
 
 // P = S^-1 of a packed symmetric positive-definite matrix by its Cholesky factor, in IEEE sqrt and division (cgp_math.hpp's cholesky

@@ -56,14 +56,15 @@ Rtc& rtc() {
     return r;
 }
 
-// (the sigma-point set as a plain point list read from global memory: no groups, no LDS stage, no closed forms)
-ModelArgs custom_args(const double* params, int64_t param_stride, const double* gamma, int64_t gamma_stride, double dt, const cgp_sigma* sg) {
-    ModelArgs ma;
-    ma.params = params; ma.param_stride = param_stride; ma.gamma = gamma; ma.gamma_stride = gamma_stride;
-    ma.model_id = -1; ma.dt = dt;
-    ma.sg.xi = sg ? sg->xi : nullptr; ma.sg.w = sg ? sg->w : nullptr; ma.sg.s = sg ? sg->s : 0; ma.sg.group_start = nullptr; ma.sg.n_groups = 0;
-    ma.sg.lds_xi = 0; ma.sg.lds_w = 0; ma.sg.lds_gs = 0; ma.sg.lds_tab = 0; ma.sg.flags = 0u;
-    return ma;
+// what the pure half needs to know of a model, with the kernel of this entry: the EKF-type one and the sigma-point one
+CustomModel custom_model(const cgp_custom_model* m, bool smoother) {
+    if (!m) return {};
+    return {true, m->kind, m->d, m->device, (smoother ? m->smoother : m->filter) != nullptr, (smoother ? m->sgp_smoother : m->sgp_filter) != nullptr};
+}
+template <class IO>
+Verdict enqueue_custom(hipFunction_t kernel, IO& io, ModelArgs& ma, void* stream) {
+    void* args[] = {&io, &ma};
+    return hip_rc(hipModuleLaunchKernel(kernel, (unsigned)((io.B + 63) / 64), 1, 1, 64, 1, 1, 0, (hipStream_t)stream, args, nullptr));
 }
 }  // namespace
 
@@ -175,57 +176,26 @@ void cgp_custom_model_destroy(cgp_custom_model* m) {
     delete m;
 }
 
+
 int cgp_filter_custom(cgp_ctx* ctx, const cgp_custom_model* m, const cgp_sigma* sigma, const double* params, int64_t param_stride, const double* gamma, int64_t gamma_stride,
                       const cgp_init* init, double dt, const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index,
                       int64_t B, int64_t T, double* mfs, double* Pfs, double* nll, uint32_t flags, void* stream) {
     if (!ctx) return CGP_E_ARG;
-    if (!m) return fail(ctx, CGP_E_ARG, "model is NULL");
-    if (B < 0 || T < 0) return fail(ctx, CGP_E_ARG, "negative B or T");
-    if (B == 0 || T == 0) return CGP_OK;
-    if (m->device != ctx->device) return fail(ctx, CGP_E_ARG, "the model was compiled for another device's context");
-    if (!ys || !params) return fail(ctx, CGP_E_ARG, "ys / params is NULL");
-    if (ys_stride < 0 || ys_repeat < 1) return fail(ctx, CGP_E_ARG, "ys_stride must be >= 0 and ys_repeat >= 1");
-    if (!init || !init->H || !init->Xi || !init->m0 || !init->P0) return fail(ctx, CGP_E_ARG, "init.H / Xi / m0 / P0 must be set");
-    if (m->kind == CGP_CUSTOM_SDE && !gamma) return fail(ctx, CGP_E_ARG, "SDE models need gamma = b b^T");
-    if (!(sigma ? m->sgp_filter : m->filter)) return fail(ctx, CGP_E_UNSUPPORTED, "a measurement function (ekf_for_kpt) has no sigma-point form");
-    DeviceScope on_device(ctx->device);
-    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
-    std::lock_guard<std::recursive_mutex> launches(ctx->launch_mutex);
-    FilterIO io;
-    io.H = init->H; io.H_stride = init->H_stride; io.Xi = init->Xi; io.Xi_stride = init->Xi_stride;
-    io.m0 = init->m0; io.m0_stride = init->m0_stride; io.P0 = init->P0; io.P0_stride = init->P0_stride;
-    io.ys = ys; io.ys_stride = ys_stride; io.ys_repeat = ys_repeat; io.ys_index = ys_index; io.B = B; io.T = T;
-    io.mfs = mfs; io.Pfs = Pfs; io.nll = nll; io.flags = flags & (CGP_NLL_FINAL_ONLY | CGP_SKIP_MISSING);
-    if (sigma && (!sigma->xi || !sigma->w || sigma->s < 1 || sigma->d != m->d)) return fail(ctx, CGP_E_ARG, "cgp_sigma needs xi, w, s >= 1 and d = the model's");
-    ModelArgs ma = custom_args(params, param_stride, gamma, gamma_stride, dt, sigma);
-    void* args[] = {&io, &ma};
-    if (hipModuleLaunchKernel(sigma ? m->sgp_filter : m->filter, (unsigned)((B + 63) / 64), 1, 1, 64, 1, 1, 0, (hipStream_t)stream, args, nullptr) != hipSuccess)
-        return fail(ctx, CGP_E_HIP, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return CGP_OK;
+    FilterIO io{};
+    ModelArgs ma;
+    const Verdict prepared = prepare_filter_custom(custom_model(m, false), sigma, params, param_stride, gamma, gamma_stride, init, dt, ys, ys_stride, ys_repeat,
+                                                   ys_index, B, T, mfs, Pfs, nll, flags, host_of(ctx), io, ma);
+    return launch_on(ctx, prepared, kLaunchLocked, [&]() -> Verdict { return enqueue_custom(sigma ? m->sgp_filter : m->filter, io, ma, stream); });
 }
 
 int cgp_smoother_custom(cgp_ctx* ctx, const cgp_custom_model* m, const cgp_sigma* sigma, const double* params, int64_t param_stride, const double* gamma, int64_t gamma_stride,
                         double dt, const double* mfs, const double* Pfs, int64_t B, int64_t T, double* mss, double* Pss, uint32_t flags, void* stream) {
     if (!ctx) return CGP_E_ARG;
-    if (!m) return fail(ctx, CGP_E_ARG, "model is NULL");
-    if (B < 0 || T < 0) return fail(ctx, CGP_E_ARG, "negative B or T");
-    if (B == 0 || T == 0) return CGP_OK;
-    if (m->device != ctx->device) return fail(ctx, CGP_E_ARG, "the model was compiled for another device's context");
-    if (!mfs || !Pfs || !mss || !Pss || !params) return fail(ctx, CGP_E_ARG, "mfs / Pfs / mss / Pss / params must be set");
-    if (m->kind == CGP_CUSTOM_SDE && !gamma) return fail(ctx, CGP_E_ARG, "SDE models need gamma = b b^T");
-    if (!(sigma ? m->sgp_smoother : m->smoother))
-        return fail(ctx, CGP_E_UNSUPPORTED, "a measurement function (ekf_for_kpt) has no smoother of its own: its dynamics are linear -- cgp_smoother with CGP_S_EKS on (F, Sigma)");
-    DeviceScope on_device(ctx->device);
-    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
-    std::lock_guard<std::recursive_mutex> launches(ctx->launch_mutex);
-    SmootherIO io;
-    io.mfs = mfs; io.Pfs = Pfs; io.B = B; io.T = T; io.mss = mss; io.Pss = Pss; io.flags = flags;
-    if (sigma && (!sigma->xi || !sigma->w || sigma->s < 1 || sigma->d != m->d)) return fail(ctx, CGP_E_ARG, "cgp_sigma needs xi, w, s >= 1 and d = the model's");
-    ModelArgs ma = custom_args(params, param_stride, gamma, gamma_stride, dt, sigma);
-    void* args[] = {&io, &ma};
-    if (hipModuleLaunchKernel(sigma ? m->sgp_smoother : m->smoother, (unsigned)((B + 63) / 64), 1, 1, 64, 1, 1, 0, (hipStream_t)stream, args, nullptr) != hipSuccess)
-        return fail(ctx, CGP_E_HIP, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return CGP_OK;
+    SmootherIO io{};
+    ModelArgs ma;
+    const Verdict prepared = prepare_smoother_custom(custom_model(m, true), sigma, params, param_stride, gamma, gamma_stride, dt, mfs, Pfs, B, T, mss, Pss, flags,
+                                                     host_of(ctx), io, ma);
+    return launch_on(ctx, prepared, kLaunchLocked, [&]() -> Verdict { return enqueue_custom(sigma ? m->sgp_smoother : m->smoother, io, ma, stream); });
 }
 
 }  // extern "C"

@@ -42,16 +42,6 @@ constexpr int kSampRec = 31;                      // G 16 (row-major) | c 4 | L 
 constexpr int kSampG = 0, kSampc = 16, kSampL = 20;
 constexpr double kSamplePivotFloor = 0x1p-40;     // a pivot <= this x the filtering variance of its component: the column is zero
 
-struct SampleIO {
-    const double* __restrict__ mfs;               // [B][T][4]
-    const double* __restrict__ Pfs;               // [B][T][4][4]
-    const double* __restrict__ normals;           // [B][S][T][4] or NULL: the Philox stream
-    int64_t B, T, S;
-    uint64_t seed, trial0, sample0;
-    double* __restrict__ paths;                   // [B][S][T][4] or NULL
-    double* __restrict__ comp_paths;              // [B][S][T] or NULL
-    int comp, func;
-};
 
 // L L^T = A under the pivot rule, `ref` the matrix whose diagonal the pivots are held against
 template <int D>

@@ -18,19 +18,6 @@
 
 namespace cgp {
 
-struct SimIO {
-    const double* __restrict__ H;  int64_t H_stride;
-    const double* __restrict__ Xi; int64_t Xi_stride;
-    const double* __restrict__ m0; int64_t m0_stride;
-    const double* __restrict__ P0; int64_t P0_stride;
-    uint64_t seed;
-    int64_t trial0;
-    int64_t B, T;
-    double* __restrict__ xs;
-    double* __restrict__ ys;
-    uint32_t vec_ok;       // bit 0: xs rows may be stored as 16-byte chunks, bit 1: ys rows
-    uint32_t flags;
-};
 
 // y += L z, L lower-triangular packed
 template <int D> CGP_DEV void add_lower_matvec(const Sym<D>& L, const double (&z)[D + (D & 1)], Vec<D>& y) {

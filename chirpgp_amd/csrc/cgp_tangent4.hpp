@@ -42,25 +42,6 @@ namespace cgp {
 constexpr int kDirDoubles = 24;      // d log rho | d q | d M (4) | d MS (3) | d Xi | d m0 (4) | d P0 (10)
 constexpr int kFisherMaxDir = CGP_FISHER_MAX_DIR;      // a Fisher row lives in registers: 2 VGPRs per slot
 
-struct TangentIO {
-    const double* __restrict__ H;  int64_t H_stride;
-    const double* __restrict__ Xi; int64_t Xi_stride;
-    const double* __restrict__ m0; int64_t m0_stride;
-    const double* __restrict__ P0; int64_t P0_stride;
-    const double* __restrict__ ys; int64_t ys_stride, ys_repeat; const int32_t* __restrict__ ys_index;
-    const double* __restrict__ dirs;     // [B][n_dir][kDirDoubles]
-    int64_t B, T;
-    int n_dir;
-    double* __restrict__ nll;            // [B]
-    double* __restrict__ grad;           // [B][n_dir]
-    double* __restrict__ fisher;         // [B][n_dir][n_dir]: the Fisher forms only (NULL otherwise)
-    __device__ __forceinline__ const double* record(int64_t trial) const {
-        int64_t g = trial;
-        if (ys_repeat > 1) g = (int64_t)((uint64_t)trial / (uint64_t)ys_repeat);
-        if (ys_index) g = ys_index[g];
-        return ys + g * ys_stride;
-    }
-};
 
 // x of lane `src` of the wavefront (any lane: ds_bpermute on the two halves; the source lane must be active)
 CGP_DEV double shuffle_f64(double x, int src) {
@@ -120,93 +101,8 @@ CGP_DEV TangentUpdate tangent_update(const double (&h)[4], double Xi, double dXi
     return u;
 }
 
-// ---- the host side the tangent entry points share (cgp_inst_tangent4.hip, cgp_inst_tangent4_sgp.hip, cgp_inst_tangent4_cd.hip): each is tangent_args, then its own
-// limit, then tangent_launch of its kernel.
-struct TangentCall {
-    const char* entry;                   // the entry point's name, for its messages
-    bool sgp, fisher;                    // takes a sigma-point set (sigma-point sets beyond the LDS stage are refused) / writes the matrix
-    bool cd = false;                     // the continuous-discrete form (cgp_tangent4_cd.hpp): the d = 4 chirp / La Scala SDE with its gamma
-};
-
-// The header's name of one flag bit, for the message that refuses it
-inline const char* tangent_flag_name(uint32_t bit) {
-    switch (bit) {
-    case CGP_NLL_FINAL_ONLY: return "CGP_NLL_FINAL_ONLY";
-    case CGP_WAVE_PER_TRIAL: return "CGP_WAVE_PER_TRIAL";
-    case CGP_THREAD_PER_TRIAL: return "CGP_THREAD_PER_TRIAL";
-    case CGP_SEQUENTIAL_SCAN: return "CGP_SEQUENTIAL_SCAN";
-    case CGP_GENERIC_KERNEL: return "CGP_GENERIC_KERNEL";
-    case CGP_SIM_FIXED_X0: return "CGP_SIM_FIXED_X0";
-    case CGP_LITERAL_SIGMA_SUM: return "CGP_LITERAL_SIGMA_SUM";
-    case CGP_DPP_KERNEL: return "CGP_DPP_KERNEL";
-    case CGP_FOUR_TRIALS_PER_WAVE: return "CGP_FOUR_TRIALS_PER_WAVE";
-    case CGP_ONE_TRIAL_PER_WAVE: return "CGP_ONE_TRIAL_PER_WAVE";
-    case CGP_TIME_SPLIT: return "CGP_TIME_SPLIT";
-    case CGP_NO_TIME_SPLIT: return "CGP_NO_TIME_SPLIT";
-    default: return "no flag of chirpgp_hip.h";
-    }
-}
-
-// The argument checks in the ABI's order (flags last: CGP_SKIP_MISSING or nothing), then io and ma filled.  -> CGP_OK with io.B > 0: launch; CGP_OK with io.B == 0: nothing to do
-// (B == 0 or n_dir == 0, decided before anything else is looked at); otherwise the code, with the message left in the context.
-inline int tangent_args(cgp_ctx* ctx, TangentCall call, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init, double dt,
-                        const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
-                        const double* dirs, int32_t n_dir, double* nll, double* grad, double* fisher, uint32_t flags, TangentIO& io, ModelArgs& ma) {
-    const std::string entry = call.entry;
-    io.B = 0;
-    if (!ctx) return CGP_E_ARG;
-    if (B < 0 || T < 0 || n_dir < 0) return fail(ctx, CGP_E_ARG, "negative B, T or n_dir");
-    if (B == 0 || n_dir == 0) return CGP_OK;
-    if (call.fisher && n_dir > kFisherMaxDir)      // a row of the matrix lives in registers, and the matrix couples all the directions of a launch
-        return fail(ctx, CGP_E_UNSUPPORTED, entry + " takes all directions in one launch: n_dir must be <= CGP_FISHER_MAX_DIR (16)");
-    if (!model || !model->params) return fail(ctx, CGP_E_ARG, "model or model.params is NULL");
-    if (call.cd) {
-        const bool sde = model->model_id == CGP_M_HARMONIC_SDE && model->n_harm == 1 && model->n_params == 3;
-        if (!sde || model->d != 4 || !model->gamma)
-            return fail(ctx, CGP_E_UNSUPPORTED, entry + " is built for the d = 4 chirp and La Scala SDE (CGP_M_HARMONIC_SDE, n_harm = 1) with model.gamma set");
-        if (model->gamma_stride != 0 && model->gamma_stride < 16) return fail(ctx, CGP_E_ARG, "model.gamma_stride < d * d");
-    } else {
-        const bool chirp = model->model_id == CGP_M_HARMONIC_LCD && model->n_harm == 1 && model->n_params == 5;
-        const bool lascala = model->model_id == CGP_M_LASCALA_LCD && model->n_params == 2;
-        if ((!chirp && !lascala) || model->d != 4) return fail(ctx, CGP_E_UNSUPPORTED, entry + " is built for the d = 4 chirp and La Scala LCD models");
-    }
-    if (model->param_stride != 0 && model->param_stride < model->n_params) return fail(ctx, CGP_E_ARG, "model.param_stride < n_params");
-    if (call.sgp) {
-        if (!sigma) return fail(ctx, CGP_E_ARG, "sigma is NULL");
-        if (sigma->d != 4) return fail(ctx, CGP_E_UNSUPPORTED, entry + " is built for d = 4 sigma-point sets");
-        if (!sigma->xi || !sigma->w || sigma->s < 1) return fail(ctx, CGP_E_ARG, "cgp_sigma.xi / w must be set and s >= 1");
-        if (SigmaSet::stage_bytes(sigma->s, 4, 0, false) > (size_t)kSigLdsMaxBytes)
-            return fail(ctx, CGP_E_UNSUPPORTED, "the sigma-point set does not fit the LDS stage of " + entry);
-    }
-    if (!init || !init->H || !init->Xi || !init->m0 || !init->P0) return fail(ctx, CGP_E_ARG, "init.H / Xi / m0 / P0 must be set");
-    if (T > 0 && !ys) return fail(ctx, CGP_E_ARG, "ys is NULL");
-    if (ys_stride < 0 || ys_repeat < 1) return fail(ctx, CGP_E_ARG, "ys_stride must be >= 0 and ys_repeat >= 1");
-    if (!dirs || !nll || !grad || (call.fisher && !fisher))
-        return fail(ctx, CGP_E_ARG, call.fisher ? "dirs / nll / grad / fisher must be set" : "dirs / nll / grad must be set");
-    if (const uint32_t other = flags & ~(uint32_t)CGP_SKIP_MISSING) {     // the one flag these entry points take
-        const uint32_t bit = other & (~other + 1u);                       // the lowest bit that is not it
-        char hex[16];
-        snprintf(hex, sizeof hex, "0x%x", (unsigned)bit);
-        return fail(ctx, CGP_E_ARG, entry + " takes CGP_SKIP_MISSING and no other flag: bit " + hex + " (" + tangent_flag_name(bit) + ") is set");
-    }
-    io.H = init->H; io.H_stride = init->H_stride; io.Xi = init->Xi; io.Xi_stride = init->Xi_stride;
-    io.m0 = init->m0; io.m0_stride = init->m0_stride; io.P0 = init->P0; io.P0_stride = init->P0_stride;
-    io.ys = ys; io.ys_stride = ys_stride; io.ys_repeat = ys_repeat; io.ys_index = ys_index;
-    io.dirs = dirs; io.B = B; io.T = T; io.n_dir = n_dir; io.nll = nll; io.grad = grad; io.fisher = call.fisher ? fisher : nullptr;
-    // the literal per-point sums: the kernels take no groups, so a grouped set is staged without its group table
-    ma = model_args(model, call.sgp ? sigma : nullptr, dt, CGP_LITERAL_SIGMA_SUM);
-    ma.sg.group_start = nullptr; ma.sg.n_groups = 0;
-    return CGP_OK;
-}
-
-// launch() on the context's device, under its launch lock
-template <class Launch>
-inline int tangent_launch(cgp_ctx* ctx, Launch launch) {
-    DeviceScope on_device(ctx->device);
-    if (!on_device.ok) return fail(ctx, CGP_E_HIP, "hipSetDevice failed");
-    std::lock_guard<std::recursive_mutex> launches(ctx->launch_mutex);
-    return launch_result(ctx, hip_rc(launch()));
-}
+// ---- the host side the tangent entry points share (cgp_inst_tangent4.hip, cgp_inst_tangent4_sgp.hip, cgp_inst_tangent4_cd.hip) is prepare_tangent with
+// its TangentCall (cgp_args.hpp: the argument checks, the limit of the entry's own grid, io and ma filled); each entry then hands launch_on its launcher.
 
 #ifndef CGP_TANGENT4_IO_ONLY      // the sigma-point units take TangentIO and not a second copy of this kernel
 // GAPS: the update gated per lane on its trial's measurement (tangent_update; the lanes of a trial read the same y, the trials of a

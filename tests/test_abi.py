@@ -12,7 +12,7 @@ HEADER = os.path.join(ROOT, 'include', 'chirpgp_hip.h')
 def _declared():
     src = open(HEADER).read()
     src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    return sorted(set(re.findall(r'\b(cgp_[a-z_]+)\s*\(', src)))
+    return sorted(set(re.findall(r'\b(cgp_[a-z0-9_]+)\s*\(', src)))
 
 
 def _lib():

@@ -1,37 +1,19 @@
-"""The argument checks the four tangent entry points share (csrc/cgp_tangent4.hpp: tangent_args): one faulty argument at a time gives the same
+"""The argument checks the four tangent entry points share (csrc/cgp_args.hpp: prepare_tangent): one faulty argument at a time gives the same
 return code from every entry point that takes the argument, and leaves the output buffers as they were.  Beside them two good calls:
 T = 9 crosses the EKF kernel's 8-step measurement block, T = 0 writes zeros.
 
-The codes are those the four hand-written copies of the checks returned before they were folded (recorded on an MI355X with the parent
-commit's library: every row of the table as it stands here, for all four entry points)."""
+The rows are those of the C-ABI's case table (tests/abi_cases.py: TANGENT_FAULTS), whose codes are those the four hand-written copies of
+the checks returned before they were folded (recorded on an MI355X with that commit's library: every row, for all four entry points)."""
 import numpy as np
 import numpy.testing as npt
 import pytest
 
+from tests.abi_cases import E_UNSUPPORTED, TANGENT_FAULTS as FAULTS
 from tests.tangent_cases import ENTRIES, ZG, directions, grad_case, raw
 
 pytestmark = pytest.mark.gpu
 VALUE_RTOL, GRAD_GATE = 1e-11, 1e-8                # the gates of test_gpu_gradient_edges.py::test_record_lengths, which runs T = 9 through mle
 FILL = 123.0
-E_ARG, E_UNSUPPORTED = -1, -2
-
-
-def _model_d6(a):
-    a['model'].d, a['model'].n_harm = 6, 2         # the two-harmonic chirp model
-
-
-# (what is wrong, the edit that makes it so, the code, sigma-point entry points only)
-FAULTS = [('dirs = NULL', lambda a: a.update(dirs=None), E_ARG, False),
-          ('nll = NULL', lambda a: a.update(nll=None), E_ARG, False),
-          ('grad = NULL', lambda a: a.update(grad=None), E_ARG, False),
-          ('ys_repeat = 0', lambda a: a.update(ys_repeat=0), E_ARG, False),
-          ('ys_stride = -1', lambda a: a.update(ys_stride=-1), E_ARG, False),
-          ('param_stride = 1', lambda a: setattr(a['model'], 'param_stride', 1), E_ARG, False),
-          ('init.P0 = NULL', lambda a: setattr(a['init'], 'P0', None), E_ARG, False),
-          ('a d = 6 model', _model_d6, E_UNSUPPORTED, False),
-          ('a sigma-point set with d = 6', lambda a: setattr(a['sigma'], 'd', 6), E_UNSUPPORTED, True),
-          ('sigma = NULL', lambda a: a.update(sigma=None), E_ARG, True),
-          ('B = 0', lambda a: a.update(B=0), 0, False)]
 
 
 @pytest.mark.parametrize('entry', ENTRIES)
