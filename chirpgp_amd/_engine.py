@@ -19,6 +19,7 @@ M_LINEAR, M_HARMONIC_LCD, M_LASCALA_LCD, M_LINEAR_SDE, M_HARMONIC_SDE, M_KPT = r
 NLL_FINAL_ONLY, WAVE_PER_TRIAL, THREAD_PER_TRIAL, SEQUENTIAL_SCAN, GENERIC_KERNEL, SIM_FIXED_X0 = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 LITERAL_SIGMA_SUM, DPP_KERNEL, FOUR_TRIALS_PER_WAVE, ONE_TRIAL_PER_WAVE = 0x40, 0x80, 0x200, 0x400
 TIME_SPLIT, NO_TIME_SPLIT, SKIP_MISSING = 0x800, 0x1000, 0x2000
+RK4_SUBSTEPS_MASK, MAX_SUBSTEPS = 0x000F0000, 16      # CGP_RK4_SUBSTEPS(n) = (n - 1) << 16, n = 1 .. 16
 SIGMA_STANDARD = 0x1
 SIGMA_AXIAL = 0x2
 MAX_D = 12            # include/chirpgp_hip.h: CGP_MAX_D (9 .. 12: the harmonic LCD model with 4 or 5 harmonics)
@@ -444,8 +445,26 @@ def _missing_flag(missing):
     raise ValueError(f"missing must be None, 'propagate' or 'skip', not {missing!r}")
 
 
+def rk4_substeps(n):
+    """CGP_RK4_SUBSTEPS(n) of include/chirpgp_hip.h: the flag bits of n = 1 .. 16 RK4 substeps between measurements (n = 1: none)."""
+    if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= MAX_SUBSTEPS:
+        raise ValueError(f'substeps must be an integer in 1 .. {MAX_SUBSTEPS}, not {n!r}')
+    return (int(n) - 1) << 16
+
+
+def _substeps_flag(substeps, continuous_discrete, time_split, what):
+    """``substeps`` of the continuous-discrete methods -> flag bits; what cannot take them is refused here, before anything is launched."""
+    bits = rk4_substeps(substeps)
+    if bits and not continuous_discrete:
+        raise ValueError(f'substeps goes with the continuous-discrete methods only (cd_ekf, cd_eks, cd_sgp_filter, cd_sgp_smoother), not with {what}')
+    if bits and time_split is not None:
+        raise ValueError('substeps does not go with time_split: the time-split kernels take one RK4 step per sample')
+    return bits
+
+
 def run_filter(method, spec, sgps, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=False, flags=0, want=(True, True, True),
-               trials_per_record=None, record_index=None, time_split=None, split_tol=None, return_junction_error=False, missing=None):
+               trials_per_record=None, record_index=None, time_split=None, split_tol=None, return_junction_error=False, missing=None,
+               substeps=1):
     """cgp_filter with NumPy / torch marshalling.  ys (T,) or (B, T) -> (mfs, Pfs, nll) with matching leading axes.
 
     Shared records (include/chirpgp_hip.h, cgp_filter): with ``trials_per_record = k`` every record of ys -- (T,) or (R, T) --
@@ -461,10 +480,15 @@ def run_filter(method, spec, sgps, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=
 
     ``missing='skip'`` (include/chirpgp_hip.h, CGP_SKIP_MISSING): a NaN measurement is a missing sample -- the prediction is that step's
     filtering result and its NLL increment is exactly 0 -- instead of the reference's poison (None / 'propagate').  Not with
-    ``time_split``."""
+    ``time_split``.
+
+    ``substeps=n`` (include/chirpgp_hip.h, CGP_RK4_SUBSTEPS; cd_ekf and cd_sgp_filter): n = 1 .. 16 RK4 steps of dt / n between two
+    measurements instead of one of dt -- the rows n - 1, 2 n - 1, ... of the same filter at step dt / n on the record refined n times
+    with gaps at the inserted times, without the n-fold record and outputs.  Not with ``time_split``."""
     gaps = _missing_flag(missing)
     if gaps and time_split is not None:
         raise ValueError("missing='skip' does not go with time_split: a burn-in that starts inside a gap has no junction to compare")
+    gaps |= _substeps_flag(substeps, int(method) in (F_CD_EKF, F_CD_SGP), time_split, 'a discrete filter')
     junction = None
     torch = _torch()
     like_numpy = not _is_torch(ys)
@@ -547,10 +571,19 @@ def release_custom_models():
     return n
 
 
-def run_filter_custom(spec, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=False, want=(True, True, True), flags=0, sgps=None, missing=None):
+def _custom_substeps_flag(spec, substeps):
+    """``substeps`` of a run-time compiled model -> flag bits: an SDE model's (models.custom_sde) alone, checked before anything is compiled."""
+    bits = rk4_substeps(substeps)
+    if bits and int(getattr(spec, 'kind', -1)) != 1:          # include/chirpgp_hip.h: CGP_CUSTOM_SDE
+        raise ValueError('substeps goes with the continuous-discrete methods only (a custom_sde model): a discrete model has no ODE to integrate')
+    return bits
+
+
+def run_filter_custom(spec, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=False, want=(True, True, True), flags=0, sgps=None, missing=None,
+                      substeps=1):
     """ekf / cd_ekf -- with `sgps`: sgp_filter / cd_sgp_filter -- on a model compiled at run time (cgp_filter_custom): the generic
-    one-lane-per-trial kernel instantiated on the caller's source.  ys (T,) or (B, T).  ``missing`` as in run_filter."""
-    gaps = _missing_flag(missing)
+    one-lane-per-trial kernel instantiated on the caller's source.  ys (T,) or (B, T).  ``missing`` and ``substeps`` (cd_ekf, cd_sgp_filter) as in run_filter."""
+    gaps = _missing_flag(missing) | _custom_substeps_flag(spec, substeps)
     torch = _torch()
     like_numpy = not _is_torch(ys)
     ys_d = dev(ys)
@@ -576,8 +609,10 @@ def run_filter_custom(spec, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=False, 
         return tuple(None if t is None else _out(t, like_numpy, squeeze) for t in (mfs, Pfs, nll))
 
 
-def run_smoother_custom(spec, gamma, dt, mfs, Pfs, flags=0, sgps=None):
-    """eks / cd_eks -- with `sgps`: sgp_smoother / cd_sgp_smoother -- on a model compiled at run time (cgp_smoother_custom)."""
+def run_smoother_custom(spec, gamma, dt, mfs, Pfs, flags=0, sgps=None, substeps=1):
+    """eks / cd_eks -- with `sgps`: sgp_smoother / cd_sgp_smoother -- on a model compiled at run time (cgp_smoother_custom).  ``substeps`` (cd_eks,
+    cd_sgp_smoother) as in run_smoother: that launch runs one wavefront per trial."""
+    flags = int(flags) | _custom_substeps_flag(spec, substeps)
     torch = _torch()
     like_numpy = not _is_torch(mfs)
     m, P = dev(mfs), dev(Pfs)
@@ -634,13 +669,14 @@ def run_sgp_nll_fisher(spec, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_recor
     return _run_nll_grad(spec, _need_sigma(sgps, 'cgp_sgp_nll_fisher'), True, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing)
 
 
-def run_cd_ekf_nll_grad(spec, gamma, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None, missing=None):
+def run_cd_ekf_nll_grad(spec, gamma, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None, missing=None, substeps=1):
     """cgp_cd_ekf_nll_grad: the continuous-discrete EKF's final NLL and its derivative along `dirs` (B, n_dir, 27) -- forward tangents
     through the RK4 stages and the update, one launch.  `spec` the drift's descriptor, `gamma` = b b^T (4, 4) or (B, 4, 4); everything
-    else, and the results, as run_ekf_nll_grad."""
+    else, and the results, as run_ekf_nll_grad.  ``substeps=n``: as run_filter's (the directions do not depend on dt: the same `dirs`)."""
     if gamma is None:
         raise ValueError('cgp_cd_ekf_nll_grad needs gamma = b b^T')
-    return _run_nll_grad(spec, None, False, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing, gamma=gamma)
+    return _run_nll_grad(spec, None, False, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing, gamma=gamma,
+                         flags=rk4_substeps(substeps))
 
 
 def _need_sigma(sgps, entry):
@@ -649,10 +685,11 @@ def _need_sigma(sgps, entry):
     return sgps
 
 
-def _run_nll_grad(spec, sgps, fisher, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing=None, gamma=None):
+def _run_nll_grad(spec, sgps, fisher, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing=None, gamma=None, flags=0):
     """The tangent entry points: the sigma-point filter's with `sgps`, the EKF's with None, the continuous-discrete EKF's with `gamma`
-    (b b^T; directions of 27 doubles, not 24); `fisher`: the matrix as a third output; `missing`: as run_filter's, through _missing_flag."""
-    gaps = _missing_flag(missing)
+    (b b^T; directions of 27 doubles, not 24); `fisher`: the matrix as a third output; `missing`: as run_filter's, through _missing_flag;
+    `flags`: the bits of CGP_RK4_SUBSTEPS (the continuous-discrete entry)."""
+    gaps = _missing_flag(missing) | int(flags)
     torch = _torch()
     ys_d = dev(ys)
     if ys_d.ndim == 1:
@@ -703,14 +740,18 @@ class SmootherSelection(dict):
 
 
 def run_smoother(method, spec, sgps, gamma, dt, mfs, Pfs, flags=0, want=(True, True), select=None, time_split=None, split_tol=None,
-                 return_junction_error=False):
+                 return_junction_error=False, substeps=1):
     """cgp_smoother / cgp_smoother_select with NumPy / torch marshalling.  (T, d) / (T, d, d) or with a leading batch axis.
 
     ``select = dict(comp=k, mean=True, var=True, expect='softplus' | 'exp' | 'identity' | 'square' | None, order=10)`` asks the launch
     for the smoothed marginal of state component k as well: its mean mss[..., k], its variance Pss[..., k, k] and / or E[f(V)] by 1-D
     Gauss-Hermite (quadratures.py:234-274 -- the step behind the smoother in every driver of the reference, demos/ekfs_mle.py:69-77).
     The call then returns ``(mss, Pss, selection)``; with ``want=(False, False)`` the full rows are not written at all (None in their
-    place) and a d = 4 smoother moves 8 - 24 bytes a step instead of 160 (include/chirpgp_hip.h: cgp_smoother_select)."""
+    place) and a d = 4 smoother moves 8 - 24 bytes a step instead of 160 (include/chirpgp_hip.h: cgp_smoother_select).
+
+    ``substeps=n`` (CGP_RK4_SUBSTEPS; cd_eks and cd_sgp_smoother, on the rows of a filter run with the same n): n backward RK4 steps of
+    dt / n per interval, each against the moments the filter's forward substeps passed through.  Not with ``time_split``."""
+    flags = int(flags) | _substeps_flag(substeps, int(method) in (S_CD_EKS, S_CD_SGP), time_split, 'a discrete smoother')
     torch = _torch()
     like_numpy = not _is_torch(mfs)
     m, P = dev(mfs), dev(Pfs)

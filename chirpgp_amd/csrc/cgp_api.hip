@@ -353,8 +353,10 @@ static Verdict enqueue_filter(cgp_ctx* ctx, const FilterCall& c, FilterPlan& p, 
         case CGP_M_LINEAR:       rc = dispatch_filter_disc_linear(c.method, model->d, route.wave, io, ma, st); break;
         case CGP_M_HARMONIC_LCD:
         case CGP_M_LASCALA_LCD:  rc = dispatch_filter_disc_harm(c.method, model->n_harm, route.wave, io, ma, st); break;
-        case CGP_M_LINEAR_SDE:   rc = dispatch_filter_sde_linear(c.method, model->d, route.wave, io, ma, st); break;
-        case CGP_M_HARMONIC_SDE: rc = dispatch_filter_sde_harm(c.method, model->n_harm, route.wave, io, ma, st); break;
+        case CGP_M_LINEAR_SDE:   rc = route.substeps ? dispatch_filter_sde_linear_substeps(c.method, model->d, route.wave, io, ma, st)
+                                                     : dispatch_filter_sde_linear(c.method, model->d, route.wave, io, ma, st); break;
+        case CGP_M_HARMONIC_SDE: rc = route.substeps ? dispatch_filter_sde_harm_substeps(c.method, model->n_harm, route.wave, io, ma, st)
+                                                     : dispatch_filter_sde_harm(c.method, model->n_harm, route.wave, io, ma, st); break;
         default: rc = CGP_E_ARG;
         }
         break;
@@ -369,9 +371,11 @@ static Verdict enqueue_filter(cgp_ctx* ctx, const FilterCall& c, FilterPlan& p, 
     case FilterRoute::kLane4Sgp:    rc = dispatch_filter_lane4(c.method, io, ma, st); break;
     case FilterRoute::kEkf8Coop:    rc = dispatch_filter_coop8_ekf(model->n_harm, io, ma, st); break;
     case FilterRoute::kSgp8Coop:    rc = dispatch_filter_coop8_sgp(model->n_harm, io, ma, st); break;
-    case FilterRoute::kCdEkf4Mfma:  rc = route.gaps ? dispatch_filter_mfma4_cdekf_gaps(io, ma, st) : dispatch_filter_mfma4_cdekf(io, ma, st); break;
+    case FilterRoute::kCdEkf4Mfma:  rc = route.substeps ? dispatch_filter_mfma4_cdekf_substeps(route.gaps, io, ma, st)
+                                         : route.gaps ? dispatch_filter_mfma4_cdekf_gaps(io, ma, st) : dispatch_filter_mfma4_cdekf(io, ma, st); break;
     case FilterRoute::kCdEkf4Coop:  rc = dispatch_filter_coop4_cdekf(io, ma, st); break;
-    case FilterRoute::kCdSgp4Mfma:  rc = route.gaps ? dispatch_filter_mfma4_cdsgp_gaps(io, ma, st) : dispatch_filter_mfma4_cdsgp(io, ma, st); break;
+    case FilterRoute::kCdSgp4Mfma:  rc = route.substeps ? dispatch_filter_mfma4_cdsgp_substeps(route.gaps, io, ma, st)
+                                         : route.gaps ? dispatch_filter_mfma4_cdsgp_gaps(io, ma, st) : dispatch_filter_mfma4_cdsgp(io, ma, st); break;
     case FilterRoute::kCdSgp4Coop:  rc = dispatch_filter_coop4_cdsgp(io, ma, st); break;
     case FilterRoute::kKpt8Coop:    rc = dispatch_filter_kpt8(model->n_harm, io, ma, st); break;
     case FilterRoute::kGenericKpt:  rc = dispatch_filter_kpt(model->n_harm, route.wave, io, ma, st); break;
@@ -408,12 +412,14 @@ static Verdict enqueue_smoother(cgp_ctx* ctx, const SmootherCall& c, SmootherPla
     case SmootherRoute::kWalk4Harm:   rc = dispatch_smoother_walk4_harm(method, io, host, ma, st); break;
     case SmootherRoute::kLane4:       rc = dispatch_smoother_lane4(method, model->model_id, io, host, ma, st); break;
     case SmootherRoute::kDiscHarm:    rc = dispatch_smoother_disc_harm(method, model->n_harm, wave, io, ma, st); break;
-    case SmootherRoute::kSdeLinear:   rc = dispatch_smoother_sde_linear(method, model->d, wave, io, ma, st); break;
+    case SmootherRoute::kSdeLinear:   rc = plan.substeps ? dispatch_smoother_sde_linear_substeps(method, model->d, io, ma, st)
+                                                         : dispatch_smoother_sde_linear(method, model->d, wave, io, ma, st); break;
     case SmootherRoute::kCdSgp4Mfma:  rc = dispatch_smoother_mfma4_cdsgp(io, ma, st); break;
     case SmootherRoute::kCdSgp4Coop:  rc = dispatch_smoother_coop4_cdsgp(io, ma, st); break;
     case SmootherRoute::kCdEks4Mfma:  rc = dispatch_smoother_mfma4_cdeks(io, ma, st); break;
     case SmootherRoute::kCdEks4Coop:  rc = dispatch_smoother_coop4_cdeks(io, ma, st); break;
-    case SmootherRoute::kSdeHarm:     rc = dispatch_smoother_sde_harm(method, model->n_harm, wave, io, ma, st); break;
+    case SmootherRoute::kSdeHarm:     rc = plan.substeps ? dispatch_smoother_sde_harm_substeps(method, model->n_harm, io, ma, st)
+                                                         : dispatch_smoother_sde_harm(method, model->n_harm, wave, io, ma, st); break;
     case SmootherRoute::kNone:        rc = CGP_E_ARG; break;
     }
     if (rc == CGP_OK && c.junction_err) {

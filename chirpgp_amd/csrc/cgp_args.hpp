@@ -77,6 +77,7 @@ inline Verdict check_model(const cgp_model* m, bool sde, bool need_sigma, const 
 // ---- flags ----------------------------------------------------------------------------------------------------------------------------
 // The header's name of one flag bit, for the message that refuses it
 inline const char* flag_name(uint32_t bit) {
+    if (bit & CGP_RK4_SUBSTEPS_MASK) return "CGP_RK4_SUBSTEPS";
     switch (bit) {
     case CGP_NLL_FINAL_ONLY: return "CGP_NLL_FINAL_ONLY";
     case CGP_WAVE_PER_TRIAL: return "CGP_WAVE_PER_TRIAL";
@@ -131,11 +132,16 @@ inline ModelArgs model_args(const double* params, int64_t param_stride, const do
         if (assertions) a.sg.flags = sg->flags;
     }
     a.dt = dt;
+    a.substeps = 1;
     return a;
 }
-// a filter's or smoother's (CGP_LITERAL_SIGMA_SUM: the set without its assertions)
+// a filter's or smoother's (CGP_LITERAL_SIGMA_SUM: the set without its assertions; CGP_RK4_SUBSTEPS: n, and the kernels' dt is the substep
+// h = dt / n -- one IEEE division, here; n = 1 leaves dt as it came)
 inline ModelArgs model_args(const cgp_model* m, const cgp_sigma* sg, double dt, uint32_t flags) {
-    return model_args(m->params, m->param_stride, m->gamma, m->gamma_stride, m->model_id, dt, sg, true, !(flags & CGP_LITERAL_SIGMA_SUM));
+    ModelArgs a = model_args(m->params, m->param_stride, m->gamma, m->gamma_stride, m->model_id, dt, sg, true, !(flags & CGP_LITERAL_SIGMA_SUM));
+    const int n = substeps_of(flags);
+    if (n > 1) { a.substeps = n; a.dt = dt / (double)n; }
+    return a;
 }
 // the literal per-point sums of kernels that take no groups (the tangent kernels, cgp_smoother_sample): a grouped set without its group table
 inline ModelArgs model_args_literal(const cgp_model* m, const cgp_sigma* sg, double dt) {
@@ -181,6 +187,7 @@ inline Verdict prepare_filter(const FilterCall& c, const HostCtx& h, FilterPlan&
         if (c.flags & CGP_SKIP_MISSING)
             return {CGP_E_UNSUPPORTED, "CGP_SKIP_MISSING goes with cgp_filter and cgp_filter_custom only: a time-split filter's burn-in that starts "
                                        "inside a gap has no junction to compare"};
+        if (c.flags & CGP_RK4_SUBSTEPS_MASK) return {CGP_E_UNSUPPORTED, kSubstepsSplit};
     }
     if (c.B < 0 || c.T < 0) return {CGP_E_ARG, "negative B or T"};
     if (c.B == 0 || c.T == 0) return kNothingToDo;
@@ -239,6 +246,7 @@ inline Verdict prepare_smoother(const SmootherCall& c, const HostCtx& h, Smoothe
     if (c.time_split) {
         if (c.segments < 1) return {CGP_E_ARG, "segments must be >= 1"};
         if (!c.junction_err) return {CGP_E_ARG, "junction_err must be set"};
+        if (c.flags & CGP_RK4_SUBSTEPS_MASK) return {CGP_E_UNSUPPORTED, kSubstepsSplit};
     }
     if (c.B < 0 || c.T < 0) return {CGP_E_ARG, "negative B or T"};
     if (c.B == 0 || c.T == 0) return kNothingToDo;
@@ -358,7 +366,8 @@ inline Verdict prepare_tangent(TangentCall call, const cgp_model* model, const c
     if (ys_stride < 0 || ys_repeat < 1) return {CGP_E_ARG, "ys_stride must be >= 0 and ys_repeat >= 1"};
     if (!dirs || !nll || !grad || (call.fisher && !fisher))
         return {CGP_E_ARG, call.fisher ? "dirs / nll / grad / fisher must be set" : "dirs / nll / grad must be set"};
-    if (const Verdict v = check_flags(entry, flags, CGP_SKIP_MISSING); v.rc != CGP_OK) return v;      // the one flag these entry points take
+    // the one flag these entry points take; the continuous-discrete one takes CGP_RK4_SUBSTEPS beside it
+    if (const Verdict v = check_flags(entry, call.cd ? flags & ~CGP_RK4_SUBSTEPS_MASK : flags, CGP_SKIP_MISSING); v.rc != CGP_OK) return v;
     // the grids: one workgroup per trial (sigma-point), 64 / n_dir whole trials per wavefront (the EKF's Fisher form), B n_dir lanes (cd)
     if (call.sgp) {
         if (B > 0x7fffffffLL) return refusef(CGP_E_UNSUPPORTED, "%s runs one workgroup per trial: B must be < 2^31", entry);
@@ -371,6 +380,7 @@ inline Verdict prepare_tangent(TangentCall call, const cgp_model* model, const c
     set_record(io, ys, ys_stride, ys_repeat, ys_index);
     io.dirs = dirs; io.B = B; io.T = T; io.n_dir = n_dir; io.nll = nll; io.grad = grad; io.fisher = call.fisher ? fisher : nullptr;
     ma = model_args_literal(model, call.sgp ? sigma : nullptr, dt);
+    if (const int n = substeps_of(flags); call.cd && n > 1) { ma.substeps = n; ma.dt = dt / (double)n; }      // (as model_args(..., flags))
     return {};
 }
 
@@ -380,6 +390,15 @@ struct CustomModel {
     int kind = 0, d = 0, device = 0;
     bool ekf = false, sgp = false;       // the entry's kernel exists in the model's code object: without / with a sigma-point set
 };
+// CGP_RK4_SUBSTEPS on a run-time compiled model: an SDE model's (CGP_CUSTOM_SDE) alone -- n, and h = dt / n as the kernels' dt, as
+// model_args(..., flags) has them
+inline Verdict custom_substeps(const CustomModel& m, uint32_t flags, double dt, ModelArgs& ma) {
+    const int n = substeps_of(flags);
+    if (n == 1) return {};
+    if (m.kind != CGP_CUSTOM_SDE) return {CGP_E_ARG, kSubstepsDiscrete};
+    ma.substeps = n; ma.dt = dt / (double)n;
+    return {};
+}
 inline Verdict check_custom_sigma(const cgp_sigma* sigma, int d) {
     if (sigma && (!sigma->xi || !sigma->w || sigma->s < 1 || sigma->d != d)) return {CGP_E_ARG, "cgp_sigma needs xi, w, s >= 1 and d = the model's"};
     return {};
@@ -398,11 +417,12 @@ inline Verdict prepare_filter_custom(const CustomModel& m, const cgp_sigma* sigm
     if (m.kind == CGP_CUSTOM_SDE && !gamma) return {CGP_E_ARG, "SDE models need gamma = b b^T"};
     if (!(sigma ? m.sgp : m.ekf)) return {CGP_E_UNSUPPORTED, "a measurement function (ekf_for_kpt) has no sigma-point form"};
     if (const Verdict v = check_custom_sigma(sigma, m.d); v.rc != CGP_OK) return v;
+    if ((flags & CGP_RK4_SUBSTEPS_MASK) && m.kind != CGP_CUSTOM_SDE) return {CGP_E_ARG, kSubstepsDiscrete};
     set_init(io, init);
     set_record(io, ys, ys_stride, ys_repeat, ys_index);
     io.B = B; io.T = T; io.mfs = mfs; io.Pfs = Pfs; io.nll = nll; io.flags = flags & (CGP_NLL_FINAL_ONLY | CGP_SKIP_MISSING);
     ma = model_args_custom(params, param_stride, gamma, gamma_stride, dt, sigma);
-    return {};
+    return custom_substeps(m, flags, dt, ma);
 }
 inline Verdict prepare_smoother_custom(const CustomModel& m, const cgp_sigma* sigma, const double* params, int64_t param_stride, const double* gamma,
                                        int64_t gamma_stride, double dt, const double* mfs, const double* Pfs, int64_t B, int64_t T, double* mss,
@@ -416,9 +436,15 @@ inline Verdict prepare_smoother_custom(const CustomModel& m, const cgp_sigma* si
     if (!(sigma ? m.sgp : m.ekf))
         return {CGP_E_UNSUPPORTED, "a measurement function (ekf_for_kpt) has no smoother of its own: its dynamics are linear -- cgp_smoother with CGP_S_EKS on (F, Sigma)"};
     if (const Verdict v = check_custom_sigma(sigma, m.d); v.rc != CGP_OK) return v;
+    if (flags & CGP_RK4_SUBSTEPS_MASK) {
+        if (m.kind != CGP_CUSTOM_SDE) return {CGP_E_ARG, kSubstepsDiscrete};
+        // (one wavefront per trial, the set staged in LDS beside the table of the interval's moments: route_smoother's condition)
+        if (sigma && SigmaSet::stage_bytes(sigma->s, m.d, 0, false) + substep_table_bytes(m.d) > (size_t)kSigLdsMaxBytes)
+            return {CGP_E_UNSUPPORTED, "CGP_RK4_SUBSTEPS: the sigma-point set does not fit the LDS stage beside the table of intermediate moments"};
+    }
     io.mfs = mfs; io.Pfs = Pfs; io.B = B; io.T = T; io.mss = mss; io.Pss = Pss; io.flags = flags;
     ma = model_args_custom(params, param_stride, gamma, gamma_stride, dt, sigma);
-    return {};
+    return custom_substeps(m, flags, dt, ma);
 }
 
 // ---- cgp_simulate, cgp_simulate_x0, cgp_add_noise ------------------------------------------------------------------------------------------------

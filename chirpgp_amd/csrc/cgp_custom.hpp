@@ -13,7 +13,9 @@
 // instantiates filter_kernel<EkfPredict<..>>, smoother_kernel<EksStep<..>>, filter_kernel<CdEkfPredict<..>>, smoother_kernel<CdEksStep<..>>
 // on them -- ekf, eks, cd_ekf, cd_eks for any model of dimension <= 8, same arithmetic as the compiled-in models -- and the sigma-point
 // methods: sgp_filter / sgp_smoother through a literal fan (SgpPredictCustom: the covariance evaluated at every point), cd_sgp_filter /
-// cd_sgp_smoother through the generic CdSgpPredict / CdSgpsStep.
+// cd_sgp_smoother through the generic CdSgpPredict / CdSgpsStep.  An SDE model's program also holds their CGP_RK4_SUBSTEPS forms
+// (cgp_steps.hpp): SubstepPredict on the two lane-per-trial filters, and SubstepSmooth on CdEksStep / CdSgpsStep with one wavefront per
+// trial -- the one place a run-time compiled model runs in that shape, its sigma-point set staged in LDS as the compiled-in models' is.
 #pragma once
 #include "cgp_kernels.hpp"
 

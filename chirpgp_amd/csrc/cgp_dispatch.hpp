@@ -74,5 +74,27 @@ static int smoother_sde(int method, bool wave, const SmootherIO& io, const Model
     default: return CGP_E_UNSUPPORTED;
     }
 }
+// CGP_RK4_SUBSTEPS (cgp_steps.hpp: SubstepPredict, SubstepSmooth): the filters in both launch shapes, the smoothers one wavefront per trial
+template <class SM>
+static int filter_sde_substeps(int method, bool wave, const FilterIO& io, const ModelArgs& ma, hipStream_t st) {
+    using Meas = LinearMeasurement<SM::D>;
+    switch (method) {
+    case CGP_F_CD_EKF:
+        return hip_rc(wave ? launch_filter<SubstepPredict<CdEkfPredict<SM, true>>, Meas>(io, ma, st)
+                           : launch_filter<SubstepPredict<CdEkfPredict<SM, false>>, Meas>(io, ma, st));
+    case CGP_F_CD_SGP:
+        return hip_rc(wave ? launch_filter<SubstepPredict<CdSgpPredict<SM, true>>, Meas>(io, ma, st)
+                           : launch_filter<SubstepPredict<CdSgpPredict<SM, false>>, Meas>(io, ma, st));
+    default: return CGP_E_UNSUPPORTED;
+    }
+}
+template <class SM>
+static int smoother_sde_substeps(int method, const SmootherIO& io, const ModelArgs& ma, hipStream_t st) {
+    switch (method) {
+    case CGP_S_CD_EKS: return hip_rc(launch_smoother<SubstepSmooth<CdEksStep<SM, true>>>(io, ma, st));
+    case CGP_S_CD_SGP: return hip_rc(launch_smoother<SubstepSmooth<CdSgpsStep<SM, true>>>(io, ma, st));
+    default: return CGP_E_UNSUPPORTED;
+    }
+}
 
 }  // namespace cgp

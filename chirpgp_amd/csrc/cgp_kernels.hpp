@@ -598,6 +598,10 @@ __global__ void __launch_bounds__(64) smoother_kernel(SmootherIO io, ModelArgs m
     Step step;
     step.setup(ma, trial);
     if constexpr (Step::USES_SIGMA && WAVE) step.sg.stage(dyn_lds(), lane, 64, D);
+    if constexpr (IsSubstepped<Step>::value) {          // CGP_RK4_SUBSTEPS (cgp_steps.hpp: SubstepSmooth): the interval's intermediate moments
+        __shared__ double subtab[SubTable<D>::DOUBLES];
+        step.attach(subtab);
+    }
     const int64_t T = io.T;
     Vec<D> ms, mf;
     Sym<D> Ps, Pf;
@@ -789,6 +793,14 @@ int dispatch_smoother_disc_linear(int method, int key, bool wave, const Smoother
 int dispatch_smoother_disc_harm(int method, int key, bool wave, const SmootherIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_sde_linear(int method, int key, bool wave, const SmootherIO&, const ModelArgs&, hipStream_t);
 int dispatch_smoother_sde_harm(int method, int key, bool wave, const SmootherIO&, const ModelArgs&, hipStream_t);
+// the same generic kernels with CGP_RK4_SUBSTEPS (cgp_inst_substeps_linear.hip, cgp_inst_substeps_harm.hip); the smoothers one wavefront per trial
+int dispatch_filter_sde_linear_substeps(int method, int key, bool wave, const FilterIO&, const ModelArgs&, hipStream_t);
+int dispatch_filter_sde_harm_substeps(int method, int key, bool wave, const FilterIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_sde_linear_substeps(int method, int key, const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_sde_harm_substeps(int method, int key, const SmootherIO&, const ModelArgs&, hipStream_t);
+// ... and the one-wavefront-per-trial matrix-core filters at d = 4, with gaps or without (cgp_inst_substeps4.hip)
+int dispatch_filter_mfma4_cdekf_substeps(bool gaps, const FilterIO&, const ModelArgs&, hipStream_t);
+int dispatch_filter_mfma4_cdsgp_substeps(bool gaps, const FilterIO&, const ModelArgs&, hipStream_t);
 // The host side of a smoother launch on the cooperative walks and the large-batch lane kernels: what their launchers need beside the
 // kernel's arguments.  Filled from the SmootherDecision (cgp_route.hpp) and the context.
 struct WalkSplit { int cap = 1; int min_tiles = 4; };      // exact time split: at most `cap` segments (1: off, 0: as many as fit), of `min_tiles` tiles or more

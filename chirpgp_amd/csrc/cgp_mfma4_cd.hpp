@@ -130,9 +130,12 @@ CGP_DEV void mfma4_update_col(double Pp, double fcol, double Hk, double Hq, doub
 }
 
 // ------------------------------------------------------------------------------------------------ cd_sgp_filter, d = 4
-template <class SM, bool TWO, bool SPLIT, bool GAPS = false>
+// SUB (CGP_RK4_SUBSTEPS): n = ma.substeps RK4 steps of ma.dt = h (divided once on the host) per sample,
+// a rolled loop around the same stage function; whole records only.  Instantiated in cgp_inst_substeps4.hip only.
+template <class SM, bool TWO, bool SPLIT, bool GAPS = false, bool SUB = false>
 __global__ void __launch_bounds__(64) cdsgp4_mfma_kernel(FilterIO io, ModelArgs ma) {
     static_assert(!(SPLIT && GAPS), "the time-split launches know no gaps");
+    static_assert(!(SPLIT && SUB), "the time-split launches take one RK4 step per sample");
     static_assert(SM::D == 4, "d = 4 kernel");
     __shared__ double2 park[64];                                         // (S, innovation) of the chunk's steps, for the NLL
     const int lane = threadIdx.x;
@@ -182,7 +185,11 @@ __global__ void __launch_bounds__(64) cdsgp4_mfma_kernel(FilterIO io, ModelArgs 
             const unsigned t = (unsigned)(t0 + slot);
             const double y = readlane_f64(ychunk, slot);
             double f = u, Pp = P;
-            rk4_lane(dt, f, Pp, [&](double tm, double tP, double& km, double& kP) { cd4_mfma_rhs<TWO>(model, R, K, grp, tm, tP, km, kP); });
+            auto rhs = [&](double tm, double tP, double& km, double& kP) { cd4_mfma_rhs<TWO>(model, R, K, grp, tm, tP, km, kP); };
+            if constexpr (SUB) {
+#pragma unroll 1
+                for (int j = 0; j < ma.substeps; j++) rk4_lane(dt, f, Pp, rhs);
+            } else rk4_lane(dt, f, Pp, rhs);
             // ---- update
             double S, innov;
             mfma4_update_col<GAPS>(Pp, f, Hk, Hq, Xi, y, P, u, S, innov);
@@ -305,7 +312,9 @@ CGP_DEV void cd4_ekf_eval(const SoftplusRegs& R, const Cd4LaneCoef& K, const Cd4
 }
 
 #ifndef CGP_NO_CD_EKF_KERNELS       // the kernels below are instantiated in cgp_inst_mfma4.hip (GAPS: cgp_inst_gaps4_sigma.hip)
-template <bool GAPS = false>
+// SUB (CGP_RK4_SUBSTEPS): n = ma.substeps RK4 steps of ma.dt = h (divided once on the host) per sample, a rolled loop
+// around the same stage function; the NLL flush and the stores go by samples as before.  Instantiated in cgp_inst_substeps4.hip only.
+template <bool GAPS = false, bool SUB = false>
 __global__ void __launch_bounds__(64) cdekf4_mfma_kernel(FilterIO io, ModelArgs ma) {
     __shared__ double2 park[64];                                         // (S, innovation) of the chunk's steps, for the NLL
     const int lane = threadIdx.x;
@@ -343,12 +352,16 @@ __global__ void __launch_bounds__(64) cdekf4_mfma_kernel(FilterIO io, ModelArgs 
             const unsigned t = (unsigned)(t0 + slot);
             const double y = readlane_f64(ychunk, slot);
             double f = u, Pp = P;
-            rk4_lane(dt, f, Pp, [&](double tm, double tP, double& km, double& kP) {
+            auto rhs = [&](double tm, double tP, double& km, double& kP) {
                 double JT;
                 cd4_ekf_eval(R, K, Jc, fs, tm, km, JT);
                 const double JP = mfma4x4(JT, tP, 0.0);                  // sum_k J[r][k] P[k][q]
                 kP = mfma4x4(JP, K.ident, JP + K.gam);                   // (J P)^T + J P + gamma
-            });
+            };
+            if constexpr (SUB) {
+#pragma unroll 1
+                for (int j = 0; j < ma.substeps; j++) rk4_lane(dt, f, Pp, rhs);
+            } else rk4_lane(dt, f, Pp, rhs);
             double S, innov;
             mfma4_update_col<GAPS>(Pp, f, Hk, Hq, Xi, y, P, u, S, innov);
             park[slot] = make_double2(S, innov);
@@ -402,6 +415,13 @@ inline int launch_cdekf4_mfma(const FilterIO& io, const ModelArgs& ma, hipStream
     hipLaunchKernelGGL(cdekf4_mfma_kernel<GAPS>, dim3((unsigned)io.B), dim3(64), 0, stream, io, ma);
     return hip_rc(hipGetLastError());
 }
+template <bool GAPS>
+inline int launch_cdekf4_mfma_substeps(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
+    if (io.B <= 0 || io.T <= 0) return CGP_OK;
+    if (!mfma4_rows_fit(io.T)) return CGP_E_UNSUPPORTED;
+    hipLaunchKernelGGL((cdekf4_mfma_kernel<GAPS, true>), dim3((unsigned)io.B), dim3(64), 0, stream, io, ma);
+    return hip_rc(hipGetLastError());
+}
 inline int launch_cdeks4_mfma(const SmootherIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
     if (!mfma4_rows_fit(io.T)) return CGP_E_UNSUPPORTED;
@@ -432,6 +452,14 @@ inline int launch_cdsgp4_mfma(const FilterIO& io, const ModelArgs& ma, hipStream
         else hipLaunchKernelGGL((cdsgp4_mfma_kernel<SM, false, true>), dim3(grid), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
     } else if (two) hipLaunchKernelGGL((cdsgp4_mfma_kernel<SM, true, false>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
     else hipLaunchKernelGGL((cdsgp4_mfma_kernel<SM, false, false>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
+    return hip_rc(hipGetLastError());
+}
+template <class SM, bool GAPS>
+inline int launch_cdsgp4_mfma_substeps(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
+    if (io.B <= 0 || io.T <= 0) return CGP_OK;
+    if (!sgp4_mfma_fits(io.T, ma) || io.segs > 1) return CGP_E_UNSUPPORTED;          // (whole records only, route_filter)
+    if (ma.sg.n_groups > 16) hipLaunchKernelGGL((cdsgp4_mfma_kernel<SM, true, false, GAPS, true>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
+    else hipLaunchKernelGGL((cdsgp4_mfma_kernel<SM, false, false, GAPS, true>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
     return hip_rc(hipGetLastError());
 }
 template <class SM>

@@ -138,6 +138,19 @@ inline bool honours_gaps(FilterRoute r) {
     return r == FilterRoute::kGenericWave || r == FilterRoute::kGenericLane || r == FilterRoute::kGenericKpt || r == FilterRoute::kEkf4Mfma ||
            r == FilterRoute::kSgp4Mfma || r == FilterRoute::kCdEkf4Mfma || r == FilterRoute::kCdSgp4Mfma;
 }
+// CGP_RK4_SUBSTEPS (include/chirpgp_hip.h): likewise -- filter_kernel in both shapes on SubstepPredict (cgp_steps.hpp), which the generic
+// routes launch for a flagged call (cgp_inst_substeps_*.hip), and the one-wavefront-per-trial matrix-core kernels of cd_ekf and cd_sgp_filter
+// at d = 4, whose launchers take the SUB instantiation, with GAPS or without (cgp_inst_substeps4.hip).  The DPP kernels take one RK4 step
+// per sample: a flagged call is handed to the generic kernel of the shape it has.  The crossovers of flagged calls are unmeasured and go
+// by the generic limits whatever kernel they take, as those of CGP_SKIP_MISSING on these two methods do.
+inline int substeps_of(uint32_t flags) { return (int)((flags & CGP_RK4_SUBSTEPS_MASK) >> 16) + 1; }
+inline bool honours_substeps(FilterRoute r) {
+    return r == FilterRoute::kGenericWave || r == FilterRoute::kGenericLane || r == FilterRoute::kCdEkf4Mfma || r == FilterRoute::kCdSgp4Mfma;
+}
+constexpr const char* kSubstepsDiscrete = "CGP_RK4_SUBSTEPS goes with the continuous-discrete methods only (cd_ekf, cd_sgp_filter, cd_eks, cd_sgp_smoother): "
+                                          "a discrete model has no ODE to integrate";
+constexpr const char* kSubstepsSplit = "CGP_RK4_SUBSTEPS goes with cgp_filter, cgp_smoother and cgp_smoother_select only: the time-split kernels take one RK4 "
+                                       "step per sample";
 // the kernels that know the segments of a time-split launch (kEkf4Mfma: as kEkf4MfmaSeg)
 inline bool knows_segments(FilterRoute r) {
     return r == FilterRoute::kEkf4Mfma || r == FilterRoute::kSgp4Mfma || r == FilterRoute::kSgp8Coop || r == FilterRoute::kCdSgp4Mfma;
@@ -161,6 +174,7 @@ struct FilterDecision {
     int segs = 1;                    // effective: without the empty ones
     bool gaps = false;               // CGP_SKIP_MISSING: the launcher of a matrix-core route takes the kernel's GAPS instantiation
     int64_t seg_len = 0;
+    bool substeps = false;           // CGP_RK4_SUBSTEPS: the generic routes launch their SubstepPredict instantiation
 };
 
 inline WaveCandidate<FilterRoute> filter_wave_candidate(const FilterQuery& q) {
@@ -243,6 +257,13 @@ inline FilterDecision route_filter(const FilterQuery& q) {
                      : sig ? ShapeLimit{8, 1} : ShapeLimit{5, 2};
         wave.limit_lane4 = wave.limit;
     }
+    d.substeps = (q.flags & CGP_RK4_SUBSTEPS_MASK) != 0;
+    if (d.substeps) {
+        if (q.method != CGP_F_CD_EKF && q.method != CGP_F_CD_SGP) { d.rc = CGP_E_ARG; d.message = kSubstepsDiscrete; return d; }
+        if (q.segments > 1) return refuse(kSubstepsSplit);
+        if (!honours_substeps(wave.route)) wave.route = FilterRoute::kGenericWave;
+        wave.limit = wave.limit_lane4 = sig ? ShapeLimit{8, 1} : ShapeLimit{5, 2};      // unmeasured: the generic limits
+    }
     // ---- time-split with burn-in (cgp_filter_time_split): segments of whole 64-step chunks, one wavefront each
     if (q.segments > 1) {
         // (kept as found: admission goes by the REQUESTED segments -- a record too short to split is refused all the same where the
@@ -264,6 +285,7 @@ inline FilterDecision route_filter(const FilterQuery& q) {
     }
     FilterRoute lane = filter_lane_candidate(q, d.segs);
     if (d.gaps && !honours_gaps(lane)) lane = FilterRoute::kGenericLane;
+    if (d.substeps && !honours_substeps(lane)) lane = FilterRoute::kGenericLane;
     const bool lane4 = lane == FilterRoute::kLane4Ekf || lane == FilterRoute::kLane4Sgp;
     d.wave = choose_wave(q.num_cus, B, d.flags, lane4 ? wave.limit_lane4 : wave.limit, sig ? q.sigma : nullptr);
     // (kept as found: unreachable -- the segments set CGP_WAVE_PER_TRIAL, and the one thing that overrides it was refused above)
@@ -321,7 +343,14 @@ struct SmootherDecision {
     SmootherSelect select = SmootherSelect::kNone;
     WalkSplit split;                 // the exact time split of the cooperative walks (walk_segments); off on every other route
     int bsegs = 1, chunks_per_bseg = 0, burn_chunks = 0;      // time split with burn-in, as SmootherIO has them; bsegs <= 1: nothing is split
+    bool substeps = false;           // CGP_RK4_SUBSTEPS: kSdeLinear / kSdeHarm launch their SubstepSmooth instantiation
 };
+// CGP_RK4_SUBSTEPS on a smoother: smoother_kernel on SubstepSmooth (cgp_steps.hpp), one wavefront per trial whatever the batch -- the
+// interval's moments are a table in LDS, (d + d (d + 1) / 2) 16 doubles a wavefront (5.6 KB at d = 8), and 64 trials' tables do not fit.
+// The matrix-core, DPP and lane smoothers take one RK4 step per sample: a flagged call is handed to the generic kernel in that shape.
+inline bool honours_substeps(SmootherRoute r, bool wave) { return wave && (r == SmootherRoute::kSdeLinear || r == SmootherRoute::kSdeHarm); }
+// (the table is static LDS of the kernel, sized for n = 16 whatever the call's n: so is this admission figure)
+inline size_t substep_table_bytes(int d) { return sizeof(double) * (size_t)(d + d * (d + 1) / 2) * kMaxSubsteps; }      // cgp_steps.hpp: SubTable
 
 // ---- the exact time split of the discrete wave-per-trial smoothers
 // Whether a launch splits: when the batch leaves two thirds of the SIMDs idle, or on request (CGP_TIME_SPLIT, which also lets a
@@ -422,6 +451,18 @@ inline SmootherDecision route_smoother(const SmootherQuery& q) {
     auto refuse = [&d](int rc, const char* message) { d.rc = rc; d.message = message; return d; };
     d.wave = choose_wave(q.num_cus, q.io->B, q.flags, limit, sig ? q.sigma : nullptr);
     d.route = d.wave ? wave.route : lane;
+    d.substeps = (q.flags & CGP_RK4_SUBSTEPS_MASK) != 0;
+    if (d.substeps) {
+        if (q.method != CGP_S_CD_EKS && q.method != CGP_S_CD_SGP) return refuse(CGP_E_ARG, kSubstepsDiscrete);
+        if (q.segments > 1) return refuse(CGP_E_UNSUPPORTED, kSubstepsSplit);
+        if (q.flags & CGP_THREAD_PER_TRIAL)
+            return refuse(CGP_E_UNSUPPORTED, "CGP_RK4_SUBSTEPS: a smoother keeps the intermediate moments of an interval in LDS and runs one wavefront per trial only");
+        if (sig && SigmaSet::stage_bytes(q.sigma->s, q.sigma->d, q.sigma->n_groups, q.sigma->group_start != nullptr) + substep_table_bytes(q.model->d) >
+                       (size_t)kSigLdsMaxBytes)
+            return refuse(CGP_E_UNSUPPORTED, "CGP_RK4_SUBSTEPS: the sigma-point set does not fit the LDS stage beside the table of intermediate moments");
+        d.wave = true;
+        d.route = q.model->model_id == CGP_M_LINEAR_SDE ? SmootherRoute::kSdeLinear : SmootherRoute::kSdeHarm;
+    }
     if (q.want_sel) {
         if (writes_selection(d.route)) d.select = SmootherSelect::kKernel;
         else if (q.null_rows)

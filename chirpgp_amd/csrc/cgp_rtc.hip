@@ -1,5 +1,5 @@
-// cgp_rtc.hip -- models compiled at run time (hiprtc) into the generic lane-per-trial kernels: cgp_model_from_source, cgp_filter_custom,
-// cgp_smoother_custom.  See cgp_custom.hpp for the model interface.  libhiprtc is opened on first use (dlopen), so a process that never
+// cgp_rtc.hip -- models compiled at run time (hiprtc) into the generic lane-per-trial kernels (and, for an SDE model's smoothers with
+// CGP_RK4_SUBSTEPS, the one-wavefront-per-trial ones): cgp_model_from_source, cgp_filter_custom, cgp_smoother_custom.  See cgp_custom.hpp for the model interface.  libhiprtc is opened on first use (dlopen), so a process that never
 // builds a custom model never loads it.
 #include <dlfcn.h>
 #include <cstring>
@@ -13,6 +13,8 @@ struct cgp_custom_model {
     int device = 0;
     hipModule_t module = nullptr;
     hipFunction_t filter = nullptr, smoother = nullptr, sgp_filter = nullptr, sgp_smoother = nullptr;
+    // CGP_RK4_SUBSTEPS (CGP_CUSTOM_SDE only): SubstepPredict in the filters' one-lane-per-trial shape, SubstepSmooth with one wavefront per trial
+    hipFunction_t filter_sub = nullptr, smoother_sub = nullptr, sgp_filter_sub = nullptr, sgp_smoother_sub = nullptr;
 };
 
 namespace {
@@ -66,6 +68,13 @@ Verdict enqueue_custom(hipFunction_t kernel, IO& io, ModelArgs& ma, void* stream
     void* args[] = {&io, &ma};
     return hip_rc(hipModuleLaunchKernel(kernel, (unsigned)((io.B + 63) / 64), 1, 1, 64, 1, 1, 0, (hipStream_t)stream, args, nullptr));
 }
+// the second launch geometry, of a smoother with CGP_RK4_SUBSTEPS: one wavefront per trial, the sigma-point set staged in dynamic LDS
+Verdict enqueue_custom_wave(hipFunction_t kernel, SmootherIO& io, ModelArgs& ma, int d, bool sigma, void* stream) {
+    if (io.B > 0x7fffffffLL) return {CGP_E_UNSUPPORTED, "CGP_RK4_SUBSTEPS: a smoother runs one workgroup per trial: B must be < 2^31"};
+    void* args[] = {&io, &ma};
+    const unsigned dyn = sigma ? (unsigned)sigma_lds_bytes(ma, d) : 0u;
+    return hip_rc(hipModuleLaunchKernel(kernel, (unsigned)io.B, 1, 1, 64, 1, 1, dyn, (hipStream_t)stream, args, nullptr));
+}
 }  // namespace
 
 extern "C" {
@@ -92,7 +101,7 @@ int cgp_model_from_source(cgp_ctx* ctx, int kind, int32_t d, const char* body, c
     // their sizes travel with the code object and are compared after loading)
     src += "\n}\nextern \"C\" __device__ const unsigned cgp_rtc_abi[3] = {(unsigned)sizeof(cgp::FilterIO), (unsigned)sizeof(cgp::SmootherIO), (unsigned)sizeof(cgp::ModelArgs)};\n"
            "struct CgpUserModel {\n";
-    std::string f_name, s_name, sf_name, ss_name;
+    std::string f_name, s_name, sf_name, ss_name, fsub_name, ssub_name, sfsub_name, sssub_name;      // (sub: CGP_RK4_SUBSTEPS, SDE models)
     if (kind == CGP_CUSTOM_DISCRETE) {
         src += "    template <class T> __device__ static void mean(const T* u, const double* p, double dt, T* m) { cgp_user::cond_mean(u, p, dt, m); }\n"
                "    __device__ static void cov(const double* u, const double* p, double dt, double* c) { cgp_user::cond_cov(u, p, dt, c); }\n};\n"
@@ -112,11 +121,16 @@ int cgp_model_from_source(cgp_ctx* ctx, int kind, int32_t d, const char* body, c
         s_name = "cgp::smoother_kernel<cgp::CdEksStep<CgpUserM, false>>";
         sf_name = "cgp::filter_kernel<cgp::CdSgpPredict<CgpUserM, false>, cgp::LinearMeasurement<" + D + ">>";
         ss_name = "cgp::smoother_kernel<cgp::CdSgpsStep<CgpUserM, false>>";
+        fsub_name = "cgp::filter_kernel<cgp::SubstepPredict<cgp::CdEkfPredict<CgpUserM, false>>, cgp::LinearMeasurement<" + D + ">>";
+        ssub_name = "cgp::smoother_kernel<cgp::SubstepSmooth<cgp::CdEksStep<CgpUserM, true>>>";
+        sfsub_name = "cgp::filter_kernel<cgp::SubstepPredict<cgp::CdSgpPredict<CgpUserM, false>>, cgp::LinearMeasurement<" + D + ">>";
+        sssub_name = "cgp::smoother_kernel<cgp::SubstepSmooth<cgp::CdSgpsStep<CgpUserM, true>>>";
     }
     void* prog = nullptr;
     if (R.CreateProgram(&prog, src.c_str(), "cgp_custom_model.hip", 0, nullptr, nullptr) != 0) return fail(ctx, CGP_E_HIP, "hiprtcCreateProgram failed");
     auto done = [&](int code, const std::string& msg) { R.DestroyProgram(&prog); return fail(ctx, code, msg); };
-    const std::string* names[4] = {&f_name, &s_name, &sf_name, &ss_name};
+    constexpr int kNames = 8;
+    const std::string* names[kNames] = {&f_name, &s_name, &sf_name, &ss_name, &fsub_name, &ssub_name, &sfsub_name, &sssub_name};
     for (const std::string* n : names)
         if (!n->empty() && R.AddNameExpression(prog, n->c_str()) != 0) return done(CGP_E_HIP, "hiprtcAddNameExpression failed");
     const std::string arch = std::string("--offload-arch=") + prop.gcnArchName;
@@ -130,18 +144,18 @@ int cgp_model_from_source(cgp_ctx* ctx, int kind, int32_t d, const char* body, c
         if (log.size() > 6000) log.resize(6000);
         return done(CGP_E_ARG, "the model source does not compile:\n" + log);
     }
-    const char* low[4] = {nullptr, nullptr, nullptr, nullptr};
+    const char* low[kNames] = {};
     size_t size = 0;
-    for (int i = 0; i < 4; i++)
+    for (int i = 0; i < kNames; i++)
         if (!names[i]->empty() && R.GetLoweredName(prog, names[i]->c_str(), &low[i]) != 0) return done(CGP_E_HIP, "hiprtc: no lowered name");
     if (R.GetCodeSize(prog, &size) != 0) return done(CGP_E_HIP, "hiprtc: no code");
     std::vector<char> code(size);
     if (R.GetCode(prog, code.data()) != 0) return done(CGP_E_HIP, "hiprtcGetCode failed");
     cgp_custom_model* m = new cgp_custom_model;
     m->kind = kind; m->d = d; m->device = ctx->device;
-    hipFunction_t* fns[4] = {&m->filter, &m->smoother, &m->sgp_filter, &m->sgp_smoother};
+    hipFunction_t* fns[kNames] = {&m->filter, &m->smoother, &m->sgp_filter, &m->sgp_smoother, &m->filter_sub, &m->smoother_sub, &m->sgp_filter_sub, &m->sgp_smoother_sub};
     bool loaded = hipModuleLoadData(&m->module, code.data()) == hipSuccess;
-    for (int i = 0; loaded && i < 4; i++)
+    for (int i = 0; loaded && i < kNames; i++)
         if (low[i]) loaded = hipModuleGetFunction(fns[i], m->module, low[i]) == hipSuccess;
     if (!loaded) {
         const std::string why = hipGetErrorString(hipGetLastError());
@@ -185,7 +199,10 @@ int cgp_filter_custom(cgp_ctx* ctx, const cgp_custom_model* m, const cgp_sigma* 
     ModelArgs ma;
     const Verdict prepared = prepare_filter_custom(custom_model(m, false), sigma, params, param_stride, gamma, gamma_stride, init, dt, ys, ys_stride, ys_repeat,
                                                    ys_index, B, T, mfs, Pfs, nll, flags, host_of(ctx), io, ma);
-    return launch_on(ctx, prepared, kLaunchLocked, [&]() -> Verdict { return enqueue_custom(sigma ? m->sgp_filter : m->filter, io, ma, stream); });
+    return launch_on(ctx, prepared, kLaunchLocked, [&]() -> Verdict {
+        if (ma.substeps > 1) return enqueue_custom(sigma ? m->sgp_filter_sub : m->filter_sub, io, ma, stream);
+        return enqueue_custom(sigma ? m->sgp_filter : m->filter, io, ma, stream);
+    });
 }
 
 int cgp_smoother_custom(cgp_ctx* ctx, const cgp_custom_model* m, const cgp_sigma* sigma, const double* params, int64_t param_stride, const double* gamma, int64_t gamma_stride,
@@ -195,7 +212,10 @@ int cgp_smoother_custom(cgp_ctx* ctx, const cgp_custom_model* m, const cgp_sigma
     ModelArgs ma;
     const Verdict prepared = prepare_smoother_custom(custom_model(m, true), sigma, params, param_stride, gamma, gamma_stride, dt, mfs, Pfs, B, T, mss, Pss, flags,
                                                      host_of(ctx), io, ma);
-    return launch_on(ctx, prepared, kLaunchLocked, [&]() -> Verdict { return enqueue_custom(sigma ? m->sgp_smoother : m->smoother, io, ma, stream); });
+    return launch_on(ctx, prepared, kLaunchLocked, [&]() -> Verdict {
+        if (ma.substeps > 1) return enqueue_custom_wave(sigma ? m->sgp_smoother_sub : m->smoother_sub, io, ma, m->d, sigma != nullptr, stream);
+        return enqueue_custom(sigma ? m->sgp_smoother : m->smoother, io, ma, stream);
+    });
 }
 
 }  // extern "C"

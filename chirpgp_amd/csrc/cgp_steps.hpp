@@ -531,8 +531,21 @@ struct ModelArgs {
     const double* __restrict__ params; int64_t param_stride;
     const double* __restrict__ gamma;  int64_t gamma_stride;
     int model_id;
+    int substeps;       // CGP_RK4_SUBSTEPS: n, 1 .. 16; read by SubstepPredict / SubstepSmooth alone (in what was padding: no other member moves)
     SigmaSet sg;
-    double dt;
+    double dt;          // a flagged continuous-discrete call: the substep h = dt / n, divided once on the host (cgp_args.hpp)
+};
+
+// CGP_RK4_SUBSTEPS (include/chirpgp_hip.h): SubstepPredict and SubstepSmooth below wrap the four continuous-discrete steps and take
+// n = ModelArgs::substeps RK4 steps of ModelArgs::dt = h per measurement interval.  They are instantiations of their own, in units of their
+// own (cgp_inst_substeps_*.hip); the steps they wrap are untouched.
+// Whether a step type is such a wrapper (the others have no SUB member):
+template <class S, class = void> struct IsSubstepped { static constexpr bool value = false; };
+template <class S> struct IsSubstepped<S, decltype((void)S::SUB)> { static constexpr bool value = S::SUB; };
+// the moments (m_kj, P_kj), j = 0 .. n - 1, of a smoother's interval: one wavefront's table in LDS (smoother_kernel)
+constexpr int kMaxSubsteps = 16;
+template <int D> struct SubTable {
+    static constexpr int ROW = D + D * (D + 1) / 2, DOUBLES = ROW * kMaxSubsteps;
 };
 
 // ============================================================================================== FILTER PREDICTORS
@@ -635,6 +648,22 @@ template <class SM, bool WAVE_> struct CdSgpPredict {
     }
 };
 
+// CGP_RK4_SUBSTEPS: either predictor with n = ModelArgs::substeps RK4 steps of ModelArgs::dt = h from (mf, Pf), in both launch shapes
+template <class Base> struct SubstepPredict : Base {
+    static constexpr int D = Base::D;
+    static constexpr bool SUB = true;
+    int n;
+    CGP_DEV void setup(const ModelArgs& a, int64_t trial) { Base::setup(a, trial); n = a.substeps; }
+    CGP_DEV void predict(int lane, double* lds, const Vec<D>& mf, const Sym<D>& Pf, Vec<D>& mp, Sym<D>& Pp) const {
+        Vec<D> m = mf; Sym<D> P = Pf;
+#pragma unroll 1
+        for (int j = 0; j < n; j++) {
+            Base::predict(lane, lds, m, P, mp, Pp);
+            m = mp; P = Pp;
+        }
+    }
+};
+
 // ============================================================================================== SMOOTHER STEPS
 // step(lane, lds, mf, Pf, ms, Ps): (ms, Ps) at k+1 -> (ms, Ps) at k, given the filtering result (mf, Pf) at k.
 
@@ -704,6 +733,14 @@ template <class SM, bool WAVE_> struct CdEksStep {
             sym_from_sum<D>(T, gamma, -1.0, dP);          // A P + P A^T - gamma
         }, ms, Ps, dt);
     }
+    // one RK4 step of length h of cd_ekf's moment ODE (CdEkfPredict), for SubstepSmooth
+    CGP_DEV void forward(int, double*, Vec<D>& m, Sym<D>& P, double h) const {
+        rk4_m_cov<D>([&](const Vec<D>& m_, const Sym<D>& P_, Vec<D>& dm, Sym<D>& dP) {
+            Mat<D> T;
+            model.drift_jp(m_, P_, dm, T);
+            sym_from_sum<D>(T, gamma, 1.0, dP);
+        }, m, P, h);
+    }
 };
 
 // cd_sgp_smoother (filters_smoothers.py:611-629)
@@ -732,6 +769,52 @@ template <class SM, bool WAVE_> struct CdSgpsStep {
             CGP_UNROLL for (int i = 0; i < D; i++)
                 CGP_UNROLL for (int j = 0; j <= i; j++) dP(i, j) = (dP(i, j) + (T.a[i][j] + T.a[j][i])) - 2.0 * gamma(i, j);
         }, ms, Ps, dt);
+    }
+    // one RK4 step of length h of cd_sgp_filter's moment ODE (CdSgpPredict), for SubstepSmooth
+    CGP_DEV void forward(int lane, double* lds, Vec<D>& m, Sym<D>& P, double h) const {
+        rk4_m_cov<D>([&](const Vec<D>& m_, const Sym<D>& P_, Vec<D>& dm, Sym<D>& dP) {
+            cd_sgp_common<SM, WAVE>(model, sg, lane, lds, gamma, m_, P_, dm, dP);
+        }, m, P, h);
+    }
+};
+
+// CGP_RK4_SUBSTEPS: either continuous-discrete smoother step with n substeps, one wavefront per trial.  The backward substep j (from the
+// moments after j + 1 forward substeps to those after j) is Base's step held against (m_kj, P_kj) in place of (mf_k, Pf_k), and the filter
+// does not store those: the step first integrates the interval forward from (mf, Pf) with the filter's moment ODE (Base::forward), n - 1 RK4
+// steps of h, and keeps each result in the wavefront's LDS table -- indexed at run time, which a register array would answer with scratch --;
+// then it walks the table backwards.  The forward pass runs redundantly on all 64 lanes and lane 0 writes its rows: that every lane would
+// have written the same bits rests on the WAVE = true contract of this file -- everything outside the fan is computed identically by all
+// lanes, and wave_allreduce hands every lane bitwise-identical totals (CdSgpsStep's fan).
+template <class Base> struct SubstepSmooth : Base {
+    static_assert(Base::WAVE, "the tables of 64 trials' intermediate moments do not fit LDS: one wavefront per trial only");
+    static constexpr int D = Base::D;
+    static constexpr bool SUB = true;
+    int n; double* tab;
+    CGP_DEV void setup(const ModelArgs& a, int64_t trial) { Base::setup(a, trial); n = a.substeps; }
+    CGP_DEV void attach(double* table) { tab = table; }      // (smoother_kernel)
+    CGP_DEV void step(int lane, double* lds, const Vec<D>& mf, const Sym<D>& Pf, Vec<D>& ms, Sym<D>& Ps) const {
+        constexpr int ROW = SubTable<D>::ROW, NS = Sym<D>::N;
+        // rows 0 .. n - 1: (mf, Pf) and the moments after 1 .. n - 1 forward substeps (row 0 too, so that nothing of the forward pass
+        // stays in registers across the backward one)
+        Vec<D> m = mf; Sym<D> P = Pf;
+#pragma unroll 1
+        for (int j = 0; j < n; j++) {
+            if (j > 0) this->forward(lane, lds, m, P, -this->dt);          // (Base::dt is -h)
+            if (lane == 0) {
+                double* row = tab + j * ROW;
+                CGP_UNROLL for (int i = 0; i < D; i++) row[i] = m.v[i];
+                CGP_UNROLL for (int i = 0; i < NS; i++) row[D + i] = P.a[i];
+            }
+        }
+        wave_lds_fence();
+#pragma unroll 1
+        for (int j = n - 1; j >= 0; j--) {
+            const double* row = tab + j * ROW;
+            CGP_UNROLL for (int i = 0; i < D; i++) m.v[i] = row[i];
+            CGP_UNROLL for (int i = 0; i < NS; i++) P.a[i] = row[D + i];
+            Base::step(lane, lds, m, P, ms, Ps);
+        }
+        wave_lds_fence();                          // the next step's writes stay behind these reads
     }
 };
 

@@ -10,6 +10,9 @@ filters_smoothers.py:26-36).  Differences a caller sees:
 * NumPy in -> NumPy out, torch CUDA tensors in -> torch CUDA tensors out (results stay in HBM);
 * every filter takes ``missing='skip'``: a NaN measurement is then a missing sample (the prediction is the step's result, its NLL
   increment exactly 0) instead of the reference's poison -- records with dropped samples, gated segments or a tail to forecast;
+* ``cd_ekf``, ``cd_eks``, ``cd_sgp_filter`` and ``cd_sgp_smoother`` take ``substeps=n`` (1 .. 16, default 1: the reference): n RK4 steps of
+  dt / n between two measurements, so that the sampling period of the record no longer fixes the step of the integrator; a smoother takes
+  the n its filter ran with.  Run-time compiled SDE models (custom_sde) take it too; not with ``time_split``;
 * ``rts_sample``, ``eks_sample`` and ``sgp_smoother_sample`` (no counterpart in the reference) draw joint posterior sample paths from the
   discrete smoothers by backward simulation.
 """
@@ -95,7 +98,7 @@ def eks(cond_m_cov, mfs, Pfs, dt, **kw):
     """Extended Kalman smoother (filters_smoothers.py:317-349)."""
     spec = _discrete(cond_m_cov, dt)
     if isinstance(spec, M.CustomDiscrete):
-        return E.run_smoother_custom(spec, None, dt, mfs, Pfs, **_custom_kw(kw, ('flags',)))
+        return E.run_smoother_custom(spec, None, dt, mfs, Pfs, **_custom_kw(kw, ('flags', 'substeps')))
     return E.run_smoother(E.S_EKS, _discrete(cond_m_cov, dt), None, None, dt, mfs, Pfs, **kw)
 
 
@@ -109,7 +112,7 @@ def cd_ekf(a, b, H, Xi, m0, P0, dt, ys, **kw):
 def cd_eks(a, b, mfs, Pfs, dt, **kw):
     """Continuous-discrete EKS (filters_smoothers.py:400-443)."""
     if isinstance(a, M.CustomDrift):
-        return E.run_smoother_custom(a, _gamma_from_callable(b), dt, mfs, Pfs, **_custom_kw(kw, ('flags',)))
+        return E.run_smoother_custom(a, _gamma_from_callable(b), dt, mfs, Pfs, **_custom_kw(kw, ('flags', 'substeps')))
     return E.run_smoother(E.S_CD_EKS, _drift(a), None, _gamma_from_callable(b), dt, mfs, Pfs, **kw)
 
 
@@ -125,7 +128,7 @@ def sgp_smoother(cond_m_cov, sgps, mfs, Pfs, dt, **kw):
     """Sigma-point smoother (filters_smoothers.py:493-531)."""
     spec = _discrete(cond_m_cov, dt)
     if isinstance(spec, M.CustomDiscrete):
-        return E.run_smoother_custom(spec, None, dt, mfs, Pfs, sgps=_sgps(sgps, spec.d), **_custom_kw(kw, ('flags',)))
+        return E.run_smoother_custom(spec, None, dt, mfs, Pfs, sgps=_sgps(sgps, spec.d), **_custom_kw(kw, ('flags', 'substeps')))
     return E.run_smoother(E.S_SGP, spec, _sgps(sgps, spec.d), None, dt, mfs, Pfs, **kw)
 
 
@@ -141,7 +144,7 @@ def cd_sgp_smoother(a, b, sgps, mfs, Pfs, dt, **kw):
     """Continuous-discrete sigma-point smoother (filters_smoothers.py:585-632)."""
     spec = _drift(a)
     if isinstance(spec, M.CustomDrift):
-        return E.run_smoother_custom(spec, _gamma_from_matrix(b), dt, mfs, Pfs, sgps=_sgps(sgps, spec.d), **_custom_kw(kw, ('flags',)))
+        return E.run_smoother_custom(spec, _gamma_from_matrix(b), dt, mfs, Pfs, sgps=_sgps(sgps, spec.d), **_custom_kw(kw, ('flags', 'substeps')))
     return E.run_smoother(E.S_CD_SGP, spec, _sgps(sgps, spec.d), _gamma_from_matrix(b), dt, mfs, Pfs, **kw)
 
 
@@ -180,7 +183,7 @@ def sgp_smoother_sample(cond_m_cov, sgps, mfs, Pfs, dt, n_samples, **kw):
     return E.run_smoother_sample(E.S_SGP, spec, _sgps(sgps, spec.d), dt, mfs, Pfs, n_samples, **kw)
 
 
-def _custom_kw(kw, allowed=('nll_final_only', 'want', 'flags', 'missing')):
+def _custom_kw(kw, allowed=('nll_final_only', 'want', 'flags', 'missing', 'substeps')):
     """Keywords a runtime-compiled model understands (one launch shape, dense records); anything else is refused by name."""
     extra = set(kw) - set(allowed)
     if extra:

@@ -25,7 +25,25 @@ def _rows_per_record(G, ys, record_index):
     return G // n_rec
 
 
-def batched_nll(method, build, thetas, ys, Xi, dt, sgps=None, record_index=None, *, missing=None, **build_kw):
+def _substeps_kw(method, substeps):
+    """``substeps`` of an objective -> the filters' keyword.  1 .. 16, and more than one for 'cd_ekf' and 'cd_sgp_filter' only: checked here,
+    before anything is built or launched."""
+    from chirpgp_amd import _engine as E
+    if not E.rk4_substeps(substeps):
+        return {}
+    if method not in ('cd_ekf', 'cd_sgp_filter'):
+        raise ValueError(f"substeps goes with method 'cd_ekf' and 'cd_sgp_filter' only, not with {method!r}: a discrete model has no ODE to integrate")
+    return dict(substeps=int(substeps))
+
+
+def _exact_with_substeps(exact, method, substeps):
+    """``exact`` of an objective with RK4 substeps: unchanged -- the tangent kernel of cd_ekf takes the substeps, and what has no exact
+    gradient without them ('cd_sgp_filter') has none with them.  The count and the method are checked here, before anything is built."""
+    _substeps_kw(method, substeps)
+    return exact
+
+
+def batched_nll(method, build, thetas, ys, Xi, dt, sgps=None, record_index=None, *, missing=None, substeps=1, **build_kw):
     """Final cumulative NLL of ``method`` for every row of ``thetas`` (unconstrained parameters, g() maps them to the
     positive model parameters as in the reference).  ``ys`` is ONE record (T,) read by all G rows, or R records (R, T) of
     which each serves G / R consecutive rows (``record_index`` (n,) first picks n of them: G / n rows each).  The records
@@ -36,10 +54,11 @@ def batched_nll(method, build, thetas, ys, Xi, dt, sgps=None, record_index=None,
     build_harmonic_chirp_model, build_lascala_model), or 'ekf_for_kpt' with models.build_kpt_chirp_model (pass ``fs=``,
     ``num_harmonics=``): tetralith/jobs/kpt_mle.py:41-44.
 
-    ``missing='skip'``: NaN samples of the records are gaps (filters_smoothers: the likelihood of the observed samples alone)."""
+    ``missing='skip'``: NaN samples of the records are gaps (filters_smoothers: the likelihood of the observed samples alone).
+    ``substeps=n`` ('cd_ekf', 'cd_sgp_filter'): n RK4 steps of dt / n between two measurements (filters_smoothers)."""
     thetas = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
     kw = dict(nll_final_only=True, want=(False, False, True), trials_per_record=_rows_per_record(thetas.shape[0], ys, record_index),
-              record_index=record_index, missing=missing)
+              record_index=record_index, missing=missing, **_substeps_kw(method, substeps))
     with np.errstate(all='ignore'):        # a probe whose parameters under- or overflow yields a NaN objective, which the line search rejects
         built = build(M.g(thetas), **build_kw)
     if method == 'ekf_for_kpt':
@@ -263,7 +282,7 @@ def _fisher_unsupported(method):
                       '(value_grad_fisher, standard_errors and fit_scoring take the discrete EKF and the sigma-point filter)')
 
 
-def _tangent_launch(fisher, build, thetas, ys, Xi, dt, record_index, method, sgps, missing=None):
+def _tangent_launch(fisher, build, thetas, ys, Xi, dt, record_index, method, sgps, missing=None, substeps=1):
     """One launch of a tangent kernel along tangent_directions at every row of thetas: (nll, grad) or, fisher, (nll, grad, F) as NumPy.
     ``missing='skip'``: NaN samples of the records are gaps (CGP_SKIP_MISSING: such a step adds exactly nothing to any of the three)."""
     from chirpgp_amd import _engine as E
@@ -277,7 +296,7 @@ def _tangent_launch(fisher, build, thetas, ys, Xi, dt, record_index, method, sgp
         drift, disp, disc, m0, P0, H = build(M.g(thetas))
     if method == 'cd_ekf':
         out = E.run_cd_ekf_nll_grad(drift, disp.outer(), H, Xi, m0, P0, dt, ys, tangent_directions_cd(build, thetas, dt, Xi),
-                                    trials_per_record=rows, record_index=record_index, missing=missing)
+                                    trials_per_record=rows, record_index=record_index, missing=missing, substeps=substeps)
         return tuple(o.cpu().numpy() for o in out)
     dirs = tangent_directions(build, thetas, dt, Xi)
     if method == 'sgp_filter':
@@ -289,14 +308,16 @@ def _tangent_launch(fisher, build, thetas, ys, Xi, dt, record_index, method, sgp
     return tuple(o.cpu().numpy() for o in out)
 
 
-def value_and_grad(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf', sgps=None, missing=None):
+def value_and_grad(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf', sgps=None, missing=None, substeps=1):
     """Objective and its EXACT gradient (forward tangents through the scan) at every row of thetas (G, P), in ONE launch: the EKF's
     (method='ekf', cgp_ekf_nll_grad: G P lanes), the continuous-discrete EKF's (method='cd_ekf', cgp_cd_ekf_nll_grad: G P lanes, the
     tangent carried through the four RK4 stages of every step) or the sigma-point filter's (method='sgp_filter' with a d = 4 SigmaPoints
     ``sgps``, cgp_sgp_nll_grad: G wavefronts).  ys (T,) or (R, T) shared out evenly over the rows as in batched_nll.  -> (nll (G,), grad (G, P)).
     ``missing='skip'``: NaN samples of the records are gaps, as in batched_nll -- the likelihood of the observed samples alone and its
-    exact gradient; a record of NaN only gives 0 and a zero gradient."""
-    return _tangent_launch(False, build, thetas, ys, Xi, dt, record_index, method, sgps, missing)
+    exact gradient; a record of NaN only gives 0 and a zero gradient.  ``substeps=n`` (method='cd_ekf'): n RK4 steps of dt / n between two
+    measurements, as in batched_nll -- the tangent goes through every one of them."""
+    _exact_with_substeps(True, method, substeps)
+    return _tangent_launch(False, build, thetas, ys, Xi, dt, record_index, method, sgps, missing, substeps)
 
 
 def value_grad_fisher(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf', sgps=None, missing=None):
@@ -441,15 +462,16 @@ def fit_scoring(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=100,
     return M.g(x), dict(fun=f, grad=g, nit=nit, launches=launches, converged=converged, fisher=F, mu=mu, history=history, iterates=iterates)
 
 
-def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=None, *, missing=None, **build_kw):
+def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=None, *, missing=None, substeps=1, **build_kw):
     """-> fun(theta) returning (nll, gradient): value and central differences from one batched launch of 2 P + 1 filter passes, or --
     ``exact=True``, the discrete EKF, the continuous-discrete EKF ('cd_ekf') or the sigma-point filter (with a d = 4 ``sgps``) on the chirp /
     La Scala models -- value and EXACT
     gradient from one launch of a tangent kernel (cgp_ekf_nll_grad: within 8e-13 of the gradient's scale against 100-digit arithmetic where
     the differences carry 2e-7; slower for a single record, see EXACT_FROM_RECORDS; cgp_sgp_nll_grad).  exact=None takes the tangent kernel
     for the EKF from EXACT_FROM_RECORDS records only and never for the sigma-point filter.  ``missing='skip'`` (a record with gaps):
-    differences only."""
-    exact = _exact_with_gaps(exact, missing)
+    differences only.  ``substeps=n`` ('cd_ekf', 'cd_sgp_filter'): n RK4 steps of dt / n between two measurements, in either form of the
+    gradient ('cd_ekf' has the exact one)."""
+    exact = _exact_with_substeps(_exact_with_gaps(exact, missing), method, substeps)
     if exact is None:
         exact = _exact_by_default(method, build, Xi, 1, build_kw)
     if exact:
@@ -459,7 +481,7 @@ def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=No
         ys_dev = E.dev(ys)
 
         def fun_exact(theta):
-            f, g_ = value_and_grad(build, np.asarray(theta, dtype=np.float64)[None, :], ys_dev, Xi, dt, method=method, sgps=sgps)
+            f, g_ = value_and_grad(build, np.asarray(theta, dtype=np.float64)[None, :], ys_dev, Xi, dt, method=method, sgps=sgps, substeps=substeps)
             if not np.isfinite(f[0]):                   # diverged filter: the reference writes NaN results and moves on
                 return np.inf, np.zeros(np.size(theta))
             return float(f[0]), np.where(np.isfinite(g_[0]), g_[0], 0.0)
@@ -473,7 +495,7 @@ def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=No
         for i in range(P):
             batch[1 + 2 * i, i] += h[i]
             batch[2 + 2 * i, i] -= h[i]
-        nll = batched_nll(method, build, batch, ys, Xi, dt, sgps, missing=missing, **build_kw)
+        nll = batched_nll(method, build, batch, ys, Xi, dt, sgps, missing=missing, substeps=substeps, **build_kw)
         grad = (nll[1::2] - nll[2::2]) / (2 * h)
         f = float(nll[0])
         if not np.isfinite(f):                      # diverged filter: the reference writes NaN results and moves on
@@ -486,7 +508,7 @@ def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=No
 DIFFERENCE_STOP = dict(ftol=1e-13, gtol=1e-7)
 
 
-def fit(method, build, init_params, ys, Xi, dt, sgps=None, maxiter=200, exact=None, *, missing=None, **build_kw):
+def fit(method, build, init_params, ys, Xi, dt, sgps=None, maxiter=200, exact=None, *, missing=None, substeps=1, **build_kw):
     """L-BFGS-B from ``init_params`` (positive model parameters, e.g. [0.1, 0.1, 0.1, 1, 1, 7]).
     Returns (opt_params, scipy OptimizeResult).
 
@@ -496,30 +518,30 @@ def fit(method, build, init_params, ys, Xi, dt, sgps=None, maxiter=200, exact=No
     the last place, what any re-ordering of the filter's arithmetic does) moved the parameters at which it stopped by up to 2.2e-3 of
     their value, seven runs, although every NLL agreed to 1e-7.  With ftol 1e-13 and gtol 1e-7 the same seven runs end within 1.7e-4 of
     the optimum, for 60 - 85 objective launches where the default took 45 - 55.  (The tangent kernels' searches, exact=True, keep
-    SciPy's rule.)"""
+    SciPy's rule.)  ``substeps`` as in :func:`make_objective`."""
     from scipy.optimize import minimize
-    exact = _exact_with_gaps(exact, missing)
+    exact = _exact_with_substeps(_exact_with_gaps(exact, missing), method, substeps)
     if exact is None:
         exact = _exact_by_default(method, build, Xi, 1, build_kw)
-    fun = make_objective(method, build, ys, Xi, dt, sgps, exact=exact, missing=missing, **build_kw)
+    fun = make_objective(method, build, ys, Xi, dt, sgps, exact=exact, missing=missing, substeps=substeps, **build_kw)
     stop = {} if exact else DIFFERENCE_STOP
     res = minimize(fun, M.g_inv(np.asarray(init_params, dtype=np.float64)), jac=True, method='L-BFGS-B',
                    options=dict(maxiter=maxiter, **stop))
     return M.g(res.x), res
 
 
-def _value_and_grad_many(method, build, thetas, yss, Xi, dt, sgps, rel_step, build_kw, record_index=None, exact=None, missing=None):
+def _value_and_grad_many(method, build, thetas, yss, Xi, dt, sgps, rel_step, build_kw, record_index=None, exact=None, missing=None, substeps=1):
     """NLL and gradient of R records (the rows ``record_index`` of yss; all of them by default) at R parameter vectors: exact (the tangent
     kernel, R P lanes) for the discrete EKF on the chirp / La Scala models (and, with exact=True, the sigma-point filter's, R wavefronts),
     else central differences -- ONE launch of R (2 P + 1) trials, each record read in place by its 2 P + 1 probes."""
     R, P = thetas.shape
-    exact = _exact_with_gaps(exact, missing)
+    exact = _exact_with_substeps(_exact_with_gaps(exact, missing), method, substeps)
     if exact is None:
         exact = _exact_by_default(method, build, Xi, R, build_kw)
     if exact:
         if not has_exact_gradient(method, build, Xi, sgps) or build_kw:
             raise _exact_unsupported()
-        f, grad = value_and_grad(build, thetas, yss, Xi, dt, record_index=record_index, method=method, sgps=sgps)
+        f, grad = value_and_grad(build, thetas, yss, Xi, dt, record_index=record_index, method=method, sgps=sgps, substeps=substeps)
         f = f.copy()
         f[~np.isfinite(f)] = np.inf
         return f, np.where(np.isfinite(grad), grad, 0.0)
@@ -528,7 +550,8 @@ def _value_and_grad_many(method, build, thetas, yss, Xi, dt, sgps, rel_step, bui
     idx = np.arange(P)
     batch[:, 1 + 2 * idx, idx] += h
     batch[:, 2 + 2 * idx, idx] -= h
-    nll = batched_nll(method, build, batch.reshape(-1, P), yss, Xi, dt, sgps, record_index=record_index, missing=missing, **build_kw).reshape(R, 2 * P + 1)
+    nll = batched_nll(method, build, batch.reshape(-1, P), yss, Xi, dt, sgps, record_index=record_index, missing=missing, substeps=substeps,
+                      **build_kw).reshape(R, 2 * P + 1)
     f = nll[:, 0].copy()
     grad = (nll[:, 1::2] - nll[:, 2::2]) / (2 * h)
     f[~np.isfinite(f)] = np.inf
@@ -536,7 +559,7 @@ def _value_and_grad_many(method, build, thetas, yss, Xi, dt, sgps, rel_step, bui
 
 
 def fit_many(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=200, history=10, gtol=1e-5, ftol=2.2e-9,
-             rel_step=1e-6, exact=None, *, missing=None, **build_kw):
+             rel_step=1e-6, exact=None, *, missing=None, substeps=1, **build_kw):
     """Maximum likelihood for R measurement records in lock step: limited-memory BFGS with a backtracking (Armijo) line
     search, every record with its own iterate, history and step length, and every probe of every record evaluated in
     the SAME kernel launch (R x 13 trials for the chirp model).  A launch costs T x 0.35 us whatever the batch up to
@@ -544,15 +567,16 @@ def fit_many(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=200, hi
     run one L-BFGS-B per record.  Same objective, same unconstrained parametrisation g() as :func:`fit`.
 
     yss (R, T);  init_params (P,) or (R, P) positive model parameters  ->  (opt_params (R, P), info dict).
-    ``missing='skip'``: NaN samples of the records are gaps (difference gradient only, as in :func:`make_objective`)."""
+    ``missing='skip'``: NaN samples of the records are gaps (difference gradient only, as in :func:`make_objective`); ``substeps`` likewise."""
     from chirpgp_amd import _engine as E
-    yss = E.dev(yss)                                  # uploaded once; every probe of every line search reads it in place
+    _substeps_kw(method, substeps)                    # a count or a method that cannot take it fails here, before anything is copied
+    yss = E.dev(yss)                                 # uploaded once; every probe of every line search reads it in place
     if yss.ndim == 1:
         yss = yss[None, :]
     R = yss.shape[0]
     x = np.array(np.broadcast_to(M.g_inv(np.asarray(init_params, dtype=np.float64)), (R, np.shape(init_params)[-1])))
     P = x.shape[1]
-    f, g = _value_and_grad_many(method, build, x, yss, Xi, dt, sgps, rel_step, build_kw, exact=exact, missing=missing)
+    f, g = _value_and_grad_many(method, build, x, yss, Xi, dt, sgps, rel_step, build_kw, exact=exact, missing=missing, substeps=substeps)
     S, Y = [], []                                    # lists of (R, P) pairs, newest last
     done = ~np.isfinite(f)
     nit = np.zeros(R, dtype=int)
@@ -587,7 +611,8 @@ def fit_many(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=200, hi
                 break
             idx = np.flatnonzero(searching)
             xt = x[idx] + step[idx, None] * d[idx]
-            ft, gt = _value_and_grad_many(method, build, xt, yss, Xi, dt, sgps, rel_step, build_kw, record_index=idx, exact=exact, missing=missing)
+            ft, gt = _value_and_grad_many(method, build, xt, yss, Xi, dt, sgps, rel_step, build_kw, record_index=idx, exact=exact, missing=missing,
+                                          substeps=substeps)
             launches += 1
             ok = ft <= f[idx] + 1e-4 * step[idx] * gd[idx]
             acc = idx[ok]
@@ -608,7 +633,7 @@ def fit_many(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=200, hi
     return M.g(x), dict(fun=f, grad=g, nit=nit, launches=launches, converged=done)
 
 
-def grid_search(method, build, grid, yss, Xi, dt, sgps=None, **build_kw):
+def grid_search(method, build, grid, yss, Xi, dt, sgps=None, *, substeps=1, **build_kw):
     """Parameter-grid MLE sweep (BASELINE config C5: "batch x param-grid MLE sweep"): the final NLL of ``method`` at every
     grid point for every record, in ONE launch of R G trials -- G parameter vectors per record, each record read in place.
 
@@ -618,7 +643,7 @@ def grid_search(method, build, grid, yss, Xi, dt, sgps=None, **build_kw):
     G = grid.shape[0]
     R = 1 if np.ndim(yss) == 1 else int(np.shape(yss)[0])
     thetas = np.tile(M.g_inv(grid), (R, 1))                     # record-major: the G rows of a record are consecutive trials
-    nll = batched_nll(method, build, thetas, yss, Xi, dt, sgps, **build_kw).reshape(R, G)
+    nll = batched_nll(method, build, thetas, yss, Xi, dt, sgps, substeps=substeps, **build_kw).reshape(R, G)
     masked = np.where(np.isfinite(nll), nll, np.inf)
     arg = np.argmin(masked, axis=1)
     best = M.g(M.g_inv(grid))[arg]                              # the parameters the filter actually ran with

@@ -179,6 +179,28 @@ typedef struct cgp_init {
 #define CGP_NO_TIME_SPLIT     0x1000u /* ... never                                                                                      */
 #define CGP_SKIP_MISSING      0x2000u /* filters (cgp_filter, cgp_filter_custom) and the gradient / Fisher entry points: a NaN measurement is
                                          a missing sample, not poison -- see cgp_filter, cgp_ekf_nll_grad */
+/* RK4 substeps between measurements, for the continuous-discrete methods: n = 1 .. 16 rides in four bits of the flags (n = 1: no bit, the
+   plain call).  With h = dt / n (one IEEE division of the caller's dt): a FILTER's prediction from one sample to the next is n consecutive
+   RK4 steps of length h of the method's moment ODE, started from (mf, Pf); the update is unchanged.  A SMOOTHER's backward step from sample
+   k + 1 to sample k is n backward RK4 steps of length h, the j-th of them counted from sample k (j = n - 1 first, j = 0 last) held against
+   (m_kj, P_kj), the predicted moments after j forward substeps from (mf_k, Pf_k) -- G = P_kj^-1 gamma and m - m_kj --, so the smoother
+   integrates each interval forward again to have them; (m_k0, P_k0) = (mf_k, Pf_k).  Equivalently: the results are rows n - 1, 2 n - 1, ...
+   of the same method run at step h on the record refined n times, NaN at the inserted times taken as gaps (CGP_SKIP_MISSING), the smoother
+   on all n T filtering rows.  The record and every output stay at the caller's T.
+   Honoured by cgp_filter with CGP_F_CD_EKF / CGP_F_CD_SGP (with CGP_SKIP_MISSING or without), by cgp_smoother / cgp_smoother_select with
+   CGP_S_CD_EKS / CGP_S_CD_SGP, and by cgp_cd_ekf_nll_grad (with CGP_SKIP_MISSING or alone): the tangent goes through every substep, and
+   since the directions do not depend on dt the `dirs` layout and values are those of the plain call; and by cgp_filter_custom and
+   cgp_smoother_custom on a CGP_CUSTOM_SDE model, whose code object holds the flagged kernels beside the plain ones.
+   A flagged filter runs the d = 4 matrix-core kernel where the plain call would (chirp / La Scala SDE, one wavefront per trial) and the
+   generic kernel (csrc/cgp_steps.hpp) in the launch shape the call has everywhere else -- the DPP forms and the d = 6 / 8 models
+   included; a run-time compiled model's in its one shape, one lane per trial.  A flagged smoother runs the generic kernel with one
+   wavefront per trial whatever the batch and whatever kernel the plain call takes (the matrix-core, DPP and large-batch lane smoothers
+   take one RK4 step per sample), a run-time compiled model's too: the moments of an interval live in LDS.
+   Refused, with nothing written: a discrete method or a discrete run-time compiled model (CGP_E_ARG), the time-split entry points
+   (CGP_E_UNSUPPORTED), a smoother forced to CGP_THREAD_PER_TRIAL or whose sigma-point set does not fit the LDS stage beside that table
+   (CGP_E_UNSUPPORTED), and every other entry point that checks its flags, the other gradient and Fisher entry points among them. */
+#define CGP_RK4_SUBSTEPS(n)   ((uint32_t)((n) - 1) << 16)
+#define CGP_RK4_SUBSTEPS_MASK 0x000F0000u
 #define CGP_SIM_FIXED_X0      0x20u /* cgp_simulate: x_0 = m0 exactly, P0 unused (simulate_sde_init, simulate_lgssm)       */
 
 /* ---- error codes ---------------------------------------------------------------------------------------- */
