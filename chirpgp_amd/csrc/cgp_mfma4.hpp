@@ -399,6 +399,9 @@ CGP_DEV void ekf4_mfma_step_spec1(const Ekf4MfmaConst& K, const SpecRegs& R, con
 // formed beside the mean update instead of behind its quad broadcast (two fewer, six more: 2.73 ms).  All of it fits one
 // picture: the step costs about the sum of its instructions' issue costs, and the order hardly matters.
 constexpr int kEkf4Unroll = 4;
+// the fast path's loop body: 8-step groups per iteration (1 -- the general path's loop -- / 2 / 4 / 8: filter 1.872 / 1.809 / 1.809 / 1.805 ms, with
+// the fast path's parking 1.793 at 2, 1.782 at 4; docs/EXPERIMENTS.md 5m)
+constexpr int kEkf4FastGroups = 4;
 
 #ifdef CGP_EKF4_KERNELS      // the kernels are instantiated by cgp_inst_ekf4.hip alone; other units take the step functions
 template <bool E1>
@@ -436,6 +439,8 @@ CGP_DEV void ekf4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
     constexpr int kParkStride = 2;                                          // 32-byte slots (measured against 16: 3.35 against 3.39 ms a pass)
     __shared__ double2 park[64 * kParkStride];
     __shared__ double ybuf[64 + 16];                                        // the chunk's measurements (+ the read-ahead of the last group)
+    // (the fast path parks S and the innovation in an array each, two 8-byte writes a step: 1.809 -> 1.782 ms against the 16-byte write)
+    __shared__ double parkS[64], parkI[64];
     double cum = 0.0;
     // sticky counts: off the common regime / off every speculative regime.  (The score starts below zero: two failed passes at a record's
     // start, before any chunk was kept, stop the trying at once -- the CRLB jobs' records are eight chunks long.)
@@ -530,6 +535,7 @@ CGP_DEV void ekf4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
             return verdict.template code<REG>();
         };
         unsigned uncommon = 1;                                              // Ekf4Verdict::code of the chunk's last speculative pass
+        int kept_reg = -1;                                                  // kRegHigh / kRegCommon: the chunk was kept there (the fast path below)
         // (where the state sits at the chunk's start is known: LOW and MID chunks are tried in their regime also while the sticky count runs;
         // a chunk that starts at the edge of a band goes to the ANY regime at once -- a pass that fails is a pass wasted, and the kernel's
         // time is that of its slowest wavefront)
@@ -559,11 +565,11 @@ CGP_DEV void ekf4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
             } else {
                 if (high) {
                     uncommon = chunk(std::integral_constant<int, kRegHigh>{});
-                    if (uncommon != 0) { x = x0; n_high_left++; } else n_high++;
+                    if (uncommon != 0) { x = x0; n_high_left++; } else { n_high++; kept_reg = kRegHigh; }
                 }
                 if (uncommon != 0) {
                     uncommon = chunk(std::integral_constant<int, kRegCommon>{});
-                    if (uncommon == 0) n_common++;
+                    if (uncommon == 0) { n_common++; kept_reg = kRegCommon; }
                 }
             }
         }
@@ -640,6 +646,78 @@ CGP_DEV void ekf4_mfma_trial(const FilterIO& io, const ModelArgs& ma) {
             wave_lds_fence();
             const double2 si = park[(lane < nsteps ? lane : 0) * kParkStride];
             cum = nll_flush_wave(si.x, si.y, lane, nsteps, cum, nll ? nll + t0 : nullptr);
+        }
+        // The FAST PATH: a run of kept chunks.  Behind a chunk kept in HIGH or COMMON (no sticky count runs then, and a chunk behind one
+        // that wrote its rows is neither burn-in nor the junction) the chunks that follow are taken by a loop of their own for as long as
+        // each one is full and its start state selects the SAME tier: staging, eight 8-step groups, the verdict, the flush, the anchor's
+        // hand-over and the counters -- no tail loops, no burn-in or junction test, none of the tiers behind.  It decides what the general
+        // path decides and steps with the same functions: a chunk whose verdict fails is handed back untouched (state and measurements
+        // restored, nothing counted) and the general path repeats it, the failed pass in this tier included.
+        if (kept_reg >= 0 && checked_left == 0 && spec_off == 0 && t0 >= span.t_out) {
+            auto fast_run = [&](auto reg_c) {
+                constexpr int REG = decltype(reg_c)::value;
+                for (;;) {
+                    const int64_t t1 = t0 + 64;
+                    if (t1 + 64 > Te) break;
+                    const unsigned hx1 = (unsigned)__builtin_amdgcn_readfirstlane(__double2hiint(x.u2()));
+                    // (the general path's bands, word for word)
+                    const bool low1 = !nll_final && hx1 - 0xBFFC0000u <= 0xC085DFFFu - 0xBFFC0000u;
+                    const bool mid1 = !nll_final && (hx1 & 0x7FFFFFFFu) < 0x3FF80000u;
+                    const bool edge1 = !nll_final && !mid1 && (hx1 & 0x7FFFFFFFu) < 0x3FFC0000u;
+                    bool high1 = false;
+                    if constexpr (E1) high1 = !nll_final && hx1 - 0x401A0000u < 0x4085DFFFu - 0x401A0000u;
+                    if (low1 || mid1 || edge1 || high1 != (REG == kRegHigh)) break;
+                    wave_lds_fence();                                       // the previous chunk's NLL flush has read its slots
+                    double ychunk = ynext;
+                    asm volatile("" : "+v"(ychunk));
+                    ynext = (t1 + 64 + lane < Te) ? ys[t1 + 64 + lane] : 0.0;
+                    const Ekf4State x1 = x;
+                    ybuf[lane] = ychunk;
+                    wave_lds_fence();
+                    const bool reanchor = anchor_age >= 4;                  // (a chunk was kept: the age is 1 at least)
+                    Ekf4Anchor anchor;
+                    if (reanchor) ekf4_anchor<E1 ? 2 : 0>(K, x.u2(), anchor);
+                    else anchor = anchor_live;
+                    Ekf4Verdict verdict;
+                    auto one = [&](int slot, unsigned k, double y) {
+                        double S, innov;
+                        ekf4_mfma_step_spec1<E1 ? 2 : 0, REG>(K, R, RH, y, x, anchor, S, innov, verdict);
+                        parkS[slot + k] = S; parkI[slot + k] = innov;
+                        const unsigned t = (unsigned)(t1 + slot);
+                        out.wP.store_s(x.P, p_off + k * 128u, t * 128u);
+                        out.wm.store_s(x.uq, m_off + k * 32u, t * 32u);
+                    };
+                    double2 ya = *reinterpret_cast<const double2*>(ybuf), yb = *reinterpret_cast<const double2*>(ybuf + 2);
+                    double2 yc = *reinterpret_cast<const double2*>(ybuf + 4), yd = *reinterpret_cast<const double2*>(ybuf + 6);
+                    auto group8 = [&](int slot) {
+                        const double2 na = *reinterpret_cast<const double2*>(ybuf + slot + 8), nb = *reinterpret_cast<const double2*>(ybuf + slot + 10);
+                        const double2 nc = *reinterpret_cast<const double2*>(ybuf + slot + 12), nd = *reinterpret_cast<const double2*>(ybuf + slot + 14);
+                        one(slot, 0u, ya.x); one(slot, 1u, ya.y); one(slot, 2u, yb.x); one(slot, 3u, yb.y);
+                        one(slot, 4u, yc.x); one(slot, 5u, yc.y); one(slot, 6u, yd.x); one(slot, 7u, yd.y);
+                        ya = na; yb = nb; yc = nc; yd = nd;
+                    };
+                    // (kEkf4FastGroups groups as one loop body: the 8-step body of the general path lost ~ 18 cycles a step at its loop branch)
+#pragma unroll 1
+                    for (int slot = 0; slot < 64; slot += 8 * kEkf4FastGroups) {
+#pragma unroll
+                        for (int g = 0; g < kEkf4FastGroups; g++) group8(slot + 8 * g);
+                    }
+                    if (verdict.template code<REG>() != 0) { x = x1; ynext = ychunk; break; }
+                    t0 = t1;
+                    anchor_live = anchor; anchor_age = reanchor ? 1 : anchor_age + 1;
+                    if (jump_streak > 0) jump_streak--;
+                    if (spec_score < 8) spec_score++;
+                    if constexpr (REG == kRegHigh) n_high++;
+                    else n_common++;
+                    if (want_nll) {
+                        wave_lds_fence();
+                        const double2 si = make_double2(parkS[lane], parkI[lane]);
+                        cum = nll_flush_wave(si.x, si.y, lane, 64, cum, nll ? nll + t1 : nullptr);
+                    }
+                }
+            };
+            if (E1 && kept_reg == kRegHigh) { if constexpr (E1) fast_run(std::integral_constant<int, kRegHigh>{}); }      // (HIGH: the H = e_1 form alone)
+            else fast_run(std::integral_constant<int, kRegCommon>{});
         }
     }
     if (span.state) {                                                       // the segment's last state and its NLL total, for the fix-up pass
