@@ -679,6 +679,17 @@ def run_cd_ekf_nll_grad(spec, gamma, H, Xi, m0, P0, dt, ys, dirs, trials_per_rec
                          flags=rk4_substeps(substeps))
 
 
+def run_cd_sgp_nll_grad(spec, gamma, sgps, H, Xi, m0, P0, dt, ys, dirs, trials_per_record=None, record_index=None, missing=None, substeps=1):
+    """cgp_sgp_nll_grad with the SDE model: the continuous-discrete sigma-point filter's final NLL and its derivative along `dirs`
+    (B, n_dir, 27) -- forward tangents through the RK4 stages of the sigma-point moment ODE and the update, one launch (one per 16
+    directions).  `spec` the drift's descriptor, `gamma` = b b^T (4, 4) or (B, 4, 4), any d = 4 SigmaPoints `sgps`; everything else, and
+    the results, as run_cd_ekf_nll_grad."""
+    if gamma is None:
+        raise ValueError('cgp_sgp_nll_grad on an SDE model needs gamma = b b^T')
+    return _run_nll_grad(spec, _need_sigma(sgps, 'cgp_sgp_nll_grad'), False, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing,
+                         gamma=gamma, flags=rk4_substeps(substeps))
+
+
 def _need_sigma(sgps, entry):
     if sgps is None:
         raise ValueError(f'{entry} needs a sigma-point set')
@@ -686,9 +697,9 @@ def _need_sigma(sgps, entry):
 
 
 def _run_nll_grad(spec, sgps, fisher, H, Xi, m0, P0, dt, ys, dirs, trials_per_record, record_index, missing=None, gamma=None, flags=0):
-    """The tangent entry points: the sigma-point filter's with `sgps`, the EKF's with None, the continuous-discrete EKF's with `gamma`
-    (b b^T; directions of 27 doubles, not 24); `fisher`: the matrix as a third output; `missing`: as run_filter's, through _missing_flag;
-    `flags`: the bits of CGP_RK4_SUBSTEPS (the continuous-discrete entry)."""
+    """The tangent entry points: the sigma-point filter's with `sgps`, the EKF's with None, the continuous-discrete forms of either with
+    `gamma` (b b^T; directions of 27 doubles, not 24: cgp_cd_ekf_nll_grad, and cgp_sgp_nll_grad on the SDE model); `fisher`: the matrix as a
+    third output; `missing`: as run_filter's, through _missing_flag; `flags`: the bits of CGP_RK4_SUBSTEPS (the continuous-discrete forms)."""
     gaps = _missing_flag(missing) | int(flags)
     torch = _torch()
     ys_d = dev(ys)
@@ -712,7 +723,7 @@ def _run_nll_grad(spec, sgps, fisher, H, Xi, m0, P0, dt, ys, dirs, trials_per_re
         dirs_d = dev(dirs_h, ys_d.device.index)
         outs = ([_new_output((B,), ys_d.device, 'nll'), _new_output((B, n_dir), ys_d.device, 'grad')]
                 + ([_new_output((B, n_dir, n_dir), ys_d.device, 'fisher')] if fisher else []))
-        entry = f'cgp_{"ekf" if sgps is None else "sgp"}_nll_{"fisher" if fisher else "grad"}' if gamma is None else 'cgp_cd_ekf_nll_grad'
+        entry = f'cgp_{"ekf" if sgps is None else "sgp"}_nll_{"fisher" if fisher else "grad"}' if gamma is None or sgps is not None else 'cgp_cd_ekf_nll_grad'
         sig = [] if sgps is None else [C.byref(_sigma_struct(sgps, d, keep, None))]
         rc = _timed('filter', lambda: getattr(load_library(), entry)(ctx, C.byref(model), *sig, C.byref(init), float(dt), _ptr(ys_d), T, rep, _ptr(idx_d),
                                                                      B, T, _ptr(dirs_d), n_dir, *(_ptr(o) for o in outs), gaps, _stream()))

@@ -328,7 +328,8 @@ inline Verdict prepare_smoother_sample(int method, const cgp_model* model, const
 // ---- the tangent entry points: cgp_ekf_nll_grad / _fisher, cgp_sgp_nll_grad / _fisher, cgp_cd_ekf_nll_grad ------------------------------------
 struct TangentCall {
     const char* entry;                   // the entry point's name, for its messages
-    bool sgp, fisher;                    // takes a sigma-point set (sigma-point sets beyond the LDS stage are refused) / writes the matrix
+    bool sgp, fisher;                    // takes a sigma-point set (sigma-point sets beyond the LDS stage are refused; with an SDE model: the
+                                         // continuous-discrete sigma-point form, cgp_tangent4_cd_sigma.hpp) / writes the matrix
     bool cd = false;                     // the continuous-discrete form (cgp_tangent4_cd.hpp): the d = 4 chirp / La Scala SDE with its gamma
 };
 // The argument checks in the ABI's order (flags last: CGP_SKIP_MISSING or nothing), then what the entry's own grid can hold.  Nothing to do:
@@ -344,9 +345,17 @@ inline Verdict prepare_tangent(TangentCall call, const cgp_model* model, const c
     if (!model || !model->params) return {CGP_E_ARG, "model or model.params is NULL"};
     const ModelShape want = model_shape(*model);
     const bool shaped = model->n_harm == 1 && model->n_params == want.n_params && model->d == want.d;      // (n_harm = 1: d = 4)
+    // the sigma-point entry points take their continuous-discrete form from the MODEL: an SDE model is cd_sgp_filter's (cgp_tangent4_cd_sigma.hpp)
+    const bool cd_sgp = call.sgp && model->model_id == CGP_M_HARMONIC_SDE;
     if (call.cd) {
         if (model->model_id != CGP_M_HARMONIC_SDE || !shaped || !model->gamma)
             return refusef(CGP_E_UNSUPPORTED, "%s is built for the d = 4 chirp and La Scala SDE (CGP_M_HARMONIC_SDE, n_harm = 1) with model.gamma set", entry);
+        if (model->gamma_stride != 0 && model->gamma_stride < 16) return {CGP_E_ARG, "model.gamma_stride < d * d"};
+    } else if (cd_sgp) {
+        if (call.fisher)
+            return refusef(CGP_E_UNSUPPORTED, "%s: the Fisher form of the continuous-discrete filters is not built (CGP_M_HARMONIC_SDE goes with cgp_sgp_nll_grad)", entry);
+        if (!shaped || !model->gamma)
+            return refusef(CGP_E_UNSUPPORTED, "%s takes CGP_M_HARMONIC_SDE with n_harm = 1, d = 4, n_params = 3 and model.gamma set: the d = 4 chirp and La Scala SDE", entry);
         if (model->gamma_stride != 0 && model->gamma_stride < 16) return {CGP_E_ARG, "model.gamma_stride < d * d"};
     } else {
         const bool chirp = model->model_id == CGP_M_HARMONIC_LCD && shaped;
@@ -358,7 +367,8 @@ inline Verdict prepare_tangent(TangentCall call, const cgp_model* model, const c
         if (!sigma) return {CGP_E_ARG, "sigma is NULL"};
         if (sigma->d != 4) return refusef(CGP_E_UNSUPPORTED, "%s is built for d = 4 sigma-point sets", entry);
         if (!sigma->xi || !sigma->w || sigma->s < 1) return {CGP_E_ARG, "cgp_sigma.xi / w must be set and s >= 1"};
-        if (SigmaSet::stage_bytes(sigma->s, 4, 0, false) > (size_t)kSigLdsMaxBytes)
+        // (the continuous-discrete form parks its RK4 step's state in LDS beside the set)
+        if (SigmaSet::stage_bytes(sigma->s, 4, 0, false) + (cd_sgp ? (size_t)kCdSgpParkBytes : 0) > (size_t)kSigLdsMaxBytes)
             return refusef(CGP_E_UNSUPPORTED, "the sigma-point set does not fit the LDS stage of %s", entry);
     }
     if (!init || !init->H || !init->Xi || !init->m0 || !init->P0) return {CGP_E_ARG, "init.H / Xi / m0 / P0 must be set"};
@@ -366,8 +376,9 @@ inline Verdict prepare_tangent(TangentCall call, const cgp_model* model, const c
     if (ys_stride < 0 || ys_repeat < 1) return {CGP_E_ARG, "ys_stride must be >= 0 and ys_repeat >= 1"};
     if (!dirs || !nll || !grad || (call.fisher && !fisher))
         return {CGP_E_ARG, call.fisher ? "dirs / nll / grad / fisher must be set" : "dirs / nll / grad must be set"};
-    // the one flag these entry points take; the continuous-discrete one takes CGP_RK4_SUBSTEPS beside it
-    if (const Verdict v = check_flags(entry, call.cd ? flags & ~CGP_RK4_SUBSTEPS_MASK : flags, CGP_SKIP_MISSING); v.rc != CGP_OK) return v;
+    // the one flag these entry points take; the continuous-discrete forms take CGP_RK4_SUBSTEPS beside it
+    const bool rk4 = call.cd || cd_sgp;
+    if (const Verdict v = check_flags(entry, rk4 ? flags & ~CGP_RK4_SUBSTEPS_MASK : flags, CGP_SKIP_MISSING); v.rc != CGP_OK) return v;
     // the grids: one workgroup per trial (sigma-point), 64 / n_dir whole trials per wavefront (the EKF's Fisher form), B n_dir lanes (cd)
     if (call.sgp) {
         if (B > 0x7fffffffLL) return refusef(CGP_E_UNSUPPORTED, "%s runs one workgroup per trial: B must be < 2^31", entry);
@@ -380,7 +391,7 @@ inline Verdict prepare_tangent(TangentCall call, const cgp_model* model, const c
     set_record(io, ys, ys_stride, ys_repeat, ys_index);
     io.dirs = dirs; io.B = B; io.T = T; io.n_dir = n_dir; io.nll = nll; io.grad = grad; io.fisher = call.fisher ? fisher : nullptr;
     ma = model_args_literal(model, call.sgp ? sigma : nullptr, dt);
-    if (const int n = substeps_of(flags); call.cd && n > 1) { ma.substeps = n; ma.dt = dt / (double)n; }      // (as model_args(..., flags))
+    if (const int n = substeps_of(flags); rk4 && n > 1) { ma.substeps = n; ma.dt = dt / (double)n; }          // (as model_args(..., flags))
     return {};
 }
 

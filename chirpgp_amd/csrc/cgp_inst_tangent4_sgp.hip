@@ -1,6 +1,8 @@
 // cgp_sgp_nll_grad and cgp_sgp_nll_fisher: the sigma-point filter's NLL with its exact gradient by forward tangents through the scan, and
 // with the Fisher information of its Gaussian innovations model along the caller's directions -- the instantiations of
 // cgp_tangent4_sigma.hpp.  With CGP_SKIP_MISSING both hand the launch to the GAPS instantiations of cgp_inst_gaps4_tangent_sgp.hip.
+// cgp_sgp_nll_grad with a CGP_M_HARMONIC_SDE model is the continuous-discrete sigma-point filter's (cgp_tangent4_cd_sigma.hpp): its launch
+// goes to cgp_inst_tangent4_cd_sgp.hip or cgp_inst_gaps4_tangent_cd_sgp.hip.
 #define CGP_COOP4_HELPERS_ONLY          // the cooperative EKF and the EKF tangent kernel live in their own units
 #define CGP_TANGENT4_IO_ONLY
 #include "cgp_tangent4_sigma.hpp"
@@ -18,6 +20,8 @@ extern "C" int cgp_sgp_nll_grad(cgp_ctx* ctx, const cgp_model* model, const cgp_
                                              dirs, n_dir, nll, grad, nullptr, flags, io, ma);
     return launch_on(ctx, prepared, kLaunchLocked, [&]() -> Verdict {
         const hipStream_t st = (hipStream_t)stream;
+        if (model->model_id == CGP_M_HARMONIC_SDE)       // cd_sgp_filter's form (prepare_tangent has checked the model's shape; substeps: ma.substeps)
+            return hip_rc((flags & CGP_SKIP_MISSING) ? launch_cd_sgp4_tangent_gaps(io, ma, st) : launch_cd_sgp4_tangent_plain(io, ma, st));
         return hip_rc((flags & CGP_SKIP_MISSING) ? launch_sgp4_tangent_gaps(io, ma, false, st) : launch_sgp4_tangent(io, ma, st));
     });
 }

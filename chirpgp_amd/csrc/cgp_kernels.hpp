@@ -240,6 +240,9 @@ struct TangentIO {
         return ys + g * ys_stride;
     }
 };
+// LDS the continuous-discrete sigma-point tangent kernel (cgp_tangent4_cd_sigma.hpp) keeps beside the reduction buffer, the direction table and
+// the staged set: the RK4 step's base point and accumulators, parked across the fan.  prepare_tangent (cgp_args.hpp) leaves it free.
+constexpr int kCdSgpParkBytes = 4608;
 // cgp_simulate (cgp_simulate.hpp)
 struct SimIO {
     const double* __restrict__ H;  int64_t H_stride;

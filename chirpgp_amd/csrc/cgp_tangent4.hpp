@@ -259,5 +259,9 @@ inline hipError_t launch_ekf4_fisher(const TangentIO& io, const ModelArgs& ma, h
 // that the unflagged units compile to what they compiled to; fisher: the form that writes the matrix.
 hipError_t launch_ekf4_tangent_gaps(const TangentIO& io, const ModelArgs& ma, bool fisher, hipStream_t stream);
 hipError_t launch_sgp4_tangent_gaps(const TangentIO& io, const ModelArgs& ma, bool fisher, hipStream_t stream);
+// The continuous-discrete sigma-point filter's tangent kernel (cgp_tangent4_cd_sigma.hpp) is reached through cgp_sgp_nll_grad: its two
+// instantiations, cgp_inst_tangent4_cd_sgp.hip and cgp_inst_gaps4_tangent_cd_sgp.hip (CGP_RK4_SUBSTEPS is a trip count of either)
+hipError_t launch_cd_sgp4_tangent_plain(const TangentIO& io, const ModelArgs& ma, hipStream_t stream);
+hipError_t launch_cd_sgp4_tangent_gaps(const TangentIO& io, const ModelArgs& ma, hipStream_t stream);
 
 }  // namespace cgp

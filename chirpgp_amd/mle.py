@@ -13,7 +13,7 @@ import numpy as np
 from chirpgp_amd import filters_smoothers as fs
 from chirpgp_amd import models as M
 
-__all__ = ['batched_nll', 'make_objective', 'fit', 'fit_many', 'grid_search', 'value_and_grad', 'tangent_directions', 'tangent_directions_cd', 'has_exact_gradient',
+__all__ = ['batched_nll', 'make_objective', 'fit', 'fit_many', 'grid_search', 'value_and_grad', 'tangent_directions', 'tangent_directions_cd', 'has_exact_gradient', 'has_tangent_kernel',
            'value_grad_fisher', 'covariance_from_fisher', 'standard_errors', 'scoring_step', 'fit_scoring']
 
 
@@ -37,8 +37,8 @@ def _substeps_kw(method, substeps):
 
 
 def _exact_with_substeps(exact, method, substeps):
-    """``exact`` of an objective with RK4 substeps: unchanged -- the tangent kernel of cd_ekf takes the substeps, and what has no exact
-    gradient without them ('cd_sgp_filter') has none with them.  The count and the method are checked here, before anything is built."""
+    """``exact`` of an objective with RK4 substeps: unchanged -- the tangent kernels of cd_ekf and cd_sgp_filter take the substeps.  The
+    count and the method are checked here, before anything is built."""
     _substeps_kw(method, substeps)
     return exact
 
@@ -235,12 +235,26 @@ def _sigma_dim(sgps):
 def has_exact_gradient(method, build, Xi, sgps=None):
     """The in-kernel tangent gradient exists on the d = 4 chirp and La Scala models with a scalar Xi for the discrete EKF
     (cgp_ekf_nll_grad), for the continuous-discrete EKF (cgp_cd_ekf_nll_grad) and for the sigma-point filter with a d = 4 sigma-point
-    set ``sgps`` (cgp_sgp_nll_grad)."""
+    set ``sgps`` (cgp_sgp_nll_grad).
+
+    This predicate describes those three OLDER forms only, and its answers are held by tests/test_cd_gradient_host.py and
+    tests/test_sgp_gradient_host.py, which assert False for 'cd_sgp_filter'.  The fourth form -- the continuous-discrete sigma-point
+    filter's -- is built; :func:`has_tangent_kernel` is the predicate that says so, and the one every front end here goes by."""
     if _constants_of(build) is None or np.ndim(Xi) != 0:
         return False
     if method in ('ekf', 'cd_ekf'):
         return True
     return method == 'sgp_filter' and _sigma_dim(sgps) == 4
+
+
+def has_tangent_kernel(method, build, Xi, sgps=None):
+    """A tangent kernel -- value and exact gradient in one launch -- exists for ``method``: wherever has_exact_gradient says so, and for
+    'cd_sgp_filter' on build_chirp_model / build_lascala_model with a scalar Xi and a d = 4 sigma-point set ``sgps`` (cgp_sgp_nll_grad on
+    the SDE model: the tangent through the four RK4 stages of the sigma-point moment ODE).  value_and_grad, make_objective, fit and fit_many
+    (exact=True) go by this predicate."""
+    if has_exact_gradient(method, build, Xi, sgps):
+        return True
+    return method == 'cd_sgp_filter' and _constants_cd_of(build) is not None and np.ndim(Xi) == 0 and _sigma_dim(sgps) == 4
 
 
 # Which form is the default (``exact=None``).  Measured on MI355X at T = 3141 (tools/grad_bench.py, profiles/r06_grad_bench.txt): the tangent
@@ -268,13 +282,13 @@ def _exact_with_gaps(exact, missing):
 
 
 def _exact_unsupported():
-    return ValueError('exact=True: the tangent kernels are built for the discrete EKF, the continuous-discrete EKF and the sigma-point filter '
-                      '(with a d = 4 sigma-point set, sgps=) on build_chirp_model / build_lascala_model with a scalar Xi')
+    return ValueError('exact=True: the tangent kernels are built for the discrete EKF, the continuous-discrete EKF and the sigma-point filters '
+                      "('sgp_filter', 'cd_sgp_filter': with a d = 4 sigma-point set, sgps=) on build_chirp_model / build_lascala_model with a scalar Xi")
 
 
 def _has_fisher_form(method):
     """The Fisher forms (cgp_ekf_nll_fisher, cgp_sgp_nll_fisher) exist for the discrete filters only."""
-    return method != 'cd_ekf'
+    return method not in ('cd_ekf', 'cd_sgp_filter')
 
 
 def _fisher_unsupported(method):
@@ -286,7 +300,7 @@ def _tangent_launch(fisher, build, thetas, ys, Xi, dt, record_index, method, sgp
     """One launch of a tangent kernel along tangent_directions at every row of thetas: (nll, grad) or, fisher, (nll, grad, F) as NumPy.
     ``missing='skip'``: NaN samples of the records are gaps (CGP_SKIP_MISSING: such a step adds exactly nothing to any of the three)."""
     from chirpgp_amd import _engine as E
-    if not has_exact_gradient(method, build, Xi, sgps):
+    if not has_tangent_kernel(method, build, Xi, sgps):
         raise _exact_unsupported()
     if fisher and not _has_fisher_form(method):
         raise _fisher_unsupported(method)
@@ -296,6 +310,10 @@ def _tangent_launch(fisher, build, thetas, ys, Xi, dt, record_index, method, sgp
         drift, disp, disc, m0, P0, H = build(M.g(thetas))
     if method == 'cd_ekf':
         out = E.run_cd_ekf_nll_grad(drift, disp.outer(), H, Xi, m0, P0, dt, ys, tangent_directions_cd(build, thetas, dt, Xi),
+                                    trials_per_record=rows, record_index=record_index, missing=missing, substeps=substeps)
+        return tuple(o.cpu().numpy() for o in out)
+    if method == 'cd_sgp_filter':
+        out = E.run_cd_sgp_nll_grad(drift, disp.outer(), sgps, H, Xi, m0, P0, dt, ys, tangent_directions_cd(build, thetas, dt, Xi),
                                     trials_per_record=rows, record_index=record_index, missing=missing, substeps=substeps)
         return tuple(o.cpu().numpy() for o in out)
     dirs = tangent_directions(build, thetas, dt, Xi)
@@ -311,10 +329,11 @@ def _tangent_launch(fisher, build, thetas, ys, Xi, dt, record_index, method, sgp
 def value_and_grad(build, thetas, ys, Xi, dt, record_index=None, *, method='ekf', sgps=None, missing=None, substeps=1):
     """Objective and its EXACT gradient (forward tangents through the scan) at every row of thetas (G, P), in ONE launch: the EKF's
     (method='ekf', cgp_ekf_nll_grad: G P lanes), the continuous-discrete EKF's (method='cd_ekf', cgp_cd_ekf_nll_grad: G P lanes, the
-    tangent carried through the four RK4 stages of every step) or the sigma-point filter's (method='sgp_filter' with a d = 4 SigmaPoints
-    ``sgps``, cgp_sgp_nll_grad: G wavefronts).  ys (T,) or (R, T) shared out evenly over the rows as in batched_nll.  -> (nll (G,), grad (G, P)).
+    tangent carried through the four RK4 stages of every step), the sigma-point filter's (method='sgp_filter' with a d = 4 SigmaPoints
+    ``sgps``, cgp_sgp_nll_grad: G wavefronts) or the continuous-discrete sigma-point filter's (method='cd_sgp_filter' with such a set: the
+    same entry point on the SDE model, G wavefronts, the tangent through the four fans of every RK4 step).  ys (T,) or (R, T) shared out evenly over the rows as in batched_nll.  -> (nll (G,), grad (G, P)).
     ``missing='skip'``: NaN samples of the records are gaps, as in batched_nll -- the likelihood of the observed samples alone and its
-    exact gradient; a record of NaN only gives 0 and a zero gradient.  ``substeps=n`` (method='cd_ekf'): n RK4 steps of dt / n between two
+    exact gradient; a record of NaN only gives 0 and a zero gradient.  ``substeps=n`` (method='cd_ekf', 'cd_sgp_filter'): n RK4 steps of dt / n between two
     measurements, as in batched_nll -- the tangent goes through every one of them."""
     _exact_with_substeps(True, method, substeps)
     return _tangent_launch(False, build, thetas, ys, Xi, dt, record_index, method, sgps, missing, substeps)
@@ -401,7 +420,7 @@ def fit_scoring(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=100,
 
     Step: (F + mu diag F) step = -grad.  It is accepted only if the NLL decreases (a non-finite trial value is a rejection); then
     mu /= nu, else mu *= nu, from mu = mu0.  A record leaves the active set when max |grad| <= gtol max(1, |f|) or when mu exceeds
-    mu_max (no decrease along any damped direction).  The methods of has_exact_gradient only.
+    mu_max (no decrease along any damped direction).  The methods with a Fisher form only: 'ekf' and 'sgp_filter'.
 
     yss (R, T); init_params (P,) or (R, P) positive model parameters -> (opt_params (R, P), info): fit_many's fun, grad, nit, launches,
     converged (by the gradient rule), and fisher (R, P, P) at the final iterates, mu (R,), and per launch history (the (R,) NLLs of the
@@ -410,7 +429,7 @@ def fit_scoring(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=100,
     ``missing='skip'``: NaN samples of the records are gaps -- value, exact gradient and information of the observed samples, from the same
     launches (the L-BFGS front ends fit, fit_many and make_objective still take the difference gradient on such records)."""
     from chirpgp_amd import _engine as E
-    if not has_exact_gradient(method, build, Xi, sgps):
+    if not has_tangent_kernel(method, build, Xi, sgps):
         raise _exact_unsupported()
     if not _has_fisher_form(method):
         raise _fisher_unsupported(method)
@@ -464,18 +483,18 @@ def fit_scoring(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=100,
 
 def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=None, *, missing=None, substeps=1, **build_kw):
     """-> fun(theta) returning (nll, gradient): value and central differences from one batched launch of 2 P + 1 filter passes, or --
-    ``exact=True``, the discrete EKF, the continuous-discrete EKF ('cd_ekf') or the sigma-point filter (with a d = 4 ``sgps``) on the chirp /
-    La Scala models -- value and EXACT
+    ``exact=True``, the discrete EKF, the continuous-discrete EKF ('cd_ekf') or a sigma-point filter ('sgp_filter', 'cd_sgp_filter', with a
+    d = 4 ``sgps``) on the chirp / La Scala models (has_tangent_kernel) -- value and EXACT
     gradient from one launch of a tangent kernel (cgp_ekf_nll_grad: within 8e-13 of the gradient's scale against 100-digit arithmetic where
     the differences carry 2e-7; slower for a single record, see EXACT_FROM_RECORDS; cgp_sgp_nll_grad).  exact=None takes the tangent kernel
-    for the EKF from EXACT_FROM_RECORDS records only and never for the sigma-point filter.  ``missing='skip'`` (a record with gaps):
+    for the EKF from EXACT_FROM_RECORDS records only and never for the sigma-point filters.  ``missing='skip'`` (a record with gaps):
     differences only.  ``substeps=n`` ('cd_ekf', 'cd_sgp_filter'): n RK4 steps of dt / n between two measurements, in either form of the
-    gradient ('cd_ekf' has the exact one)."""
+    gradient (both have the exact one)."""
     exact = _exact_with_substeps(_exact_with_gaps(exact, missing), method, substeps)
     if exact is None:
         exact = _exact_by_default(method, build, Xi, 1, build_kw)
     if exact:
-        if not has_exact_gradient(method, build, Xi, sgps) or build_kw:
+        if not has_tangent_kernel(method, build, Xi, sgps) or build_kw:
             raise _exact_unsupported()
         from chirpgp_amd import _engine as E
         ys_dev = E.dev(ys)
@@ -539,7 +558,7 @@ def _value_and_grad_many(method, build, thetas, yss, Xi, dt, sgps, rel_step, bui
     if exact is None:
         exact = _exact_by_default(method, build, Xi, R, build_kw)
     if exact:
-        if not has_exact_gradient(method, build, Xi, sgps) or build_kw:
+        if not has_tangent_kernel(method, build, Xi, sgps) or build_kw:
             raise _exact_unsupported()
         f, grad = value_and_grad(build, thetas, yss, Xi, dt, record_index=record_index, method=method, sgps=sgps, substeps=substeps)
         f = f.copy()

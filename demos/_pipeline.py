@@ -49,11 +49,12 @@ def _family_setup(method, family, num_harmonics, dt, init):
     return build, (init_default if init is None else init), build_kw
 
 
-def _filter_and_smooth(method, build, build_kw, params, sgps, Xi, dt, ys, keep_rows=True):
+def _filter_and_smooth(method, build, build_kw, params, sgps, Xi, dt, ys, keep_rows=True, substeps=1):
     """Filter + smoother + E[g(V)] at given model parameters; `params` and `ys` may both carry a leading record axis.
     The estimate E[g(V)] of the frequency marginal (demos/ekfs_mle.py:69-77: gaussian_expectation on mss[:, 2], sqrt(Pss[:, 2, 2])) is
     written by the smoother launch itself (`select`: include/chirpgp_hip.h, cgp_smoother_select); with ``keep_rows=False`` the full
-    smoothing rows are not written at all (None in their place) -- what a caller that only wants the RMSE needs."""
+    smoothing rows are not written at all (None in their place) -- what a caller that only wants the RMSE needs.  ``substeps`` ('cd_ghfs'):
+    the RK4 steps between two measurements, in the filter and in the smoother that walks its rows."""
     if method == 'kpt':      # tetralith/jobs/kpt_mle.py:54-76: ekf_for_kpt, then the LINEAR smoother; frequency = g(x_0) fs / 2 pi
         F, Sigma, m0, P0, h = build(params, **build_kw)
         mfs, Pfs, _ = fs.ekf_for_kpt(F, Sigma, h, Xi, m0, P0, dt, ys)
@@ -75,8 +76,9 @@ def _filter_and_smooth(method, build, build_kw, params, sgps, Xi, dt, ys, keep_r
         mfs, Pfs, _ = fs.cd_ekf(drift, dispersion, H, Xi, m0, P0, dt, ys)
         mss, Pss, sel = fs.cd_eks(drift, dispersion, mfs, Pfs, dt, **kw)
     else:   # the reference passes the dispersion MATRIX: dispersion(jnp.eye(4)) (demos/cd_ghfs_mle.py:48)
-        mfs, Pfs, _ = fs.cd_sgp_filter(drift, dispersion(None), sgps, H, Xi, m0, P0, dt, ys)
-        mss, Pss, sel = fs.cd_sgp_smoother(drift, dispersion(None), sgps, mfs, Pfs, dt, **kw)
+        sub = dict(substeps=substeps) if substeps != 1 else {}
+        mfs, Pfs, _ = fs.cd_sgp_filter(drift, dispersion(None), sgps, H, Xi, m0, P0, dt, ys, **sub)
+        mss, Pss, sel = fs.cd_sgp_smoother(drift, dispersion(None), sgps, mfs, Pfs, dt, **kw, **sub)
     return mss, Pss, sel['expect']
 
 
@@ -96,17 +98,22 @@ def run_records(method, yss, Xi, dt, sgps=None, num_harmonics=0, maxiter=200, in
     return dict(opt_params=params, fun=info['fun'], nll0=nll0, mss=mss, Pss=Pss, est_freq=est, nit=info['nit'], launches=info['launches'])
 
 
-def run_record(method, ys, Xi, dt, sgps=None, num_harmonics=0, maxiter=200, init=None, family=None, keep_rows=True, exact=False):
+def run_record(method, ys, Xi, dt, sgps=None, num_harmonics=0, maxiter=200, init=None, family=None, keep_rows=True, exact=False, substeps=1):
     """MLE -> filter -> smoother -> E[g(V)] on one measurement record.
     method: 'ekfs' | 'ghfs' | 'cd_ekfs' | 'cd_ghfs' | 'kpt';  family: 'chirp' | 'harmonic' | 'lascala' | 'kpt'
     (default: 'kpt' for method 'kpt', else 'harmonic' when num_harmonics > 0, else 'chirp').
     exact=True: the fit's gradient from a tangent kernel (chirpgp_amd.mle.make_objective) instead of the default route.
+    substeps=n (method 'cd_ghfs'): n RK4 steps of dt / n between two measurements, in the objective -- with exact=True in its exact gradient
+    too -- and in the filter and smoother behind the fit.
     Returns a dict with opt_params, the scipy result, nll0 (objective at the start), the smoothing results and est_freq."""
     build, init, build_kw = _family_setup(method, family, num_harmonics, dt, init)
     filt = FILTER_OF[method]
-    nll0 = float(mle.batched_nll(filt, build, np.log(np.expm1(np.asarray(init, dtype=np.float64))), ys, Xi, dt, sgps, **build_kw)[0])
-    opt_params, res = mle.fit(filt, build, init, ys, Xi, dt, sgps=sgps, maxiter=maxiter, exact=True if exact else None, **build_kw)
-    mss, Pss, est = _filter_and_smooth(method, build, build_kw, opt_params, sgps, Xi, dt, ys, keep_rows)
+    if substeps != 1 and method != 'cd_ghfs':
+        raise ValueError("substeps goes with method 'cd_ghfs' here")
+    sub = dict(substeps=substeps) if substeps != 1 else {}
+    nll0 = float(mle.batched_nll(filt, build, np.log(np.expm1(np.asarray(init, dtype=np.float64))), ys, Xi, dt, sgps, **sub, **build_kw)[0])
+    opt_params, res = mle.fit(filt, build, init, ys, Xi, dt, sgps=sgps, maxiter=maxiter, exact=True if exact else None, **sub, **build_kw)
+    mss, Pss, est = _filter_and_smooth(method, build, build_kw, opt_params, sgps, Xi, dt, ys, keep_rows, substeps)
     return dict(opt_params=opt_params, res=res, nll0=nll0, mss=mss, Pss=Pss, est_freq=est)
 
 
@@ -125,11 +132,11 @@ def records_of_run(seed, T, dt, Xi, signal_harmonics, mags=None):
 
 
 def demo(method, sgps=None, num_harmonics=0, T=3141, seed=555, Xi=0.1, dt=0.001, maxiter=200, save_dir=None, mags=None, quiet=False,
-         family=None, signal_harmonics=None, result_name=None, mc=None, exact=False):
+         family=None, signal_harmonics=None, result_name=None, mc=None, exact=False, substeps=1):
     """One run per magnitude law, as the reference's demo scripts do; returns [(name, rmse, nll0, nll_opt), ...].
     ``signal_harmonics``: harmonics of the SIGNAL (default: those of the model); ``result_name``: file stem of the saved
     results (the reference's jobs: 'kpt_mle', 'lascala_ekfs_mle', ...; default: the method name), numbered ``mc`` (default: the
-    position of the magnitude law, as the demos have a single run); ``exact``: fit with the exact gradient (run_record)."""
+    position of the magnitude law, as the demos have a single run); ``exact``, ``substeps``: run_record's."""
     sig_h = num_harmonics if signal_harmonics is None else signal_harmonics
     ts = np.linspace(dt, dt * T, T)
     true_freq_func, _ = meow_freq(offset=8.)
@@ -137,7 +144,7 @@ def demo(method, sgps=None, num_harmonics=0, T=3141, seed=555, Xi=0.1, dt=0.001,
     for k, name, ys in records_of_run(seed, T, dt, Xi, sig_h, mags):
         t0 = time.time()
         r = run_record(method, ys, Xi, dt, sgps=sgps, num_harmonics=num_harmonics, maxiter=maxiter, family=family, keep_rows=bool(save_dir),
-                       exact=exact)
+                       exact=exact, substeps=substeps)
         err = float(rmse(true_freq_func(ts), r['est_freq'])) if r['res'].success or np.isfinite(r['res'].fun) else float('nan')
         if save_dir:       # tetralith/jobs/ekfs_mle.py:75-81: NaN results for a diverged run
             results.save_result(save_dir, result_name or method, name, k if mc is None else mc, r['mss'], r['Pss'], err)

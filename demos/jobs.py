@@ -51,11 +51,15 @@ JOBS = {
 }
 
 
-def run_job(job, num_mcs=100, T=3141, results=None, maxiter=200, seed=0, mags=None, quiet=False, lockstep=False):
+def run_job(job, num_mcs=100, T=3141, results=None, maxiter=200, seed=0, mags=None, quiet=False, lockstep=False, exact=False, substeps=1):
     """The job's Monte-Carlo loop; result files go to `results` (None: not saved).  `lockstep`: all runs of a magnitude law
     at once -- one lock-step maximum-likelihood fit, one batched filter and one batched smoother launch (_pipeline.run_records).
+    `exact`, `substeps` (the cd_ghfs_mle loop, record by record): the fit's gradient from the continuous-discrete sigma-point tangent
+    kernel, and RK4 substeps between two measurements (demos/cd_ghfs_mle.py's switches).
     -> [(mc, mag, rmse, nll at the start, nll at the optimum), ...]"""
     method, family, model_h, signal_h, sg = JOBS[job]
+    if (exact or substeps != 1) and (job != 'cd_ghfs_mle' or lockstep):
+        raise ValueError('--exact and --substeps go with the cd_ghfs_mle job, record by record')
     rows = []
     if lockstep:
         dt, Xi = 0.001, 0.1
@@ -80,7 +84,7 @@ def run_job(job, num_mcs=100, T=3141, results=None, maxiter=200, seed=0, mags=No
         return sorted(rows)
     for mc in range(num_mcs):
         out = demo(method, sgps=sg() if sg else None, num_harmonics=model_h, signal_harmonics=signal_h, family=family, T=T,
-                   seed=seed + mc, maxiter=maxiter, save_dir=results, result_name=job, mc=mc, mags=mags, quiet=quiet)
+                   seed=seed + mc, maxiter=maxiter, save_dir=results, result_name=job, mc=mc, mags=mags, quiet=quiet, exact=exact, substeps=substeps)
         for name, err, nll0, nll1 in out:
             rows.append((mc, name, err, nll0, nll1))
     return rows
@@ -95,8 +99,10 @@ def main(argv=None):
     ap.add_argument('--maxiter', type=int, default=200)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--lockstep', action='store_true', help='all Monte-Carlo runs of a magnitude law at once (lock-step MLE, batched filter / smoother)')
+    ap.add_argument('--exact', action='store_true', help='cd_ghfs_mle: exact gradients from the tangent kernel (cgp_sgp_nll_grad on the SDE model)')
+    ap.add_argument('--substeps', type=int, default=1, help='cd_ghfs_mle: RK4 steps between two measurements (1 .. 16)')
     a = ap.parse_args(argv)
-    return run_job(a.job, num_mcs=a.num_mcs, T=a.T, results=a.results, maxiter=a.maxiter, seed=a.seed, lockstep=a.lockstep)
+    return run_job(a.job, num_mcs=a.num_mcs, T=a.T, results=a.results, maxiter=a.maxiter, seed=a.seed, lockstep=a.lockstep, exact=a.exact, substeps=a.substeps)
 
 
 if __name__ == '__main__':

@@ -21,7 +21,8 @@
  *   cgp_smoother_sample                                                (no counterpart: the reference reports marginals only) joint posterior sample paths
  *                                                                      of rts / eks / sgp_smoother by backward simulation on the smoother's own affine maps
  *   cgp_ekf_nll_grad                                                   value_and_grad of ekf(...)[-1][-1] through the scan, demos/ekfs_mle.py:43-51
- *   cgp_sgp_nll_grad                                                   value_and_grad of sgp_filter(...)[-1][-1] through the scan, demos/ghfs_mle.py:53-56
+ *   cgp_sgp_nll_grad                                                   value_and_grad of sgp_filter(...)[-1][-1] through the scan, demos/ghfs_mle.py:53-56;
+ *                                                                      with the SDE model: of cd_sgp_filter(...)[-1][-1], demos/cd_ghfs_mle.py
  *   cgp_cd_ekf_nll_grad                                                value_and_grad of cd_ekf(...)[-1][-1] through the scan, demos/cd_ekfs_mle.py
  *   cgp_ekf_nll_fisher / cgp_sgp_nll_fisher                            (no counterpart: the reference's jobs report point estimates only)
  *   cgp_model_from_source, cgp_filter_custom, cgp_smoother_custom      ekf / eks / cd_ekf / cd_eks on ANY model (the reference traces any callable:
@@ -188,7 +189,7 @@ typedef struct cgp_init {
    of the same method run at step h on the record refined n times, NaN at the inserted times taken as gaps (CGP_SKIP_MISSING), the smoother
    on all n T filtering rows.  The record and every output stay at the caller's T.
    Honoured by cgp_filter with CGP_F_CD_EKF / CGP_F_CD_SGP (with CGP_SKIP_MISSING or without), by cgp_smoother / cgp_smoother_select with
-   CGP_S_CD_EKS / CGP_S_CD_SGP, and by cgp_cd_ekf_nll_grad (with CGP_SKIP_MISSING or alone): the tangent goes through every substep, and
+   CGP_S_CD_EKS / CGP_S_CD_SGP, and by cgp_cd_ekf_nll_grad and cgp_sgp_nll_grad on the SDE model (with CGP_SKIP_MISSING or alone): the tangent goes through every substep, and
    since the directions do not depend on dt the `dirs` layout and values are those of the plain call; and by cgp_filter_custom and
    cgp_smoother_custom on a CGP_CUSTOM_SDE model, whose code object holds the flagged kernels beside the plain ones.
    A flagged filter runs the d = 4 matrix-core kernel where the plain call would (chirp / La Scala SDE, one wavefront per trial) and the
@@ -295,7 +296,21 @@ int cgp_ekf_nll_grad(cgp_ctx* ctx, const cgp_model* model, const cgp_init* init,
  * chirp / La Scala LCD), directions, records and outputs as cgp_ekf_nll_grad, with ANY d = 4 sigma-point set: the kernel takes the
  * literal sum over the points (group_start and the CGP_SIGMA_* flags are not needed and not used).  One wavefront per trial; B < 2^31.
  * CGP_E_UNSUPPORTED for another model or a set of another dimension; a Cholesky that breaks down writes NaN to nll and grad, as
- * sgp_filter writes NaN; T = 0 writes nll = 0 and grad = 0.  flags: 0 or CGP_SKIP_MISSING, as cgp_ekf_nll_grad. */
+ * sgp_filter writes NaN; T = 0 writes nll = 0 and grad = 0.  flags: 0 or CGP_SKIP_MISSING, as cgp_ekf_nll_grad.
+ *
+ * With the SDE model -- CGP_M_HARMONIC_SDE with n_harm = 1, d = 4, n_params = 3 and cgp_model.gamma set, the model of cgp_cd_ekf_nll_grad --
+ * the same entry point is the CONTINUOUS-DISCRETE sigma-point filter's (cd_sgp_filter, filters_smoothers.py:534-582): its final negative
+ * log-likelihood and exact gradient by forward tangents through the four RK4 stages (quadratures.py:34-54) of the sigma-point moment ODE
+ *     P = L L^T, chi_p = m + L xi_p, dm/dt = sum w_p a(chi_p), dP/dt = C + C^T + gamma, C = sum w_p (chi_p - m) a(chi_p)^T   (:124-137)
+ * -- the Cholesky factor's tangent and every sigma point's tangent through the drift at each stage -- and through the update
+ * (demos/cd_ghfs_mle.py, tetralith/jobs/cd_ghfs_mle.py).  dirs is then [B][n_dir][CGP_CD_DIR_DOUBLES]: the directions of
+ * cgp_cd_ekf_nll_grad, value for value (chirpgp_amd/mle.py: tangent_directions_cd); dt carries no tangent.  Any d = 4 set whose stage
+ * leaves 4.5 KB of LDS free (1011 points).  flags: CGP_SKIP_MISSING and / or CGP_RK4_SUBSTEPS(n), with the meaning they have in
+ * cgp_cd_ekf_nll_grad (a gap: the RK4 prediction is the step's result along every direction, nothing is added to nll and grad; n RK4
+ * steps of dt / n between two measurements, the tangent through every one).  An SDE model of another shape or without gamma is
+ * CGP_E_UNSUPPORTED (the message names the shape); model.gamma_stride < 16 (and not 0) is CGP_E_ARG.  With an LCD model the substeps bits
+ * are refused as any stray flag is.  One wavefront per trial, up to 16 directions a launch and further ones as slices; a Cholesky that
+ * breaks down at any stage writes NaN to nll and to every grad entry of that trial, as cd_sgp_filter writes NaN. */
 int cgp_sgp_nll_grad(cgp_ctx* ctx, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init, double dt,
                      const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
                      const double* dirs, int32_t n_dir, double* nll, double* grad, uint32_t flags, void* stream);
@@ -310,7 +325,8 @@ int cgp_sgp_nll_grad(cgp_ctx* ctx, const cgp_model* model, const cgp_sigma* sigm
  * n_dir <= CGP_FISHER_MAX_DIR, CGP_E_UNSUPPORTED beyond.  The EKF form runs 64 / n_dir whole trials per wavefront.  T = 0 writes
  * nll = 0, grad = 0, fisher = 0; a diverged filter (a non-positive S, a Cholesky that breaks down) writes NaN to all three.
  * flags: 0 or CGP_SKIP_MISSING, as cgp_ekf_nll_grad -- the sum then runs over the observed steps only (the EKF form gates every lane on
- * its own trial's measurement). */
+ * its own trial's measurement).  The Fisher form of the continuous-discrete filters is not built: cgp_sgp_nll_fisher with a
+ * CGP_M_HARMONIC_SDE model is CGP_E_UNSUPPORTED. */
 #define CGP_FISHER_MAX_DIR 16
 int cgp_ekf_nll_fisher(cgp_ctx* ctx, const cgp_model* model, const cgp_init* init, double dt,
                        const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index, int64_t B, int64_t T,
