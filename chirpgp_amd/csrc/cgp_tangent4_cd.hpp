@@ -163,7 +163,8 @@ inline hipError_t launch_cd_ekf4_tangent(const TangentIO& io, const ModelArgs& m
 // The GAPS instantiation (CGP_SKIP_MISSING) lives in a unit of its own, cgp_inst_gaps4_tangent_cd.hip, as the other tangent kernels' do.
 hipError_t launch_cd_ekf4_tangent_gaps(const TangentIO& io, const ModelArgs& ma, hipStream_t stream);
 // CGP_RK4_SUBSTEPS: a kernel template of its own, cd_ekf4_tangent_substeps_kernel<GAPS> in cgp_inst_substeps4_tangent_cd.hip -- the kernel
-// above with its four-stage loop run n = ma.substeps times per sample, on the stage function above -- so that the one above stays as it is.
+// above with its four-stage loop run n = ma.substeps times per sample, on the stage function above.  The two stay two texts: with the RK4
+// step in one function of both, the plain form's gradient moves in its last bits on the MI355X (profiles/tangent_sharing_trial.txt).
 hipError_t launch_cd_ekf4_tangent_substeps(const TangentIO& io, const ModelArgs& ma, bool gaps, hipStream_t stream);
 
 }  // namespace cgp

@@ -11,7 +11,7 @@
 //     a(u) = [-lam u0 - w u1,  w u0 - lam u1,  u3,  -gam^2 u2 - 2 gam u3]
 // and then the scalar update (filters_smoothers.py:55-68).  Along one direction (the 27 constants of cgp_tangent4_cd.hpp,
 // CGP_CD_DIR_DOUBLES) a stage is
-//     dL = L Phi(L^-1 dP L^-T)       column by column, as in cgp_tangent4_sigma.hpp
+//     dL = L Phi(L^-1 dP L^-T)       column by column, the lines of cgp_tangent4_sigma.hpp a second time (see the layout below)
 //     d chi_p = dm + dL xi_p         d (chi_p - m) = dL xi_p
 //     d a_p = J(chi_p) d chi_p + (da/dlam) d lam + (da/dgam) d gam       (the drift has no sine or cosine, and its tangent needs no
 //                                                                         second derivative of softplus)
@@ -21,7 +21,9 @@
 //
 // Layout: that of sgp4_tangent_kernel (cgp_tangent4_sigma.hpp) -- one wavefront per trial, the primal replicated in every lane, lane
 // k < nd OWNS direction k, the fan one sigma point per lane in 1 + nd / 2 passes of 28 partial sums, each reduced by coop_reduce_to_lds;
-// up to kSgpMaxDir directions per launch, more as slices.  What is new is where the RK4 step's state lives.  Base point, stage point and
+// up to kSgpMaxDir directions per launch, more as slices (launch_tangent_slices of that header).  The Cholesky tangent and the fan's pass
+// loop are that kernel's lines a second time in the stage below, not functions of both: shared, they change sgp4_tangent_kernel's bits
+// or make it 4 % slower (profiles/tangent_sharing_trial.txt).  What is new is where the RK4 step's state lives.  Base point, stage point and
 // accumulators are 3 x 14 doubles of primal and 3 x 14 of tangent; the fan (sgp4_tangent_kernel: 396 of the 512 VGPRs) reads none of
 // them but the stage point, and that only through L and the direction table.  So across the fan the base point and the accumulators
 // are PARKED in LDS: the replicated primal once per wavefront (lane 0 writes, every lane reads the same address back), the tangents in a
@@ -298,19 +300,9 @@ __global__ void __launch_bounds__(64) cd_sgp4_tangent_kernel(SgpTangentIO sio, M
     if (owner) io.grad[trial * io.n_dir + sio.dir0 + lane] = dnll;
 }
 
-// One launch per slice of kSgpMaxDir directions; every slice repeats the primal (nll is written by the first).  B < 2^31 (the caller).
 template <bool GAPS>
 inline hipError_t launch_cd_sgp4_tangent(const TangentIO& io, const ModelArgs& ma, hipStream_t stream) {
-    if (io.B <= 0 || io.n_dir <= 0) return hipSuccess;
-    for (int dir0 = 0; dir0 < io.n_dir; dir0 += kSgpMaxDir) {
-        SgpTangentIO sio;
-        sio.t = io; sio.dir0 = dir0;
-        sio.nd = io.n_dir - dir0 < kSgpMaxDir ? io.n_dir - dir0 : kSgpMaxDir;
-        hipLaunchKernelGGL((cd_sgp4_tangent_kernel<GAPS>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, sio, ma);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return launch_tangent_slices<cd_sgp4_tangent_kernel<GAPS>>(io, ma, stream);      // (cgp_tangent4_sigma.hpp)
 }
 
 }  // namespace cgp

@@ -288,19 +288,25 @@ __global__ void __launch_bounds__(64) sgp4_tangent_kernel(SgpTangentIO sio, Mode
 }
 
 // One launch per slice of kSgpMaxDir directions; every slice repeats the primal (nll is written by the first).  B < 2^31 (the caller).
-// kFisher: n_dir <= kSgpMaxDir (the caller), so there is one slice with every direction in it.
-template <bool kFisher = false, bool GAPS = false>
-inline hipError_t launch_sgp4_tangent(const TangentIO& io, const ModelArgs& ma, hipStream_t stream) {
+// kKernel: an instantiation of sgp4_tangent_kernel or of cd_sgp4_tangent_kernel (cgp_tangent4_cd_sigma.hpp).
+template <void (*kKernel)(SgpTangentIO, ModelArgs)>
+inline hipError_t launch_tangent_slices(const TangentIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.n_dir <= 0) return hipSuccess;
     for (int dir0 = 0; dir0 < io.n_dir; dir0 += kSgpMaxDir) {
         SgpTangentIO sio;
         sio.t = io; sio.dir0 = dir0;
         sio.nd = io.n_dir - dir0 < kSgpMaxDir ? io.n_dir - dir0 : kSgpMaxDir;
-        hipLaunchKernelGGL((sgp4_tangent_kernel<kFisher, GAPS>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, sio, ma);
+        hipLaunchKernelGGL(kKernel, dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, sio, ma);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// kFisher: n_dir <= kSgpMaxDir (the caller), so there is one slice with every direction in it.
+template <bool kFisher = false, bool GAPS = false>
+inline hipError_t launch_sgp4_tangent(const TangentIO& io, const ModelArgs& ma, hipStream_t stream) {
+    return launch_tangent_slices<sgp4_tangent_kernel<kFisher, GAPS>>(io, ma, stream);
 }
 
 }  // namespace cgp
