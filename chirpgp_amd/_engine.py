@@ -65,6 +65,10 @@ EXPORTS = ('cgp_version', 'cgp_create', 'cgp_destroy', 'cgp_last_error', 'cgp_fi
            'cgp_reserve_workspace', 'cgp_release_workspace', 'cgp_source_hash', 'cgp_smoother_select', 'cgp_ekf_nll_grad', 'cgp_sgp_nll_grad', 'cgp_ekf_nll_fisher', 'cgp_sgp_nll_fisher', 'cgp_cd_ekf_nll_grad', 'cgp_model_from_source', 'cgp_custom_model_destroy',
            'cgp_filter_custom', 'cgp_smoother_custom', 'cgp_smoother_time_split', 'cgp_smoother_sample', 'cgp_pcrlb_sums', 'cgp_simulate_x0')
 
+# include/chirpgp_hip_timed.h: the continuous-discrete methods with one interval per step.  A tuple of its own: EXPORTS is chirpgp_hip.h's.
+TIMED_EXPORTS = ('cgp_filter_timed', 'cgp_smoother_timed')
+TIMED_VERSION = 1      # CGP_TIMED_VERSION
+
 _lib = None
 _lock = threading.Lock()
 
@@ -105,6 +109,12 @@ def load_library():
         lib.cgp_smoother_select.restype = C.c_int
         lib.cgp_smoother_select.argtypes = [_vp, C.c_int, C.POINTER(CgpModel), C.POINTER(CgpSigma), C.c_double,
                                             _vp, _vp, C.c_int64, C.c_int64, C.POINTER(CgpSmoothOut), C.c_uint32, _vp]
+        lib.cgp_filter_timed.restype = C.c_int
+        lib.cgp_filter_timed.argtypes = [_vp, C.c_int, C.POINTER(CgpModel), C.POINTER(CgpSigma), C.POINTER(CgpInit), _vp, C.c_int64,
+                                         _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_uint32, _vp]
+        lib.cgp_smoother_timed.restype = C.c_int
+        lib.cgp_smoother_timed.argtypes = [_vp, C.c_int, C.POINTER(CgpModel), C.POINTER(CgpSigma), _vp, C.c_int64, C.c_int64, _vp,
+                                           _vp, _vp, C.c_int64, C.c_int64, C.POINTER(CgpSmoothOut), C.c_uint32, _vp]
         lib.cgp_smoother_sample.restype = C.c_int
         lib.cgp_smoother_sample.argtypes = [_vp, C.c_int, C.POINTER(CgpModel), C.POINTER(CgpSigma), C.c_double, _vp, _vp, C.c_int64, C.c_int64, C.c_int64,
                                             C.c_uint64, C.c_int64, C.c_int64, _vp, C.POINTER(CgpSampleOut), C.c_uint32, _vp]
@@ -170,13 +180,15 @@ def load_library():
 
 def source_hash():
     """sha256 of the sources a library of this tree is built from -- csrc/*.hip, csrc/*.hpp (byte order of the names), csrc/Makefile,
-    include/chirpgp_hip.h, concatenated: what csrc/Makefile embeds as cgp_source_hash().  None where the sources are not shipped
+    include/chirpgp_hip.h, include/chirpgp_hip_timed.h, concatenated: what csrc/Makefile embeds as cgp_source_hash().  None where the sources are not shipped
     (a binary-only install), in which case nothing can be compared."""
     import glob
     import hashlib
     src = os.path.join(_HERE, 'csrc')
     names = sorted(os.path.basename(p) for p in glob.glob(os.path.join(src, '*.hip')) + glob.glob(os.path.join(src, '*.hpp')))
-    files = [os.path.join(src, n) for n in names] + [os.path.join(src, 'Makefile'), os.path.join(os.path.dirname(_HERE), 'include', 'chirpgp_hip.h')]
+    include = os.path.join(os.path.dirname(_HERE), 'include')
+    files = [os.path.join(src, n) for n in names] + [os.path.join(src, 'Makefile'), os.path.join(include, 'chirpgp_hip.h'),
+                                                     os.path.join(include, 'chirpgp_hip_timed.h')]
     if not names or not all(os.path.exists(f) for f in files):
         return None
     h = hashlib.sha256()
@@ -462,9 +474,57 @@ def _substeps_flag(substeps, continuous_discrete, time_split, what):
     return bits
 
 
+def _leading_shape(x):
+    return tuple(int(v) for v in (x.shape if hasattr(x, 'shape') else np.shape(x)))
+
+
+def check_intervals(dts, T, grids=None):
+    """``dts`` of a timed call (include/chirpgp_hip_timed.h) -> its host copy, float64 (G, T): (T,) is one time grid for the whole call
+    (G = 1), (G, T) one per record -- G must then be ``grids`` where that is given.  A NaN, an infinite or a negative entry is a
+    ValueError that names the first one: the C entry points do not look at device memory and would integrate it."""
+    a = dts.detach().cpu().numpy() if _is_torch(dts) else np.asarray(dts)
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    one = a.ndim == 1
+    if one:
+        a = a[None, :]
+    if a.ndim != 2 or a.shape[1] != T:
+        raise ValueError(f'dts must be (T,) or (records, T) with T = {T}, got {tuple(np.shape(dts))}')
+    if not one and grids is not None and a.shape[0] != grids:
+        raise ValueError(f'dts has {a.shape[0]} time grids for {grids} records: pass (T,) for one shared grid or one row per record')
+    bad = ~(np.isfinite(a) & (a >= 0.0))
+    if bad.any():
+        g, t = (int(v) for v in np.argwhere(bad)[0])
+        where = f'dts[{t}]' if one else f'dts[{g}, {t}]'
+        raise ValueError(f'{where} = {float(a[g, t])!r}: an interval must be finite and >= 0 (0: two samples at one instant)')
+    return a
+
+
+def _intervals(dts, T, grids=None, check=True):
+    """The intervals of a launch -> (number of grids, the checked host copy or None).  check=False: shapes only -- for a caller that checked
+    the same intervals once already (an MLE search passes one grid to every launch; checking a device tensor costs a copy to the host)."""
+    if check:
+        a = check_intervals(dts, T, grids)
+        return a.shape[0], a
+    shape = _leading_shape(dts)
+    if len(shape) not in (1, 2) or shape[-1] != T or (len(shape) == 2 and grids is not None and shape[0] != grids):
+        check_intervals(dts, T, grids)                  # (raises the shape's ValueError)
+    return (1 if len(shape) == 1 else shape[0]), None
+
+
+def _timed_call(dts, dt, continuous_discrete, time_split, what):
+    """The refusals of ``dts=`` that need no data: with it dt must be None, the method continuous-discrete, and no time split."""
+    if dt is not None:
+        raise ValueError('pass either dt or dts=, not both: with dts= every step has its own interval and dt must be None')
+    if not continuous_discrete:
+        raise ValueError(f'dts= goes with the continuous-discrete methods only (cd_ekf, cd_eks, cd_sgp_filter, cd_sgp_smoother), not with {what}: '
+                         f'a discrete model\'s constants are fixed per dt when it is built')
+    if time_split is not None:
+        raise ValueError('dts= does not go with time_split: there is no timed form of the time-split kernels')
+
+
 def run_filter(method, spec, sgps, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=False, flags=0, want=(True, True, True),
                trials_per_record=None, record_index=None, time_split=None, split_tol=None, return_junction_error=False, missing=None,
-               substeps=1):
+               substeps=1, dts=None, check_dts=True):
     """cgp_filter with NumPy / torch marshalling.  ys (T,) or (B, T) -> (mfs, Pfs, nll) with matching leading axes.
 
     Shared records (include/chirpgp_hip.h, cgp_filter): with ``trials_per_record = k`` every record of ys -- (T,) or (R, T) --
@@ -484,7 +544,20 @@ def run_filter(method, spec, sgps, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=
 
     ``substeps=n`` (include/chirpgp_hip.h, CGP_RK4_SUBSTEPS; cd_ekf and cd_sgp_filter): n = 1 .. 16 RK4 steps of dt / n between two
     measurements instead of one of dt -- the rows n - 1, 2 n - 1, ... of the same filter at step dt / n on the record refined n times
-    with gaps at the inserted times, without the n-fold record and outputs.  Not with ``time_split``."""
+    with gaps at the inserted times, without the n-fold record and outputs.  Not with ``time_split``.
+
+    ``dts=`` (include/chirpgp_hip_timed.h, cgp_filter_timed; cd_ekf and cd_sgp_filter): one interval per step in place of ``dt``, which must
+    then be None -- dts[t] is the time from sample t - 1 to sample t, dts[0] from (m0, P0) to sample 0; (T,) is one time grid for the whole
+    call, (R, T) one per record of ys, addressed like the records (``trials_per_record``, ``record_index``).  Entries must be finite and
+    >= 0 (``check_dts=False``: the caller has checked them, as mle does once per search).  Composes with ``missing`` and ``substeps``; not
+    with ``time_split``."""
+    n_grids = dts_h = None
+    if dts is not None:
+        _timed_call(dts, dt, int(method) in (F_CD_EKF, F_CD_SGP), time_split, 'a discrete filter')
+        shape = _leading_shape(ys)
+        if len(shape) not in (1, 2):
+            raise ValueError(f'ys must be (T,) or (B, T), got {shape}')
+        n_grids, dts_h = _intervals(dts, shape[-1], shape[0] if len(shape) == 2 else 1, check_dts)
     gaps = _missing_flag(missing)
     if gaps and time_split is not None:
         raise ValueError("missing='skip' does not go with time_split: a burn-in that starts inside a gap has no junction to compare")
@@ -516,6 +589,15 @@ def run_filter(method, spec, sgps, gamma, H, Xi, m0, P0, dt, ys, nll_final_only=
         nll = _new_output((B,) if nll_final_only else (B, T), ys_d.device, 'nll') if want[2] else None
         fl = int(flags) | (NLL_FINAL_ONLY if nll_final_only else 0) | gaps
         lib, st = load_library(), _stream()
+        if n_grids is not None:
+            dts_d = dev(dts, ys_d.device) if _is_torch(dts) else dev_const(dts if dts_h is None else dts_h)      # (cached by value: an MLE search passes one grid again and again)
+            keep.append(dts_d)
+            rc = _timed('filter', lambda: lib.cgp_filter_timed(ctx, int(method), C.byref(model), C.byref(sig) if sig is not None else None,
+                                                               C.byref(init), _ptr(dts_d), T if n_grids > 1 else 0, _ptr(ys_d), T, rep,
+                                                               _ptr(idx_d), B, T, _ptr(mfs), _ptr(Pfs), _ptr(nll), fl, st))
+            _check(ctx, rc, 'cgp_filter_timed')
+            _per_thread.junction_error = None
+            return tuple(None if t is None else _out(t, like_numpy, squeeze) for t in (mfs, Pfs, nll))
         if time_split is not None:
             segments, burn_in = (int(v) for v in time_split)
             err = _new_output((B,), ys_d.device, 'junction_err')
@@ -751,7 +833,7 @@ class SmootherSelection(dict):
 
 
 def run_smoother(method, spec, sgps, gamma, dt, mfs, Pfs, flags=0, want=(True, True), select=None, time_split=None, split_tol=None,
-                 return_junction_error=False, substeps=1):
+                 return_junction_error=False, substeps=1, dts=None, trials_per_record=None, record_index=None, check_dts=True):
     """cgp_smoother / cgp_smoother_select with NumPy / torch marshalling.  (T, d) / (T, d, d) or with a leading batch axis.
 
     ``select = dict(comp=k, mean=True, var=True, expect='softplus' | 'exp' | 'identity' | 'square' | None, order=10)`` asks the launch
@@ -761,7 +843,26 @@ def run_smoother(method, spec, sgps, gamma, dt, mfs, Pfs, flags=0, want=(True, T
     place) and a d = 4 smoother moves 8 - 24 bytes a step instead of 160 (include/chirpgp_hip.h: cgp_smoother_select).
 
     ``substeps=n`` (CGP_RK4_SUBSTEPS; cd_eks and cd_sgp_smoother, on the rows of a filter run with the same n): n backward RK4 steps of
-    dt / n per interval, each against the moments the filter's forward substeps passed through.  Not with ``time_split``."""
+    dt / n per interval, each against the moments the filter's forward substeps passed through.  Not with ``time_split``.
+
+    ``dts=`` (include/chirpgp_hip_timed.h, cgp_smoother_timed; cd_eks and cd_sgp_smoother, on the rows of a filter run with the same
+    intervals): one interval per step in place of ``dt``, which must then be None; the step from row t + 1 to row t runs over dts[t + 1].
+    (T,) is one time grid for the whole call, (R, T) one per record: without further arguments one per trial, with
+    ``trials_per_record`` / ``record_index`` addressed as the filter addressed its records.  ``select`` and ``want`` work as without."""
+    n_grids = dts_h = grid_rep = grid_idx = None
+    if dts is not None:
+        _timed_call(dts, dt, int(method) in (S_CD_EKS, S_CD_SGP), time_split, 'a discrete smoother')
+        shape = _leading_shape(mfs)
+        if len(shape) not in (2, 3):
+            raise ValueError(f'mfs must be (T, d) or (B, T, d), got {shape}')
+        n_grids, dts_h = _intervals(dts, shape[-2], None, check_dts)
+        grid_rep, grid_idx, grid_B = _record_addressing(n_grids, trials_per_record, record_index)
+        n_trials = shape[0] if len(shape) == 3 else 1
+        if n_grids > 1 or trials_per_record is not None or record_index is not None:
+            if grid_B != n_trials:
+                raise ValueError(f'dts addresses {grid_B} trials, mfs has {n_trials}')
+    elif trials_per_record is not None or record_index is not None:
+        raise ValueError('trials_per_record / record_index address the time grids of dts=')
     flags = int(flags) | _substeps_flag(substeps, int(method) in (S_CD_EKS, S_CD_SGP), time_split, 'a discrete smoother')
     torch = _torch()
     like_numpy = not _is_torch(mfs)
@@ -784,6 +885,27 @@ def run_smoother(method, spec, sgps, gamma, dt, mfs, Pfs, flags=0, want=(True, T
         sig = _sigma_struct(sgps, d, keep, _nonlinear_coord(spec))
         lib, st = load_library(), _stream()
         sig_ref = C.byref(sig) if sig is not None else None
+        # the launch: cgp_smoother / cgp_smoother_select with dt, or cgp_smoother_timed -- one entry point for both -- with the intervals
+        smooth_full = lambda mss_, Pss_: lib.cgp_smoother(ctx, int(method), C.byref(model), sig_ref, float(dt), _ptr(m), _ptr(P), B, T,      # noqa: E731
+                                                          _ptr(mss_), _ptr(Pss_), int(flags), st)
+        smooth_select = lambda o_: lib.cgp_smoother_select(ctx, int(method), C.byref(model), sig_ref, float(dt), _ptr(m), _ptr(P), B, T,      # noqa: E731
+                                                           C.byref(o_), int(flags), st)
+        entry_full, entry_select = 'cgp_smoother', 'cgp_smoother_select'
+        if n_grids is not None:
+            dts_d = dev(dts, m.device) if _is_torch(dts) else dev_const(dts if dts_h is None else dts_h)
+            gidx_d = _index_const(grid_idx) if grid_idx is not None else None
+            keep += [dts_d, gidx_d]
+            shared_grid = n_grids == 1 and grid_idx is None and trials_per_record is None
+
+            def smooth_select(o_):
+                return lib.cgp_smoother_timed(ctx, int(method), C.byref(model), sig_ref, _ptr(dts_d), 0 if shared_grid else T,
+                                              1 if shared_grid else grid_rep, _ptr(gidx_d), _ptr(m), _ptr(P), B, T, C.byref(o_), int(flags), st)
+
+            def smooth_full(mss_, Pss_):
+                o_ = CgpSmoothOut()
+                o_.mss, o_.Pss, o_.comp = _ptr(mss_), _ptr(Pss_), -1
+                return smooth_select(o_)
+            entry_full = entry_select = 'cgp_smoother_timed'
         if time_split is not None:
             # cgp_smoother_time_split (cd_sgp_smoother, cd_eks): several wavefronts per trial, each starting `burn_in` steps later than its piece from the
             # filtering row there; the launch reports the mismatch at its junctions (with split_tol: fall back to the sequential smoother)
@@ -806,9 +928,8 @@ def run_smoother(method, spec, sgps, gamma, dt, mfs, Pfs, flags=0, want=(True, T
             return res + (junction,) if return_junction_error else res
         if select is None:
             mss, Pss = _new_output(tuple(m.shape), m.device, 'mss'), _new_output(tuple(P.shape), P.device, 'Pss')
-            rc = _timed('smoother', lambda: lib.cgp_smoother(ctx, int(method), C.byref(model), sig_ref,
-                                                             float(dt), _ptr(m), _ptr(P), B, T, _ptr(mss), _ptr(Pss), int(flags), st))
-            _check(ctx, rc, 'cgp_smoother')
+            rc = _timed('smoother', lambda: smooth_full(mss, Pss))
+            _check(ctx, rc, entry_full)
             return _out(mss, like_numpy, squeeze), _out(Pss, like_numpy, squeeze)
         unknown = set(select) - {'comp', 'mean', 'var', 'expect', 'order'}
         if unknown:
@@ -841,17 +962,15 @@ def run_smoother(method, spec, sgps, gamma, dt, mfs, Pfs, flags=0, want=(True, T
         mss = _new_output(tuple(m.shape), m.device, 'mss') if want[0] else None
         Pss = _new_output(tuple(P.shape), P.device, 'Pss') if want[1] else None
         o.mss, o.Pss = _ptr(mss), _ptr(Pss)
-        rc = _timed('smoother', lambda: lib.cgp_smoother_select(ctx, int(method), C.byref(model), sig_ref, float(dt), _ptr(m), _ptr(P), B, T,
-                                                                C.byref(o), int(flags), st))
+        rc = _timed('smoother', lambda: smooth_select(o))
         if rc == E_UNSUPPORTED and (mss is None or Pss is None):
             # a kernel that can only gather the selection from its full rows: give it (temporary) rows
             tm = mss if mss is not None else _new_output(tuple(m.shape), m.device, 'mss (temporary)')
             tP = Pss if Pss is not None else _new_output(tuple(P.shape), P.device, 'Pss (temporary)')
             o.mss, o.Pss = _ptr(tm), _ptr(tP)
-            rc = _timed('smoother', lambda: lib.cgp_smoother_select(ctx, int(method), C.byref(model), sig_ref, float(dt), _ptr(m), _ptr(P), B, T,
-                                                                    C.byref(o), int(flags), st))
+            rc = _timed('smoother', lambda: smooth_select(o))
             keep += [tm, tP]
-        _check(ctx, rc, 'cgp_smoother_select')
+        _check(ctx, rc, entry_select)
         selection = SmootherSelection({k: _out(v, like_numpy, squeeze) for k, v in sel.items()})
         return (None if mss is None else _out(mss, like_numpy, squeeze), None if Pss is None else _out(Pss, like_numpy, squeeze), selection)
 

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <string>
 #include "cgp_kernels.hpp"
+#include "../../include/chirpgp_hip_timed.h"
 #include "cgp_ctx.hpp"
 #include "cgp_sample4.hpp"
 #include "cgp_pcrlb.hpp"
@@ -353,9 +354,11 @@ static Verdict enqueue_filter(cgp_ctx* ctx, const FilterCall& c, FilterPlan& p, 
         case CGP_M_LINEAR:       rc = dispatch_filter_disc_linear(c.method, model->d, route.wave, io, ma, st); break;
         case CGP_M_HARMONIC_LCD:
         case CGP_M_LASCALA_LCD:  rc = dispatch_filter_disc_harm(c.method, model->n_harm, route.wave, io, ma, st); break;
-        case CGP_M_LINEAR_SDE:   rc = route.substeps ? dispatch_filter_sde_linear_substeps(c.method, model->d, route.wave, io, ma, st)
+        case CGP_M_LINEAR_SDE:   rc = route.timed ? dispatch_filter_sde_linear_timed(c.method, model->d, route.wave, route.substeps, io, ma, st)
+                                      : route.substeps ? dispatch_filter_sde_linear_substeps(c.method, model->d, route.wave, io, ma, st)
                                                      : dispatch_filter_sde_linear(c.method, model->d, route.wave, io, ma, st); break;
-        case CGP_M_HARMONIC_SDE: rc = route.substeps ? dispatch_filter_sde_harm_substeps(c.method, model->n_harm, route.wave, io, ma, st)
+        case CGP_M_HARMONIC_SDE: rc = route.timed ? dispatch_filter_sde_harm_timed(c.method, model->n_harm, route.wave, route.substeps, io, ma, st)
+                                      : route.substeps ? dispatch_filter_sde_harm_substeps(c.method, model->n_harm, route.wave, io, ma, st)
                                                      : dispatch_filter_sde_harm(c.method, model->n_harm, route.wave, io, ma, st); break;
         default: rc = CGP_E_ARG;
         }
@@ -371,10 +374,12 @@ static Verdict enqueue_filter(cgp_ctx* ctx, const FilterCall& c, FilterPlan& p, 
     case FilterRoute::kLane4Sgp:    rc = dispatch_filter_lane4(c.method, io, ma, st); break;
     case FilterRoute::kEkf8Coop:    rc = dispatch_filter_coop8_ekf(model->n_harm, io, ma, st); break;
     case FilterRoute::kSgp8Coop:    rc = dispatch_filter_coop8_sgp(model->n_harm, io, ma, st); break;
-    case FilterRoute::kCdEkf4Mfma:  rc = route.substeps ? dispatch_filter_mfma4_cdekf_substeps(route.gaps, io, ma, st)
+    case FilterRoute::kCdEkf4Mfma:  rc = route.timed ? dispatch_filter_mfma4_cdekf_timed(route.gaps, route.substeps, io, ma, st)
+                                         : route.substeps ? dispatch_filter_mfma4_cdekf_substeps(route.gaps, io, ma, st)
                                          : route.gaps ? dispatch_filter_mfma4_cdekf_gaps(io, ma, st) : dispatch_filter_mfma4_cdekf(io, ma, st); break;
     case FilterRoute::kCdEkf4Coop:  rc = dispatch_filter_coop4_cdekf(io, ma, st); break;
-    case FilterRoute::kCdSgp4Mfma:  rc = route.substeps ? dispatch_filter_mfma4_cdsgp_substeps(route.gaps, io, ma, st)
+    case FilterRoute::kCdSgp4Mfma:  rc = route.timed ? dispatch_filter_mfma4_cdsgp_timed(route.gaps, route.substeps, io, ma, st)
+                                         : route.substeps ? dispatch_filter_mfma4_cdsgp_substeps(route.gaps, io, ma, st)
                                          : route.gaps ? dispatch_filter_mfma4_cdsgp_gaps(io, ma, st) : dispatch_filter_mfma4_cdsgp(io, ma, st); break;
     case FilterRoute::kCdSgp4Coop:  rc = dispatch_filter_coop4_cdsgp(io, ma, st); break;
     case FilterRoute::kKpt8Coop:    rc = dispatch_filter_kpt8(model->n_harm, io, ma, st); break;
@@ -412,13 +417,15 @@ static Verdict enqueue_smoother(cgp_ctx* ctx, const SmootherCall& c, SmootherPla
     case SmootherRoute::kWalk4Harm:   rc = dispatch_smoother_walk4_harm(method, io, host, ma, st); break;
     case SmootherRoute::kLane4:       rc = dispatch_smoother_lane4(method, model->model_id, io, host, ma, st); break;
     case SmootherRoute::kDiscHarm:    rc = dispatch_smoother_disc_harm(method, model->n_harm, wave, io, ma, st); break;
-    case SmootherRoute::kSdeLinear:   rc = plan.substeps ? dispatch_smoother_sde_linear_substeps(method, model->d, io, ma, st)
+    case SmootherRoute::kSdeLinear:   rc = plan.timed ? dispatch_smoother_sde_linear_timed(method, model->d, wave, plan.substeps, io, ma, st)
+                                           : plan.substeps ? dispatch_smoother_sde_linear_substeps(method, model->d, io, ma, st)
                                                          : dispatch_smoother_sde_linear(method, model->d, wave, io, ma, st); break;
-    case SmootherRoute::kCdSgp4Mfma:  rc = dispatch_smoother_mfma4_cdsgp(io, ma, st); break;
+    case SmootherRoute::kCdSgp4Mfma:  rc = plan.timed ? dispatch_smoother_mfma4_cdsgp_timed(io, ma, st) : dispatch_smoother_mfma4_cdsgp(io, ma, st); break;
     case SmootherRoute::kCdSgp4Coop:  rc = dispatch_smoother_coop4_cdsgp(io, ma, st); break;
-    case SmootherRoute::kCdEks4Mfma:  rc = dispatch_smoother_mfma4_cdeks(io, ma, st); break;
+    case SmootherRoute::kCdEks4Mfma:  rc = plan.timed ? dispatch_smoother_mfma4_cdeks_timed(io, ma, st) : dispatch_smoother_mfma4_cdeks(io, ma, st); break;
     case SmootherRoute::kCdEks4Coop:  rc = dispatch_smoother_coop4_cdeks(io, ma, st); break;
-    case SmootherRoute::kSdeHarm:     rc = plan.substeps ? dispatch_smoother_sde_harm_substeps(method, model->n_harm, io, ma, st)
+    case SmootherRoute::kSdeHarm:     rc = plan.timed ? dispatch_smoother_sde_harm_timed(method, model->n_harm, wave, plan.substeps, io, ma, st)
+                                           : plan.substeps ? dispatch_smoother_sde_harm_substeps(method, model->n_harm, io, ma, st)
                                                          : dispatch_smoother_sde_harm(method, model->n_harm, wave, io, ma, st); break;
     case SmootherRoute::kNone:        rc = CGP_E_ARG; break;
     }
@@ -490,6 +497,23 @@ int cgp_smoother_select(cgp_ctx* ctx, int method, const cgp_model* model, const 
                         const double* mfs, const double* Pfs, int64_t B, int64_t T, const cgp_smooth_out* out,
                         uint32_t flags, void* stream) {
     return smoother_entry(ctx, {method, model, sigma, dt, mfs, Pfs, B, T, out, flags}, stream);
+}
+
+// ---- include/chirpgp_hip_timed.h: one interval per step; the kernels read FilterIO::dts / SmootherIO::dts, never ModelArgs::dt
+int cgp_filter_timed(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, const cgp_init* init,
+                     const double* dts, int64_t dts_stride, const double* ys, int64_t ys_stride, int64_t ys_repeat, const int32_t* ys_index,
+                     int64_t B, int64_t T, double* mfs, double* Pfs, double* nll, uint32_t flags, void* stream) {
+    FilterCall call{method, model, sigma, init, 0.0, ys, ys_stride, ys_repeat, ys_index, B, T, mfs, Pfs, nll, flags};
+    call.dts = dts; call.dts_stride = dts_stride; call.timed = true;
+    return filter_entry(ctx, call, stream);
+}
+
+int cgp_smoother_timed(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma,
+                       const double* dts, int64_t dts_stride, int64_t dts_repeat, const int32_t* dts_index,
+                       const double* mfs, const double* Pfs, int64_t B, int64_t T, const cgp_smooth_out* out, uint32_t flags, void* stream) {
+    SmootherCall call{method, model, sigma, 0.0, mfs, Pfs, B, T, out, flags};
+    call.dts = dts; call.dts_stride = dts_stride; call.dts_repeat = dts_repeat; call.dts_index = dts_index; call.timed = true;
+    return smoother_entry(ctx, call, stream);
 }
 
 int cgp_smoother_sample(cgp_ctx* ctx, int method, const cgp_model* model, const cgp_sigma* sigma, double dt,

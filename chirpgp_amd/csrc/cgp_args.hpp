@@ -175,6 +175,8 @@ struct FilterCall {
     bool time_split = false;                         // cgp_filter_time_split, with its three arguments
     int64_t segments = 1, burn_in = 0;
     double* junction_err = nullptr;
+    const double* dts = nullptr; int64_t dts_stride = 0;      // cgp_filter_timed (include/chirpgp_hip_timed.h): one interval per step; dt is not read
+    bool timed = false;
 };
 struct FilterPlan {
     FilterIO io{};                                   // complete but for the workspace of the segment records (seg_state)
@@ -188,17 +190,23 @@ inline Verdict prepare_filter(const FilterCall& c, const HostCtx& h, FilterPlan&
             return {CGP_E_UNSUPPORTED, "CGP_SKIP_MISSING goes with cgp_filter and cgp_filter_custom only: a time-split filter's burn-in that starts "
                                        "inside a gap has no junction to compare"};
         if (c.flags & CGP_RK4_SUBSTEPS_MASK) return {CGP_E_UNSUPPORTED, kSubstepsSplit};
+        if (c.timed) return {CGP_E_UNSUPPORTED, kTimedSplit};
     }
     if (c.B < 0 || c.T < 0) return {CGP_E_ARG, "negative B or T"};
     if (c.B == 0 || c.T == 0) return kNothingToDo;
     if (!c.ys) return {CGP_E_ARG, "ys is NULL"};
     if (c.ys_stride < 0) return {CGP_E_ARG, "ys_stride must be >= 0 (T for dense [B][T] records, 0 for one shared record)"};
     if (c.ys_repeat < 1) return {CGP_E_ARG, "ys_repeat must be >= 1"};
+    if (c.timed) {
+        if (!c.dts) return {CGP_E_ARG, "dts is NULL"};
+        if (c.dts_stride < 0) return {CGP_E_ARG, "dts_stride must be >= 0 (T for one time grid per record, 0 for one shared grid)"};
+    }
     if (!c.init || !c.init->Xi || !c.init->m0 || !c.init->P0) return {CGP_E_ARG, "init.Xi / m0 / P0 must be set"};
     if (c.method != CGP_F_EKF_KPT && !c.init->H) return {CGP_E_ARG, "init.H must be set"};
     const bool sde = c.method == CGP_F_CD_EKF || c.method == CGP_F_CD_SGP;
     const bool sig = c.method == CGP_F_SGP || c.method == CGP_F_CD_SGP;
     if (c.method < CGP_F_EKF || c.method > CGP_F_EKF_KPT) return {CGP_E_ARG, "unknown filter method"};
+    if (c.timed && (!sde || (c.model && !model_shape(*c.model).sde))) return {CGP_E_ARG, kTimedDiscrete};
     if (const Verdict v = check_model(c.model, sde, sig, c.sigma); v.rc != CGP_OK) return v;
     if ((c.method == CGP_F_EKF_KPT) != (c.model->model_id == CGP_M_KPT)) return {CGP_E_ARG, "CGP_F_EKF_KPT goes with CGP_M_KPT only"};
     const bool split = c.segments > 1;
@@ -211,8 +219,9 @@ inline Verdict prepare_filter(const FilterCall& c, const HostCtx& h, FilterPlan&
     set_record(io, c.ys, c.ys_stride, c.ys_repeat, c.ys_index);
     io.B = c.B; io.T = c.T; io.mfs = c.mfs; io.Pfs = c.Pfs; io.nll = c.nll; io.flags = c.flags;
     io.counters = h.counters;
+    if (c.timed) { io.dts = c.dts; io.dts_stride = c.dts_stride; }
     p.ma = model_args(c.model, c.sigma, c.dt, c.flags);
-    p.route = route_filter({c.method, c.model, c.sigma, &io, &p.ma, c.flags, c.segments, h.num_cus});
+    p.route = route_filter({c.method, c.model, c.sigma, &io, &p.ma, c.flags, c.segments, h.num_cus, c.timed});
     if (p.route.rc != CGP_OK) return {p.route.rc, p.route.message};
     io.flags = p.route.flags;
     if (split) {
@@ -235,6 +244,9 @@ struct SmootherCall {
     bool time_split = false;                         // cgp_smoother_time_split, with its three arguments
     int64_t segments = 1, burn_in = 0;
     double* junction_err = nullptr;
+    // cgp_smoother_timed (include/chirpgp_hip_timed.h): one interval per step, with an addressing of their own; dt is not read
+    const double* dts = nullptr; int64_t dts_stride = 0, dts_repeat = 1; const int32_t* dts_index = nullptr;
+    bool timed = false;
 };
 struct SmootherPlan {
     SmootherIO io{};                                 // complete but for the workspace of the junction states (junction)
@@ -247,12 +259,18 @@ inline Verdict prepare_smoother(const SmootherCall& c, const HostCtx& h, Smoothe
         if (c.segments < 1) return {CGP_E_ARG, "segments must be >= 1"};
         if (!c.junction_err) return {CGP_E_ARG, "junction_err must be set"};
         if (c.flags & CGP_RK4_SUBSTEPS_MASK) return {CGP_E_UNSUPPORTED, kSubstepsSplit};
+        if (c.timed) return {CGP_E_UNSUPPORTED, kTimedSplit};
     }
     if (c.B < 0 || c.T < 0) return {CGP_E_ARG, "negative B or T"};
     if (c.B == 0 || c.T == 0) return kNothingToDo;
     if (!c.out) return {CGP_E_ARG, "out is NULL"};
     const cgp_smooth_out& out = *c.out;
     const bool want_sel = out.comp_mean || out.comp_var || out.expect;
+    if (c.timed) {
+        if (!c.dts) return {CGP_E_ARG, "dts is NULL"};
+        if (c.dts_stride < 0) return {CGP_E_ARG, "dts_stride must be >= 0 (T for one time grid per trial, 0 for one shared grid)"};
+        if (c.dts_repeat < 1) return {CGP_E_ARG, "dts_repeat must be >= 1"};
+    }
     if (!c.mfs || !c.Pfs) return {CGP_E_ARG, "mfs / Pfs must be set"};
     if (!want_sel && (!out.mss || !out.Pss)) return {CGP_E_ARG, "mfs / Pfs / mss / Pss must be set"};
     if (want_sel) {
@@ -263,6 +281,7 @@ inline Verdict prepare_smoother(const SmootherCall& c, const HostCtx& h, Smoothe
     if (c.method < CGP_S_EKS || c.method > CGP_S_CD_SGP) return {CGP_E_ARG, "unknown smoother method"};
     const bool sde = c.method == CGP_S_CD_EKS || c.method == CGP_S_CD_SGP;
     const bool sig = c.method == CGP_S_SGP || c.method == CGP_S_CD_SGP;
+    if (c.timed && (!sde || (c.model && !model_shape(*c.model).sde))) return {CGP_E_ARG, kTimedDiscrete};
     if (const Verdict v = check_model(c.model, sde, sig, c.sigma); v.rc != CGP_OK) return v;
     if (c.model->model_id == CGP_M_KPT) return {CGP_E_ARG, "the KPT model has no smoother in the reference"};
     SmootherIO& io = p.io;
@@ -273,6 +292,8 @@ inline Verdict prepare_smoother(const SmootherCall& c, const HostCtx& h, Smoothe
     query.walk_cap = h.walk_segments;
     query.segments = c.segments; query.burn_in = c.burn_in;
     query.want_sel = want_sel; query.null_rows = !out.mss || !out.Pss;
+    query.timed = c.timed;
+    if (c.timed) { io.dts = c.dts; io.dts_stride = c.dts_stride; io.dts_repeat = c.dts_repeat; io.dts_index = c.dts_index; }
     p.route = route_smoother(query);
     if (p.route.rc != CGP_OK) return {p.route.rc, p.route.message};
     p.sel = smooth_sel(out);

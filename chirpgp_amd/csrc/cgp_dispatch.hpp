@@ -96,5 +96,37 @@ static int smoother_sde_substeps(int method, const SmootherIO& io, const ModelAr
     default: return CGP_E_UNSUPPORTED;
     }
 }
+// Timed calls (include/chirpgp_hip_timed.h; cgp_steps.hpp: TimedPredict, TimedSmooth): the same steps with each step's own interval, in
+// both launch shapes; `sub`: around the substep wrappers -- the smoothers then one wavefront per trial, as untimed
+template <class SM>
+static int filter_sde_timed(int method, bool wave, bool sub, const FilterIO& io, const ModelArgs& ma, hipStream_t st) {
+    using Meas = LinearMeasurement<SM::D>;
+    switch (method) {
+    case CGP_F_CD_EKF:
+        if (sub) return hip_rc(wave ? launch_filter<TimedPredict<SubstepPredict<CdEkfPredict<SM, true>>>, Meas>(io, ma, st)
+                                    : launch_filter<TimedPredict<SubstepPredict<CdEkfPredict<SM, false>>>, Meas>(io, ma, st));
+        return hip_rc(wave ? launch_filter<TimedPredict<CdEkfPredict<SM, true>>, Meas>(io, ma, st)
+                           : launch_filter<TimedPredict<CdEkfPredict<SM, false>>, Meas>(io, ma, st));
+    case CGP_F_CD_SGP:
+        if (sub) return hip_rc(wave ? launch_filter<TimedPredict<SubstepPredict<CdSgpPredict<SM, true>>>, Meas>(io, ma, st)
+                                    : launch_filter<TimedPredict<SubstepPredict<CdSgpPredict<SM, false>>>, Meas>(io, ma, st));
+        return hip_rc(wave ? launch_filter<TimedPredict<CdSgpPredict<SM, true>>, Meas>(io, ma, st)
+                           : launch_filter<TimedPredict<CdSgpPredict<SM, false>>, Meas>(io, ma, st));
+    default: return CGP_E_UNSUPPORTED;
+    }
+}
+template <class SM>
+static int smoother_sde_timed(int method, bool wave, bool sub, const SmootherIO& io, const ModelArgs& ma, hipStream_t st) {
+    if (sub && !wave) return CGP_E_UNSUPPORTED;                            // (route_smoother: substeps run one wavefront per trial)
+    switch (method) {
+    case CGP_S_CD_EKS:
+        if (sub) return hip_rc(launch_smoother<TimedSmooth<SubstepSmooth<CdEksStep<SM, true>>>>(io, ma, st));
+        return hip_rc(wave ? launch_smoother<TimedSmooth<CdEksStep<SM, true>>>(io, ma, st) : launch_smoother<TimedSmooth<CdEksStep<SM, false>>>(io, ma, st));
+    case CGP_S_CD_SGP:
+        if (sub) return hip_rc(launch_smoother<TimedSmooth<SubstepSmooth<CdSgpsStep<SM, true>>>>(io, ma, st));
+        return hip_rc(wave ? launch_smoother<TimedSmooth<CdSgpsStep<SM, true>>>(io, ma, st) : launch_smoother<TimedSmooth<CdSgpsStep<SM, false>>>(io, ma, st));
+    default: return CGP_E_UNSUPPORTED;
+    }
+}
 
 }  // namespace cgp

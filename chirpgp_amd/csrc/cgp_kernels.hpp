@@ -49,6 +49,18 @@ struct FilterIO {
         if (ys_index) g = ys_index[g];
         return ys + g * ys_stride;
     }
+    // Per-step intervals of a timed call (include/chirpgp_hip_timed.h, cgp_filter_timed): dts[t] is the time from sample t - 1 to sample t,
+    // dts[0] from the initial condition to sample 0.  They belong to the record: trial b reads those of the record its measurements come
+    // from, dts_stride doubles apart (0: one time grid for the whole call).  NULL on every other call; read by the timed kernels alone.
+    // (Behind every older member, so that none of them moves.)
+    const double* __restrict__ dts = nullptr;
+    int64_t dts_stride = 0;
+    __device__ __forceinline__ const double* intervals(int64_t trial) const {
+        int64_t g = trial;
+        if (ys_repeat > 1) g = (int64_t)((uint64_t)trial / (uint64_t)ys_repeat);
+        if (ys_index) g = ys_index[g];
+        return dts + g * dts_stride;
+    }
 };
 
 // The span of time steps of workgroup v of a (possibly time-split) filter launch.
@@ -215,6 +227,19 @@ struct SmootherIO {
     static constexpr int kJunctionDoubles = 4 + 16;
     double* __restrict__ junction = nullptr;
     SmoothSel sel;                // cgp_smoother_select: selected outputs (mss / Pss may then be NULL); comp < 0: off
+    // Per-step intervals of a timed call (include/chirpgp_hip_timed.h, cgp_smoother_timed): the step from row t + 1 to row t runs over
+    // dts[t + 1]; dts[0] is never read.  A smoother has no record addressing of its own, so the intervals bring theirs, with FilterIO::record's
+    // rule: trial b reads grid dts_index[b / dts_repeat] (b / dts_repeat without an index), dts_stride doubles apart (0: one grid for the call).
+    // NULL on every other call; read by the timed kernels alone.  (Behind every older member, so that none of them moves.)
+    const double* __restrict__ dts = nullptr;
+    int64_t dts_stride = 0, dts_repeat = 1;
+    const int32_t* __restrict__ dts_index = nullptr;
+    __device__ __forceinline__ const double* intervals(int64_t trial) const {
+        int64_t g = trial;
+        if (dts_repeat > 1) g = (int64_t)((uint64_t)trial / (uint64_t)dts_repeat);
+        if (dts_index) g = dts_index[g];
+        return dts + g * dts_stride;
+    }
 };
 static_assert(__builtin_offsetof(SmootherIO, segs) == 52 && __builtin_offsetof(SmootherIO, tiles_per_seg) == 64 && __builtin_offsetof(SmootherIO, ws) == 72,
               "the walks' arguments moved: compare their register use (tools/resusage.py) before and after");
@@ -288,7 +313,7 @@ inline size_t sigma_lds_bytes(const ModelArgs& ma, int d) {
 }
 // (the kernels' view of the caller's model and sigma-point set: model_args, cgp_args.hpp)
 // The argument structs travel by value, and the run-time-compiled models compare their sizes with this build's after loading (cgp_rtc.hip)
-static_assert(sizeof(ModelArgs) == 104 && sizeof(FilterIO) == 192 && sizeof(SmootherIO) == 144, "the kernels' argument structs changed size");
+static_assert(sizeof(ModelArgs) == 104 && sizeof(FilterIO) == 208 && sizeof(SmootherIO) == 176, "the kernels' argument structs changed size");
 
 // Linear scalar measurement y = H x + noise (every filter but ekf_for_kpt).
 template <int D> struct LinearMeasurement {
@@ -445,6 +470,10 @@ filter_kernel(FilterIO io, ModelArgs ma) {
 
     const int64_t T = io.T;
     const double* __restrict__ ys = io.record(trial);
+    // a timed call (cgp_steps.hpp: TimedPredict): the record's intervals, one per step, handed to the predictor before the step
+    constexpr bool TIMED = IsTimed<Pred>::value;
+    const double* __restrict__ dtr = nullptr;
+    if constexpr (TIMED) dtr = io.intervals(trial);
     double* __restrict__ mfs = io.mfs ? io.mfs + trial * T * D : nullptr;
     double* __restrict__ Pfs = io.Pfs ? io.Pfs + trial * T * D * D : nullptr;
     const bool nll_final = (io.flags & CGP_NLL_FINAL_ONLY) != 0;
@@ -466,12 +495,18 @@ filter_kernel(FilterIO io, ModelArgs ma) {
             // (where it would also wait for the previous step's ten output stores to be acknowledged).
             double ychunk = (t0 + lane < T) ? ys[t0 + lane] : 0.0;
             asm volatile("" : "+v"(ychunk));
+            double dtchunk = 0.0;                                        // (timed: the chunk's 64 intervals beside its measurements)
+            if constexpr (TIMED) {
+                dtchunk = (t0 + lane < T) ? dtr[t0 + lane] : 0.0;
+                asm volatile("" : "+v"(dtchunk));
+            }
             const int nsteps = (T - t0 < 64) ? (int)(T - t0) : 64;
             for (int slot = 0; slot < nsteps; slot++) {
                 const int64_t t = t0 + slot;
                 const double y = readlane_f64(ychunk, slot);
                 Vec<D> mp; Sym<D> Pp;
                 double S, innov;
+                if constexpr (TIMED) pred.set_interval(readlane_f64(dtchunk, slot));
                 pred.predict(lane, lds, mf, Pf, mp, Pp);
                 Meas::update(mp, Pp, H, Xi, y, mf, Pf, S, innov, gaps);
                 if (lane == slot) { S_l = S; innov_l = innov; }
@@ -522,6 +557,7 @@ filter_kernel(FilterIO io, ModelArgs ma) {
                 const double y = ytile[lane * kYPitch + k];
                 Vec<D> mp; Sym<D> Pp;
                 double S, innov;
+                if constexpr (TIMED) pred.set_interval(dtr[t]);            // (the lane's own trial's, clamped like `trial`)
                 pred.predict(lane, lds, mf, Pf, mp, Pp);
                 Meas::update(mp, Pp, H, Xi, y, mf, Pf, S, innov, gaps);
                 if (want_nll) {
@@ -557,6 +593,7 @@ filter_kernel(FilterIO io, ModelArgs ma) {
             const double y = ys[t];
             Vec<D> mp; Sym<D> Pp;
             double S, innov;
+            if constexpr (TIMED) pred.set_interval(dtr[t]);
             pred.predict(lane, lds, mf, Pf, mp, Pp);
             Meas::update(mp, Pp, H, Xi, y, mf, Pf, S, innov, gaps);
             if (want_nll) {
@@ -606,6 +643,10 @@ __global__ void __launch_bounds__(64) smoother_kernel(SmootherIO io, ModelArgs m
         step.attach(subtab);
     }
     const int64_t T = io.T;
+    // a timed call (cgp_steps.hpp: TimedSmooth): the step from row t + 1 to row t runs over dts[t + 1] of the trial's grid
+    constexpr bool TIMED = IsTimed<Step>::value;
+    const double* __restrict__ dtr = nullptr;
+    if constexpr (TIMED) dtr = io.intervals(trial);
     Vec<D> ms, mf;
     Sym<D> Ps, Pf;
     if constexpr (TILED) {
@@ -620,6 +661,7 @@ __global__ void __launch_bounds__(64) smoother_kernel(SmootherIO io, ModelArgs m
             block_load_rows<D>(tile, lane, io.mfs + (block_first * T + t) * D, T * D, nvalid, mf.v);
             block_load_rows<D * D>(tile, lane, io.Pfs + (block_first * T + t) * D * D, T * D * D, nvalid, row);
             row_to_sym<D>(row, Pf);
+            if constexpr (TIMED) step.set_interval(dtr[t + 1]);
             step.step(lane, lds, mf, Pf, ms, Ps);
             block_store_rows<D>(tile, lane, ms.v, io.mss + (block_first * T + t) * D, T * D, nvalid);
             sym_to_row<D>(Ps, row);
@@ -640,6 +682,7 @@ __global__ void __launch_bounds__(64) smoother_kernel(SmootherIO io, ModelArgs m
         for (int64_t t = T - 2; t >= 0; t--) {
             load_vec<D>(mfs + t * D, mf);
             load_sym<D>(Pfs + t * D * D, Pf);
+            if constexpr (TIMED) step.set_interval(dtr[t + 1]);
             step.step(lane, lds, mf, Pf, ms, Ps);
             if constexpr (WAVE && D >= 6) wave_store_step<D>(rowpark, lane, ms, Ps, mss + t * D, Pss + t * D * D);
             else if (writer) {
@@ -804,6 +847,17 @@ int dispatch_smoother_sde_harm_substeps(int method, int key, const SmootherIO&, 
 // ... and the one-wavefront-per-trial matrix-core filters at d = 4, with gaps or without (cgp_inst_substeps4.hip)
 int dispatch_filter_mfma4_cdekf_substeps(bool gaps, const FilterIO&, const ModelArgs&, hipStream_t);
 int dispatch_filter_mfma4_cdsgp_substeps(bool gaps, const FilterIO&, const ModelArgs&, hipStream_t);
+// Timed calls (include/chirpgp_hip_timed.h; cgp_steps.hpp: TimedPredict, TimedSmooth): the generic kernels in both launch shapes, `sub`
+// with CGP_RK4_SUBSTEPS -- the smoothers then one wavefront per trial -- (cgp_inst_timed_{linear,harm}_{filters,smoothers}.hip) ...
+int dispatch_filter_sde_linear_timed(int method, int key, bool wave, bool sub, const FilterIO&, const ModelArgs&, hipStream_t);
+int dispatch_filter_sde_harm_timed(int method, int key, bool wave, bool sub, const FilterIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_sde_linear_timed(int method, int key, bool wave, bool sub, const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_sde_harm_timed(int method, int key, bool wave, bool sub, const SmootherIO&, const ModelArgs&, hipStream_t);
+// ... and the one-wavefront-per-trial matrix-core kernels at d = 4 (cgp_inst_timed4.hip; the smoothers: cgp_inst_timed4_smoothers.hip)
+int dispatch_filter_mfma4_cdekf_timed(bool gaps, bool sub, const FilterIO&, const ModelArgs&, hipStream_t);
+int dispatch_filter_mfma4_cdsgp_timed(bool gaps, bool sub, const FilterIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_mfma4_cdeks_timed(const SmootherIO&, const ModelArgs&, hipStream_t);
+int dispatch_smoother_mfma4_cdsgp_timed(const SmootherIO&, const ModelArgs&, hipStream_t);
 // The host side of a smoother launch on the cooperative walks and the large-batch lane kernels: what their launchers need beside the
 // kernel's arguments.  Filled from the SmootherDecision (cgp_route.hpp) and the context.
 struct WalkSplit { int cap = 1; int min_tiles = 4; };      // exact time split: at most `cap` segments (1: off, 0: as many as fit), of `min_tiles` tiles or more

@@ -132,10 +132,17 @@ CGP_DEV void mfma4_update_col(double Pp, double fcol, double Hk, double Hq, doub
 // ------------------------------------------------------------------------------------------------ cd_sgp_filter, d = 4
 // SUB (CGP_RK4_SUBSTEPS): n = ma.substeps RK4 steps of ma.dt = h (divided once on the host) per sample,
 // a rolled loop around the same stage function; whole records only.  Instantiated in cgp_inst_substeps4.hip only.
-template <class SM, bool TWO, bool SPLIT, bool GAPS = false, bool SUB = false>
-__global__ void __launch_bounds__(64) cdsgp4_mfma_kernel(FilterIO io, ModelArgs ma) {
+// TIMED (include/chirpgp_hip_timed.h): the step's interval is the record's own, dts[t] -- the chunk's 64 loaded beside its measurements,
+// one readlane per step, and with SUB one division by n per lane and chunk (h_t = dts[t] / n, correctly rounded); ma.dt is not read.
+// Whole records only.  Instantiated in cgp_inst_timed4.hip only.
+template <class SM, bool TWO, bool SPLIT, bool GAPS = false, bool SUB = false, bool TIMED = false>
+// (TIMED with two passes and substeps: the allocator, left alone, takes 255 registers and 2 - 4 accumulation registers more, one wavefront per
+// SIMD where the untimed sibling holds two -- 18 % at two trials per SIMD; asked for two it needs 237 - 239 and no scratch.  1: no request)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((TIMED && TWO && SUB) ? 2 : 1)))
+cdsgp4_mfma_kernel(FilterIO io, ModelArgs ma) {
     static_assert(!(SPLIT && GAPS), "the time-split launches know no gaps");
     static_assert(!(SPLIT && SUB), "the time-split launches take one RK4 step per sample");
+    static_assert(!(SPLIT && TIMED), "the time-split launches take one dt");
     static_assert(SM::D == 4, "d = 4 kernel");
     __shared__ double2 park[64];                                         // (S, innovation) of the chunk's steps, for the NLL
     const int lane = threadIdx.x;
@@ -164,6 +171,8 @@ __global__ void __launch_bounds__(64) cdsgp4_mfma_kernel(FilterIO io, ModelArgs 
     double u = io.m0[trial * io.m0_stride + q];                          // the mean in column form
     double P = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, r, q);
     const double* __restrict__ ys = io.record(trial);
+    const double* __restrict__ dtr = nullptr;
+    if constexpr (TIMED) dtr = io.intervals(trial);
     Tile4FilterOut out;
     out.init(io, trial, lane);
     // (the struct's own offsets, formed before this kernel's lane range is known, cost its <false, true> form a register: 229 -> 230)
@@ -174,6 +183,12 @@ __global__ void __launch_bounds__(64) cdsgp4_mfma_kernel(FilterIO io, ModelArgs 
     for (int64_t t0 = span.t_begin; t0 < span.t_end; t0 += 64) {
         double ychunk = (t0 + lane < span.t_end) ? ys[t0 + lane] : 0.0;
         asm volatile("" : "+v"(ychunk));
+        double dtchunk = 0.0;
+        if constexpr (TIMED) {
+            dtchunk = (t0 + lane < span.t_end) ? dtr[t0 + lane] : 0.0;
+            if constexpr (SUB) dtchunk = dtchunk / (double)ma.substeps;      // h_t of the chunk's 64 steps at once: a step's own stays a readlane
+            asm volatile("" : "+v"(dtchunk));
+        }
         const int nsteps = (span.t_end - t0 < 64) ? (int)(span.t_end - t0) : 64;
         const bool burn = t0 < span.t_out;                               // burn-in chunks of a segment write nothing
         const OobWindow wPc = out.P_window(burn), wmc = out.m_window(burn);
@@ -186,7 +201,13 @@ __global__ void __launch_bounds__(64) cdsgp4_mfma_kernel(FilterIO io, ModelArgs 
             const double y = readlane_f64(ychunk, slot);
             double f = u, Pp = P;
             auto rhs = [&](double tm, double tP, double& km, double& kP) { cd4_mfma_rhs<TWO>(model, R, K, grp, tm, tP, km, kP); };
-            if constexpr (SUB) {
+            if constexpr (TIMED) {
+                const double h = readlane_f64(dtchunk, slot);
+                if constexpr (SUB) {
+#pragma unroll 1
+                    for (int j = 0; j < ma.substeps; j++) rk4_lane(h, f, Pp, rhs);
+                } else rk4_lane(h, f, Pp, rhs);
+            } else if constexpr (SUB) {
 #pragma unroll 1
                 for (int j = 0; j < ma.substeps; j++) rk4_lane(dt, f, Pp, rhs);
             } else rk4_lane(dt, f, Pp, rhs);
@@ -215,7 +236,9 @@ __global__ void __launch_bounds__(64) cdsgp4_mfma_kernel(FilterIO io, ModelArgs 
 // SPLIT (round 6; cgp_smoother_time_split): one wavefront per (trial, segment) -- see SmootherIO::bsegs.  Chunk j covers the rows
 // T - 2 - 64 j - 63 .. T - 2 - 64 j; segment s owns the chunks [s cps, (s + 1) cps) and starts burn_chunks chunks earlier in its walk
 // (later in time) from the FILTERING row there; the burn-in chunks store through a zero-byte window.
-template <bool SPLIT, class Rhs>
+// TIMED (include/chirpgp_hip_timed.h): the step from row t + 1 to row t runs over the trial's dts[t + 1] -- lane l of a chunk loads the
+// interval of the chunk's slot l, dts[t_hi - l + 1], and each step takes its own by readlane and negates it; `dt` is not read.
+template <bool SPLIT, bool TIMED = false, class Rhs>
 CGP_DEV void cd4_mfma_smoother_walk(const SmootherIO& io, Tile4SmootherIO& sio, int lane, const Sym<4>& gamma, double dt, double* gbuf, Rhs rhs) {
     const int r = lane >> 4, q = lane & 3;
     if (!sio.template init<SPLIT>(io, lane)) return;
@@ -223,6 +246,9 @@ CGP_DEV void cd4_mfma_smoother_walk(const SmootherIO& io, Tile4SmootherIO& sio, 
     const double* __restrict__ mfs = sio.mfs;
     const double* __restrict__ Pfs = sio.Pfs;
     const SmootherSpan sp = sio.sp;
+    static_assert(!(SPLIT && TIMED), "the time-split launches take one dt");
+    const double* __restrict__ dtr = nullptr;
+    if constexpr (TIMED) dtr = io.intervals(sio.trial);
     double ms = mfs[sp.t_start * 4 + q];                                 // the mean in column form
     double Ps = coop4_load_sym_entry(Pfs + sp.t_start * 16, r, q);
 
@@ -234,12 +260,19 @@ CGP_DEV void cd4_mfma_smoother_walk(const SmootherIO& io, Tile4SmootherIO& sio, 
         const OobWindow& om = sio.m_window(own);
         const int nsteps = t_hi + 1 < 64 ? (int)(t_hi + 1) : 64;
         coop4_chunk_gains(gbuf, lane, nsteps, t_hi, mfs, Pfs, gamma);
+        double dtchunk = 0.0;
+        if constexpr (TIMED) {
+            dtchunk = (lane < nsteps) ? dtr[t_hi - lane + 1] : 0.0;       // (t_hi + 1 <= T - 1: inside the grid)
+            asm volatile("" : "+v"(dtchunk));
+        }
         for (int slot = 0; slot < nsteps; slot++) {
             const unsigned t = (unsigned)(t_hi - slot);
             const double* gl = gbuf + slot * kGainPitch;
             const double Gd = gl[r * 4 + q];
             const double mf = gl[16 + q];
-            rk4_lane(dt, ms, Ps, [&](double tm, double tP, double& km, double& kP) { rhs(tm, tP, Gd, mf, km, kP); });
+            double h = dt;
+            if constexpr (TIMED) h = -readlane_f64(dtchunk, slot);
+            rk4_lane(h, ms, Ps, [&](double tm, double tP, double& km, double& kP) { rhs(tm, tP, Gd, mf, km, kP); });
             oP.store(Ps, t * 128u + sio.offP);
             om.store(ms, t * 32u + sio.offm);
         }
@@ -252,7 +285,7 @@ CGP_DEV void cd4_mfma_smoother_walk(const SmootherIO& io, Tile4SmootherIO& sio, 
 // G is constant over the four stages and computed a chunk of 64 steps at a time, lane-parallel (cgp_coop4_sigma.hpp:
 // coop4_chunk_gains); the walk reads it back from LDS one entry per lane, and mf in column form.
 // SPLIT: cd4_mfma_smoother_walk.
-template <class SM, bool TWO, bool SPLIT = false>
+template <class SM, bool TWO, bool SPLIT = false, bool TIMED = false>
 __global__ void __launch_bounds__(64) cdsgps4_mfma_kernel(SmootherIO io, ModelArgs ma) {
     static_assert(SM::D == 4, "d = 4 kernel");
     __shared__ __attribute__((aligned(16))) double gbuf[64 * kGainPitch];
@@ -276,7 +309,7 @@ __global__ void __launch_bounds__(64) cdsgps4_mfma_kernel(SmootherIO io, ModelAr
     K.init(r, q, grp.W, model.lam, model.gam, coop4_load_sym_entry(ma.gamma + trial * ma.gamma_stride, r, q));
     SoftplusRegs R;
     R.init();
-    cd4_mfma_smoother_walk<SPLIT>(io, sio, lane, gamma, -ma.dt, gbuf, [&](double tm, double tP, double Gd, double mf, double& km, double& kP) {
+    cd4_mfma_smoother_walk<SPLIT, TIMED>(io, sio, lane, gamma, -ma.dt, gbuf, [&](double tm, double tP, double Gd, double mf, double& km, double& kP) {
         cd4_mfma_rhs<TWO>(model, R, K, grp, tm, tP, km, kP);            // (_m, _P), _P includes + gamma
         const double drow = mfma4x4(tm - mf, K.ident, 0.0);             // m - mf from column to row form: [r][q] <- [q][r]
         km = mfma4x4(drow, Gd, km);                                     // _m + G^T (m - mf): sum_k (m - mf)[k] G[k][q]   (A operand G[k][r'], B operand G[k][q'])
@@ -314,7 +347,8 @@ CGP_DEV void cd4_ekf_eval(const SoftplusRegs& R, const Cd4LaneCoef& K, const Cd4
 #ifndef CGP_NO_CD_EKF_KERNELS       // the kernels below are instantiated in cgp_inst_mfma4.hip (GAPS: cgp_inst_gaps4_sigma.hip)
 // SUB (CGP_RK4_SUBSTEPS): n = ma.substeps RK4 steps of ma.dt = h (divided once on the host) per sample, a rolled loop
 // around the same stage function; the NLL flush and the stores go by samples as before.  Instantiated in cgp_inst_substeps4.hip only.
-template <bool GAPS = false, bool SUB = false>
+// TIMED: as in cdsgp4_mfma_kernel.  Instantiated in cgp_inst_timed4.hip only.
+template <bool GAPS = false, bool SUB = false, bool TIMED = false>
 __global__ void __launch_bounds__(64) cdekf4_mfma_kernel(FilterIO io, ModelArgs ma) {
     __shared__ double2 park[64];                                         // (S, innovation) of the chunk's steps, for the NLL
     const int lane = threadIdx.x;
@@ -340,6 +374,8 @@ __global__ void __launch_bounds__(64) cdekf4_mfma_kernel(FilterIO io, ModelArgs 
     double P = coop4_load_sym_entry(io.P0 + trial * io.P0_stride, r, q);
     const int64_t T = io.T;
     const double* __restrict__ ys = io.record(trial);
+    const double* __restrict__ dtr = nullptr;
+    if constexpr (TIMED) dtr = io.intervals(trial);
     Tile4FilterOut out;
     out.init(io, trial, lane);
 
@@ -347,6 +383,12 @@ __global__ void __launch_bounds__(64) cdekf4_mfma_kernel(FilterIO io, ModelArgs 
     for (int64_t t0 = 0; t0 < T; t0 += 64) {
         double ychunk = (t0 + lane < T) ? ys[t0 + lane] : 0.0;
         asm volatile("" : "+v"(ychunk));
+        double dtchunk = 0.0;
+        if constexpr (TIMED) {
+            dtchunk = (t0 + lane < T) ? dtr[t0 + lane] : 0.0;
+            if constexpr (SUB) dtchunk = dtchunk / (double)ma.substeps;      // h_t of the chunk's 64 steps at once: a step's own stays a readlane
+            asm volatile("" : "+v"(dtchunk));
+        }
         const int nsteps = (T - t0 < 64) ? (int)(T - t0) : 64;
         for (int slot = 0; slot < nsteps; slot++) {
             const unsigned t = (unsigned)(t0 + slot);
@@ -358,7 +400,13 @@ __global__ void __launch_bounds__(64) cdekf4_mfma_kernel(FilterIO io, ModelArgs 
                 const double JP = mfma4x4(JT, tP, 0.0);                  // sum_k J[r][k] P[k][q]
                 kP = mfma4x4(JP, K.ident, JP + K.gam);                   // (J P)^T + J P + gamma
             };
-            if constexpr (SUB) {
+            if constexpr (TIMED) {
+                const double h = readlane_f64(dtchunk, slot);
+                if constexpr (SUB) {
+#pragma unroll 1
+                    for (int j = 0; j < ma.substeps; j++) rk4_lane(h, f, Pp, rhs);
+                } else rk4_lane(h, f, Pp, rhs);
+            } else if constexpr (SUB) {
 #pragma unroll 1
                 for (int j = 0; j < ma.substeps; j++) rk4_lane(dt, f, Pp, rhs);
             } else rk4_lane(dt, f, Pp, rhs);
@@ -376,7 +424,7 @@ __global__ void __launch_bounds__(64) cdekf4_mfma_kernel(FilterIO io, ModelArgs 
     out.store_nll_total(io, trial, lane, cum);
 }
 
-template <bool SPLIT = false>      // SPLIT: cgp_smoother_time_split, as cdsgps4_mfma_kernel
+template <bool SPLIT = false, bool TIMED = false>      // SPLIT: cgp_smoother_time_split, as cdsgps4_mfma_kernel; TIMED: cd4_mfma_smoother_walk
 __global__ void __launch_bounds__(64) cdeks4_mfma_kernel(SmootherIO io, ModelArgs ma) {
     __shared__ __attribute__((aligned(16))) double gbuf[64 * kGainPitch];
     const int lane = threadIdx.x;
@@ -398,7 +446,7 @@ __global__ void __launch_bounds__(64) cdeks4_mfma_kernel(SmootherIO io, ModelArg
     Sym<4> gamma;
     load_sym<4>(ma.gamma + trial * ma.gamma_stride, gamma);
     const double fs = model.fs;
-    cd4_mfma_smoother_walk<SPLIT>(io, sio, lane, gamma, -ma.dt, gbuf, [&](double tm, double tP, double Gd, double mf, double& km, double& kP) {
+    cd4_mfma_smoother_walk<SPLIT, TIMED>(io, sio, lane, gamma, -ma.dt, gbuf, [&](double tm, double tP, double Gd, double mf, double& km, double& kP) {
         double JT;
         cd4_ekf_eval(R, K, Jc, fs, tm, km, JT);
         const double drow = mfma4x4(tm - mf, K.ident, 0.0);             // m - mf from column to row form
@@ -422,6 +470,22 @@ inline int launch_cdekf4_mfma_substeps(const FilterIO& io, const ModelArgs& ma, 
     hipLaunchKernelGGL((cdekf4_mfma_kernel<GAPS, true>), dim3((unsigned)io.B), dim3(64), 0, stream, io, ma);
     return hip_rc(hipGetLastError());
 }
+// timed calls (cgp_inst_timed4.hip, cgp_inst_timed4_smoothers.hip): whole records, one wavefront per trial
+template <bool GAPS, bool SUB>
+inline int launch_cdekf4_mfma_timed(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
+    if (io.B <= 0 || io.T <= 0) return CGP_OK;
+    if (!mfma4_rows_fit(io.T) || !io.dts) return CGP_E_UNSUPPORTED;
+    hipLaunchKernelGGL((cdekf4_mfma_kernel<GAPS, SUB, true>), dim3((unsigned)io.B), dim3(64), 0, stream, io, ma);
+    return hip_rc(hipGetLastError());
+}
+template <bool TIMED = true>         // (a template, so that only the unit that calls it holds the kernel)
+inline int launch_cdeks4_mfma_timed(const SmootherIO& io, const ModelArgs& ma, hipStream_t stream) {
+    if (io.B <= 0 || io.T <= 0) return CGP_OK;
+    if (!mfma4_rows_fit(io.T) || io.bsegs > 1 || !io.dts) return CGP_E_UNSUPPORTED;
+    hipLaunchKernelGGL((cdeks4_mfma_kernel<false, TIMED>), dim3((unsigned)io.B), dim3(64), 0, stream, io, ma);
+    return hip_rc(hipGetLastError());
+}
+#ifndef CGP_NO_UNTIMED_CD_EKS      // (not a template: every unit that sees it holds its two kernels; the units of the timed kernels leave it out)
 inline int launch_cdeks4_mfma(const SmootherIO& io, const ModelArgs& ma, hipStream_t stream) {
     if (io.B <= 0 || io.T <= 0) return CGP_OK;
     if (!mfma4_rows_fit(io.T)) return CGP_E_UNSUPPORTED;
@@ -433,6 +497,7 @@ inline int launch_cdeks4_mfma(const SmootherIO& io, const ModelArgs& ma, hipStre
     }
     return hip_rc(hipGetLastError());
 }
+#endif  // CGP_NO_UNTIMED_CD_EKS
 #endif  // CGP_NO_CD_EKF_KERNELS
 
 template <class SM, bool GAPS = false>
@@ -460,6 +525,22 @@ inline int launch_cdsgp4_mfma_substeps(const FilterIO& io, const ModelArgs& ma, 
     if (!sgp4_mfma_fits(io.T, ma) || io.segs > 1) return CGP_E_UNSUPPORTED;          // (whole records only, route_filter)
     if (ma.sg.n_groups > 16) hipLaunchKernelGGL((cdsgp4_mfma_kernel<SM, true, false, GAPS, true>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
     else hipLaunchKernelGGL((cdsgp4_mfma_kernel<SM, false, false, GAPS, true>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
+    return hip_rc(hipGetLastError());
+}
+template <class SM, bool GAPS, bool SUB>
+inline int launch_cdsgp4_mfma_timed(const FilterIO& io, const ModelArgs& ma, hipStream_t stream) {
+    if (io.B <= 0 || io.T <= 0) return CGP_OK;
+    if (!sgp4_mfma_fits(io.T, ma) || io.segs > 1 || !io.dts) return CGP_E_UNSUPPORTED;
+    if (ma.sg.n_groups > 16) hipLaunchKernelGGL((cdsgp4_mfma_kernel<SM, true, false, GAPS, SUB, true>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
+    else hipLaunchKernelGGL((cdsgp4_mfma_kernel<SM, false, false, GAPS, SUB, true>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
+    return hip_rc(hipGetLastError());
+}
+template <class SM>
+inline int launch_cdsgps4_mfma_timed(const SmootherIO& io, const ModelArgs& ma, hipStream_t stream) {
+    if (io.B <= 0 || io.T <= 0) return CGP_OK;
+    if (!sgp4_mfma_fits(io.T, ma) || io.bsegs > 1 || !io.dts) return CGP_E_UNSUPPORTED;
+    if (ma.sg.n_groups > 16) hipLaunchKernelGGL((cdsgps4_mfma_kernel<SM, true, false, true>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
+    else hipLaunchKernelGGL((cdsgps4_mfma_kernel<SM, false, false, true>), dim3((unsigned)io.B), dim3(64), sigma_lds_bytes(ma, 4), stream, io, ma);
     return hip_rc(hipGetLastError());
 }
 template <class SM>

@@ -151,6 +151,17 @@ constexpr const char* kSubstepsDiscrete = "CGP_RK4_SUBSTEPS goes with the contin
                                           "a discrete model has no ODE to integrate";
 constexpr const char* kSubstepsSplit = "CGP_RK4_SUBSTEPS goes with cgp_filter, cgp_smoother and cgp_smoother_select only: the time-split kernels take one RK4 "
                                        "step per sample";
+// Timed calls (include/chirpgp_hip_timed.h: one interval per step): likewise -- filter_kernel in both shapes on TimedPredict
+// (cgp_steps.hpp; cgp_inst_timed_*.hip) and the one-wavefront-per-trial matrix-core kernels of cd_ekf and cd_sgp_filter at d = 4, whose
+// launchers take the TIMED instantiation, with GAPS and SUB or without (cgp_inst_timed4.hip).  A timed call is routed like the untimed
+// call with the same flags -- kernel, launch shape, crossover -- and where that ends on any other kernel (the DPP forms, a large-batch lane
+// kernel) it takes the generic kernel in the shape the call has.
+inline bool honours_times(FilterRoute r) {
+    return r == FilterRoute::kGenericWave || r == FilterRoute::kGenericLane || r == FilterRoute::kCdEkf4Mfma || r == FilterRoute::kCdSgp4Mfma;
+}
+constexpr const char* kTimedDiscrete = "per-step intervals go with the continuous-discrete methods on an SDE model only (cd_ekf, cd_sgp_filter, cd_eks, "
+                                       "cd_sgp_smoother): a discrete model's constants are fixed per dt at set-up";
+constexpr const char* kTimedSplit = "there is no timed form of the time-split entry points: their kernels take one dt";
 // the kernels that know the segments of a time-split launch (kEkf4Mfma: as kEkf4MfmaSeg)
 inline bool knows_segments(FilterRoute r) {
     return r == FilterRoute::kEkf4Mfma || r == FilterRoute::kSgp4Mfma || r == FilterRoute::kSgp8Coop || r == FilterRoute::kCdSgp4Mfma;
@@ -164,6 +175,7 @@ struct FilterQuery {
     uint32_t flags;
     int64_t segments;                // requested (cgp_filter_time_split); 1: none
     int num_cus;
+    bool timed = false;              // cgp_filter_timed: one interval per step (FilterIO::dts)
 };
 struct FilterDecision {
     int rc = CGP_OK;                 // or the refusal and its message
@@ -175,6 +187,7 @@ struct FilterDecision {
     bool gaps = false;               // CGP_SKIP_MISSING: the launcher of a matrix-core route takes the kernel's GAPS instantiation
     int64_t seg_len = 0;
     bool substeps = false;           // CGP_RK4_SUBSTEPS: the generic routes launch their SubstepPredict instantiation
+    bool timed = false;              // cgp_filter_timed: the generic and the cd matrix-core routes launch their TIMED instantiation
 };
 
 inline WaveCandidate<FilterRoute> filter_wave_candidate(const FilterQuery& q) {
@@ -291,6 +304,15 @@ inline FilterDecision route_filter(const FilterQuery& q) {
     // (kept as found: unreachable -- the segments set CGP_WAVE_PER_TRIAL, and the one thing that overrides it was refused above)
     if (d.segs > 1 && !d.wave) return refuse("time-split filters run one wavefront per trial only");
     d.route = d.wave ? wave.route : lane;
+    d.timed = q.timed;
+    if (d.timed) {
+        const int id = q.model->model_id;
+        if ((q.method != CGP_F_CD_EKF && q.method != CGP_F_CD_SGP) || (id != CGP_M_LINEAR_SDE && id != CGP_M_HARMONIC_SDE)) {
+            d.rc = CGP_E_ARG; d.message = kTimedDiscrete; return d;
+        }
+        if (q.segments > 1) return refuse(kTimedSplit);
+        if (!honours_times(d.route)) d.route = d.wave ? FilterRoute::kGenericWave : FilterRoute::kGenericLane;
+    }
     if (d.route == FilterRoute::kEkf4Mfma) {
         // beyond one wave per SIMD the four MFMA blocks carry four trials (CGP_ONE_TRIAL_PER_WAVE keeps one, for tests).  Kept as found:
         // "one wave per SIMD" is the literal 1024, whatever num_cus says.
@@ -333,6 +355,7 @@ struct SmootherQuery {
     int64_t burn_in = 0;
     bool want_sel = false;           // cgp_smoother_select: selected outputs are wanted ...
     bool null_rows = false;          // ... and mss or Pss is NULL
+    bool timed = false;              // cgp_smoother_timed: one interval per step (SmootherIO::dts)
 };
 enum class SmootherSelect { kNone, kKernel, kGather };      // selected outputs: none, written by the kernel, gathered from the full rows (smooth_select_kernel)
 struct SmootherDecision {
@@ -344,7 +367,15 @@ struct SmootherDecision {
     WalkSplit split;                 // the exact time split of the cooperative walks (walk_segments); off on every other route
     int bsegs = 1, chunks_per_bseg = 0, burn_chunks = 0;      // time split with burn-in, as SmootherIO has them; bsegs <= 1: nothing is split
     bool substeps = false;           // CGP_RK4_SUBSTEPS: kSdeLinear / kSdeHarm launch their SubstepSmooth instantiation
+    bool timed = false;              // cgp_smoother_timed: kSdeLinear / kSdeHarm / kCdEks4Mfma / kCdSgp4Mfma launch their TIMED instantiation
 };
+// Timed calls (include/chirpgp_hip_timed.h): smoother_kernel in both shapes on TimedSmooth (cgp_steps.hpp) -- around SubstepSmooth with
+// CGP_RK4_SUBSTEPS, one wavefront per trial as untimed -- and the matrix-core walks of cd_eks and cd_sgp_smoother at d = 4
+// (cgp_inst_timed4_smoothers.hip).  A timed call whose untimed twin ends on another kernel (the DPP forms, the large-batch lane kernel)
+// takes the generic kernel in the shape the call has.
+inline bool honours_times(SmootherRoute r) {
+    return r == SmootherRoute::kSdeLinear || r == SmootherRoute::kSdeHarm || r == SmootherRoute::kCdEks4Mfma || r == SmootherRoute::kCdSgp4Mfma;
+}
 // CGP_RK4_SUBSTEPS on a smoother: smoother_kernel on SubstepSmooth (cgp_steps.hpp), one wavefront per trial whatever the batch -- the
 // interval's moments are a table in LDS, (d + d (d + 1) / 2) 16 doubles a wavefront (5.6 KB at d = 8), and 64 trials' tables do not fit.
 // The matrix-core, DPP and lane smoothers take one RK4 step per sample: a flagged call is handed to the generic kernel in that shape.
@@ -462,6 +493,13 @@ inline SmootherDecision route_smoother(const SmootherQuery& q) {
             return refuse(CGP_E_UNSUPPORTED, "CGP_RK4_SUBSTEPS: the sigma-point set does not fit the LDS stage beside the table of intermediate moments");
         d.wave = true;
         d.route = q.model->model_id == CGP_M_LINEAR_SDE ? SmootherRoute::kSdeLinear : SmootherRoute::kSdeHarm;
+    }
+    d.timed = q.timed;
+    if (d.timed) {
+        const int id = q.model->model_id;
+        if ((q.method != CGP_S_CD_EKS && q.method != CGP_S_CD_SGP) || (id != CGP_M_LINEAR_SDE && id != CGP_M_HARMONIC_SDE)) return refuse(CGP_E_ARG, kTimedDiscrete);
+        if (q.segments > 1) return refuse(CGP_E_UNSUPPORTED, kTimedSplit);
+        if (!honours_times(d.route)) d.route = id == CGP_M_LINEAR_SDE ? SmootherRoute::kSdeLinear : SmootherRoute::kSdeHarm;
     }
     if (q.want_sel) {
         if (writes_selection(d.route)) d.select = SmootherSelect::kKernel;

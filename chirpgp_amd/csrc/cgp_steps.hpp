@@ -664,6 +664,22 @@ template <class Base> struct SubstepPredict : Base {
     }
 };
 
+// Timed calls (include/chirpgp_hip_timed.h): TimedPredict and TimedSmooth (below) wrap a continuous-discrete step, or its substep wrapper,
+// and have the kernel hand them each step's own interval before the step (filter_kernel, smoother_kernel: set_interval).  The step's
+// arithmetic is the wrapped one's: only its dt member, set once from ModelArgs::dt otherwise, is set per step.  With substeps the step
+// length is h_t = dts[t] / n, one IEEE division per step -- on a constant grid the quotient the host forms once for an untimed call.
+// Instantiations of their own, in units of their own (cgp_inst_timed_*.hip); the steps they wrap are untouched.
+template <class S, class = void> struct IsTimed { static constexpr bool value = false; };
+template <class S> struct IsTimed<S, decltype((void)S::TIMED)> { static constexpr bool value = S::TIMED; };
+template <class Base> struct TimedPredict : Base {
+    static constexpr int D = Base::D;
+    static constexpr bool TIMED = true;
+    CGP_DEV void set_interval(double dti) {
+        if constexpr (IsSubstepped<Base>::value) this->dt = dti / (double)this->n;
+        else this->dt = dti;
+    }
+};
+
 // ============================================================================================== SMOOTHER STEPS
 // step(lane, lds, mf, Pf, ms, Ps): (ms, Ps) at k+1 -> (ms, Ps) at k, given the filtering result (mf, Pf) at k.
 
@@ -815,6 +831,17 @@ template <class Base> struct SubstepSmooth : Base {
             Base::step(lane, lds, m, P, ms, Ps);
         }
         wave_lds_fence();                          // the next step's writes stay behind these reads
+    }
+};
+
+// Timed calls: either continuous-discrete smoother step, or its substep wrapper, over the interval dts[t + 1] of the step from row t + 1 to
+// row t (TimedPredict, above; the steps hold dt negated)
+template <class Base> struct TimedSmooth : Base {
+    static constexpr int D = Base::D;
+    static constexpr bool TIMED = true;
+    CGP_DEV void set_interval(double dti) {
+        if constexpr (IsSubstepped<Base>::value) this->dt = -(dti / (double)this->n);
+        else this->dt = -dti;
     }
 };
 

@@ -13,6 +13,10 @@ filters_smoothers.py:26-36).  Differences a caller sees:
 * ``cd_ekf``, ``cd_eks``, ``cd_sgp_filter`` and ``cd_sgp_smoother`` take ``substeps=n`` (1 .. 16, default 1: the reference): n RK4 steps of
   dt / n between two measurements, so that the sampling period of the record no longer fixes the step of the integrator; a smoother takes
   the n its filter ran with.  Run-time compiled SDE models (custom_sde) take it too; not with ``time_split``;
+* the same four take ``dts=`` in place of ``dt`` (which is then ``None``): one interval per step, for records with their own time stamps --
+  dts[t] is the time from sample t - 1 to sample t, dts[0] from (m0, P0) to sample 0 (``tools.intervals`` makes them from time stamps);
+  ``(T,)`` is one time grid for the call, ``(R, T)`` one per record of ``ys``.  It composes with ``missing`` and ``substeps``; the discrete
+  methods, run-time compiled models and ``time_split`` have no timed form and say so;
 * ``rts_sample``, ``eks_sample`` and ``sgp_smoother_sample`` (no counterpart in the reference) draw joint posterior sample paths from the
   discrete smoothers by backward simulation.
 """
@@ -62,18 +66,34 @@ def _sgps(sgps, d):
     return sgps
 
 
+def _no_dts(kw, what):
+    """``dts=`` on a discrete method: refused here, by name, before the model is even discretised."""
+    if kw.get('dts') is not None:
+        raise ValueError(f'dts= goes with the continuous-discrete methods only (cd_ekf, cd_eks, cd_sgp_filter, cd_sgp_smoother), not with {what}: '
+                         f'a discrete model\'s constants (exp(-lam dt), the Matern transition) are fixed per dt when it is built')
+
+
+def _no_custom_dts(kw):
+    if kw.get('dts') is not None:
+        raise ValueError('dts= with a run-time compiled drift (custom_sde): the timed form of the run-time compiled models is not built; '
+                         'they take one dt')
+
+
 def kf(F, Sigma, H, Xi, m0, P0, ys, **kw):
     """Kalman filter for a scalar measurement (filters_smoothers.py:145-184) -> (mfs, Pfs, cumulative nll)."""
+    _no_dts(kw, 'kf')
     return E.run_filter(E.F_EKF, M.linear_cond_m_cov(_np(F), _np(Sigma)), None, None, H, Xi, m0, P0, 0., ys, **kw)
 
 
 def rts(F, Sigma, mfs, Pfs, **kw):
     """RTS smoother (filters_smoothers.py:187-219) -> (mss, Pss)."""
+    _no_dts(kw, 'rts')
     return E.run_smoother(E.S_EKS, M.linear_cond_m_cov(_np(F), _np(Sigma)), None, None, 0., mfs, Pfs, **kw)
 
 
 def ekf(cond_m_cov, H, Xi, m0, P0, dt, ys, **kw):
     """Extended Kalman filter (filters_smoothers.py:222-264)."""
+    _no_dts(kw, 'ekf')
     spec = _discrete(cond_m_cov, dt)
     if isinstance(spec, M.CustomDiscrete):            # a model compiled at run time: the generic kernel on the caller's source
         return E.run_filter_custom(spec, None, H, Xi, m0, P0, dt, ys, **_custom_kw(kw))
@@ -82,6 +102,7 @@ def ekf(cond_m_cov, H, Xi, m0, P0, dt, ys, **kw):
 
 def ekf_for_kpt(F, Sigma, h, Xi, m0, P0, dt, ys, **kw):
     """Ad-hoc EKF of the KPT model: linear dynamics, harmonic measurement h (filters_smoothers.py:267-314)."""
+    _no_dts(kw, 'ekf_for_kpt')
     if isinstance(h, M.CustomMeasurement):            # a measurement function compiled at run time over the linear dynamics
         spec = h.with_dynamics(_np(F), _np(Sigma))
         return E.run_filter_custom(spec, None, spec.q, Xi, m0, P0, dt, ys, **_custom_kw(kw))
@@ -96,6 +117,7 @@ def ekf_for_kpt(F, Sigma, h, Xi, m0, P0, dt, ys, **kw):
 
 def eks(cond_m_cov, mfs, Pfs, dt, **kw):
     """Extended Kalman smoother (filters_smoothers.py:317-349)."""
+    _no_dts(kw, 'eks')
     spec = _discrete(cond_m_cov, dt)
     if isinstance(spec, M.CustomDiscrete):
         return E.run_smoother_custom(spec, None, dt, mfs, Pfs, **_custom_kw(kw, ('flags', 'substeps')))
@@ -103,21 +125,25 @@ def eks(cond_m_cov, mfs, Pfs, dt, **kw):
 
 
 def cd_ekf(a, b, H, Xi, m0, P0, dt, ys, **kw):
-    """Continuous-discrete EKF with RK4 moment integration (filters_smoothers.py:352-397)."""
+    """Continuous-discrete EKF with RK4 moment integration (filters_smoothers.py:352-397).  ``dts=`` (with dt = None): one interval per
+    step, (T,) or one row per record of ys."""
     if isinstance(a, M.CustomDrift):
+        _no_custom_dts(kw)
         return E.run_filter_custom(a, _gamma_from_callable(b), H, Xi, m0, P0, dt, ys, **_custom_kw(kw))
     return E.run_filter(E.F_CD_EKF, _drift(a), None, _gamma_from_callable(b), H, Xi, m0, P0, dt, ys, **kw)
 
 
 def cd_eks(a, b, mfs, Pfs, dt, **kw):
-    """Continuous-discrete EKS (filters_smoothers.py:400-443)."""
+    """Continuous-discrete EKS (filters_smoothers.py:400-443).  ``dts=`` (with dt = None): the intervals the filter ran with."""
     if isinstance(a, M.CustomDrift):
+        _no_custom_dts(kw)
         return E.run_smoother_custom(a, _gamma_from_callable(b), dt, mfs, Pfs, **_custom_kw(kw, ('flags', 'substeps')))
     return E.run_smoother(E.S_CD_EKS, _drift(a), None, _gamma_from_callable(b), dt, mfs, Pfs, **kw)
 
 
 def sgp_filter(cond_m_cov, sgps, H, Xi, m0, P0, dt, ys, **kw):
     """Sigma-point (Gauss-Hermite / cubature) filter on a discretised model (filters_smoothers.py:446-490)."""
+    _no_dts(kw, 'sgp_filter')
     spec = _discrete(cond_m_cov, dt)
     if isinstance(spec, M.CustomDiscrete):            # a model compiled at run time: the literal fan, covariance at every point
         return E.run_filter_custom(spec, None, H, Xi, m0, P0, dt, ys, sgps=_sgps(sgps, spec.d), **_custom_kw(kw))
@@ -126,6 +152,7 @@ def sgp_filter(cond_m_cov, sgps, H, Xi, m0, P0, dt, ys, **kw):
 
 def sgp_smoother(cond_m_cov, sgps, mfs, Pfs, dt, **kw):
     """Sigma-point smoother (filters_smoothers.py:493-531)."""
+    _no_dts(kw, 'sgp_smoother')
     spec = _discrete(cond_m_cov, dt)
     if isinstance(spec, M.CustomDiscrete):
         return E.run_smoother_custom(spec, None, dt, mfs, Pfs, sgps=_sgps(sgps, spec.d), **_custom_kw(kw, ('flags', 'substeps')))
@@ -136,6 +163,7 @@ def cd_sgp_filter(a, b, sgps, H, Xi, m0, P0, dt, ys, **kw):
     """Continuous-discrete sigma-point filter; b is the constant (d, dw) dispersion matrix (filters_smoothers.py:534-582)."""
     spec = _drift(a)
     if isinstance(spec, M.CustomDrift):
+        _no_custom_dts(kw)
         return E.run_filter_custom(spec, _gamma_from_matrix(b), H, Xi, m0, P0, dt, ys, sgps=_sgps(sgps, spec.d), **_custom_kw(kw))
     return E.run_filter(E.F_CD_SGP, spec, _sgps(sgps, spec.d), _gamma_from_matrix(b), H, Xi, m0, P0, dt, ys, **kw)
 
@@ -144,6 +172,7 @@ def cd_sgp_smoother(a, b, sgps, mfs, Pfs, dt, **kw):
     """Continuous-discrete sigma-point smoother (filters_smoothers.py:585-632)."""
     spec = _drift(a)
     if isinstance(spec, M.CustomDrift):
+        _no_custom_dts(kw)
         return E.run_smoother_custom(spec, _gamma_from_matrix(b), dt, mfs, Pfs, sgps=_sgps(sgps, spec.d), **_custom_kw(kw, ('flags', 'substeps')))
     return E.run_smoother(E.S_CD_SGP, spec, _sgps(sgps, spec.d), _gamma_from_matrix(b), dt, mfs, Pfs, **kw)
 

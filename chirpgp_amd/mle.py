@@ -43,7 +43,30 @@ def _exact_with_substeps(exact, method, substeps):
     return exact
 
 
-def batched_nll(method, build, thetas, ys, Xi, dt, sgps=None, record_index=None, *, missing=None, substeps=1, **build_kw):
+def _dts_kw(method, dts, dt, check=True):
+    """``dts=`` of an objective (one interval per step in place of dt: filters_smoothers) -> the filters' keyword.  For 'cd_ekf' and
+    'cd_sgp_filter' only, and dt must then be None: checked here, before anything is built or launched."""
+    if dts is None:
+        return {}
+    if method not in ('cd_ekf', 'cd_sgp_filter'):
+        raise ValueError(f"dts= goes with method 'cd_ekf' and 'cd_sgp_filter' only, not with {method!r}: a discrete model's constants are fixed per dt")
+    if dt is not None:
+        raise ValueError('pass either dt or dts=, not both: with dts= every step has its own interval and dt must be None')
+    return dict(dts=dts, check_dts=check)
+
+
+def _exact_with_times(exact, method, dts, dt):
+    """``exact`` of an objective on a record with its own time stamps: the tangent kernels take one dt, so None resolves to the difference
+    gradient and True is refused."""
+    if dts is None:
+        return exact
+    _dts_kw(method, dts, dt)
+    if exact:
+        raise ValueError('exact=True does not go with dts=: the tangent kernels take one dt; the difference gradient (exact=False) takes the intervals')
+    return False
+
+
+def batched_nll(method, build, thetas, ys, Xi, dt, sgps=None, record_index=None, *, missing=None, substeps=1, dts=None, check_dts=True, **build_kw):
     """Final cumulative NLL of ``method`` for every row of ``thetas`` (unconstrained parameters, g() maps them to the
     positive model parameters as in the reference).  ``ys`` is ONE record (T,) read by all G rows, or R records (R, T) of
     which each serves G / R consecutive rows (``record_index`` (n,) first picks n of them: G / n rows each).  The records
@@ -55,10 +78,12 @@ def batched_nll(method, build, thetas, ys, Xi, dt, sgps=None, record_index=None,
     ``num_harmonics=``): tetralith/jobs/kpt_mle.py:41-44.
 
     ``missing='skip'``: NaN samples of the records are gaps (filters_smoothers: the likelihood of the observed samples alone).
-    ``substeps=n`` ('cd_ekf', 'cd_sgp_filter'): n RK4 steps of dt / n between two measurements (filters_smoothers)."""
+    ``substeps=n`` ('cd_ekf', 'cd_sgp_filter'): n RK4 steps of dt / n between two measurements (filters_smoothers).
+    ``dts=`` ('cd_ekf', 'cd_sgp_filter'; dt is then None): one interval per step, (T,) for all records or (R, T) one time grid per record
+    of ys -- every row of a record reads the one copy of its grid, like its samples; ``check_dts=False``: the caller has checked the entries."""
     thetas = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
     kw = dict(nll_final_only=True, want=(False, False, True), trials_per_record=_rows_per_record(thetas.shape[0], ys, record_index),
-              record_index=record_index, missing=missing, **_substeps_kw(method, substeps))
+              record_index=record_index, missing=missing, **_substeps_kw(method, substeps), **_dts_kw(method, dts, dt, check_dts))
     with np.errstate(all='ignore'):        # a probe whose parameters under- or overflow yields a NaN objective, which the line search rejects
         built = build(M.g(thetas), **build_kw)
     if method == 'ekf_for_kpt':
@@ -481,7 +506,7 @@ def fit_scoring(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=100,
     return M.g(x), dict(fun=f, grad=g, nit=nit, launches=launches, converged=converged, fisher=F, mu=mu, history=history, iterates=iterates)
 
 
-def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=None, *, missing=None, substeps=1, **build_kw):
+def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=None, *, missing=None, substeps=1, dts=None, **build_kw):
     """-> fun(theta) returning (nll, gradient): value and central differences from one batched launch of 2 P + 1 filter passes, or --
     ``exact=True``, the discrete EKF, the continuous-discrete EKF ('cd_ekf') or a sigma-point filter ('sgp_filter', 'cd_sgp_filter', with a
     d = 4 ``sgps``) on the chirp / La Scala models (has_tangent_kernel) -- value and EXACT
@@ -489,8 +514,13 @@ def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=No
     the differences carry 2e-7; slower for a single record, see EXACT_FROM_RECORDS; cgp_sgp_nll_grad).  exact=None takes the tangent kernel
     for the EKF from EXACT_FROM_RECORDS records only and never for the sigma-point filters.  ``missing='skip'`` (a record with gaps):
     differences only.  ``substeps=n`` ('cd_ekf', 'cd_sgp_filter'): n RK4 steps of dt / n between two measurements, in either form of the
-    gradient (both have the exact one)."""
-    exact = _exact_with_substeps(_exact_with_gaps(exact, missing), method, substeps)
+    gradient (both have the exact one).  ``dts=`` ('cd_ekf', 'cd_sgp_filter'; dt is then None): one interval per step -- differences only,
+    exact=None resolves to False and exact=True is refused (the tangent kernels take one dt)."""
+    exact = _exact_with_times(_exact_with_substeps(_exact_with_gaps(exact, missing), method, substeps), method, dts, dt)
+    if dts is not None:                               # checked once, here: every launch of the search passes the same intervals
+        from chirpgp_amd import _engine as E
+        shape = E._leading_shape(ys)
+        E.check_intervals(dts, shape[-1], None if len(shape) == 1 else shape[0])
     if exact is None:
         exact = _exact_by_default(method, build, Xi, 1, build_kw)
     if exact:
@@ -514,7 +544,7 @@ def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=No
         for i in range(P):
             batch[1 + 2 * i, i] += h[i]
             batch[2 + 2 * i, i] -= h[i]
-        nll = batched_nll(method, build, batch, ys, Xi, dt, sgps, missing=missing, substeps=substeps, **build_kw)
+        nll = batched_nll(method, build, batch, ys, Xi, dt, sgps, missing=missing, substeps=substeps, dts=dts, check_dts=False, **build_kw)
         grad = (nll[1::2] - nll[2::2]) / (2 * h)
         f = float(nll[0])
         if not np.isfinite(f):                      # diverged filter: the reference writes NaN results and moves on
@@ -527,7 +557,7 @@ def make_objective(method, build, ys, Xi, dt, sgps=None, rel_step=1e-6, exact=No
 DIFFERENCE_STOP = dict(ftol=1e-13, gtol=1e-7)
 
 
-def fit(method, build, init_params, ys, Xi, dt, sgps=None, maxiter=200, exact=None, *, missing=None, substeps=1, **build_kw):
+def fit(method, build, init_params, ys, Xi, dt, sgps=None, maxiter=200, exact=None, *, missing=None, substeps=1, dts=None, **build_kw):
     """L-BFGS-B from ``init_params`` (positive model parameters, e.g. [0.1, 0.1, 0.1, 1, 1, 7]).
     Returns (opt_params, scipy OptimizeResult).
 
@@ -537,24 +567,25 @@ def fit(method, build, init_params, ys, Xi, dt, sgps=None, maxiter=200, exact=No
     the last place, what any re-ordering of the filter's arithmetic does) moved the parameters at which it stopped by up to 2.2e-3 of
     their value, seven runs, although every NLL agreed to 1e-7.  With ftol 1e-13 and gtol 1e-7 the same seven runs end within 1.7e-4 of
     the optimum, for 60 - 85 objective launches where the default took 45 - 55.  (The tangent kernels' searches, exact=True, keep
-    SciPy's rule.)  ``substeps`` as in :func:`make_objective`."""
+    SciPy's rule.)  ``substeps`` and ``dts`` as in :func:`make_objective`."""
     from scipy.optimize import minimize
-    exact = _exact_with_substeps(_exact_with_gaps(exact, missing), method, substeps)
+    exact = _exact_with_times(_exact_with_substeps(_exact_with_gaps(exact, missing), method, substeps), method, dts, dt)
     if exact is None:
         exact = _exact_by_default(method, build, Xi, 1, build_kw)
-    fun = make_objective(method, build, ys, Xi, dt, sgps, exact=exact, missing=missing, substeps=substeps, **build_kw)
+    fun = make_objective(method, build, ys, Xi, dt, sgps, exact=exact, missing=missing, substeps=substeps, dts=dts, **build_kw)
     stop = {} if exact else DIFFERENCE_STOP
     res = minimize(fun, M.g_inv(np.asarray(init_params, dtype=np.float64)), jac=True, method='L-BFGS-B',
                    options=dict(maxiter=maxiter, **stop))
     return M.g(res.x), res
 
 
-def _value_and_grad_many(method, build, thetas, yss, Xi, dt, sgps, rel_step, build_kw, record_index=None, exact=None, missing=None, substeps=1):
+def _value_and_grad_many(method, build, thetas, yss, Xi, dt, sgps, rel_step, build_kw, record_index=None, exact=None, missing=None, substeps=1,
+                         dts=None):
     """NLL and gradient of R records (the rows ``record_index`` of yss; all of them by default) at R parameter vectors: exact (the tangent
     kernel, R P lanes) for the discrete EKF on the chirp / La Scala models (and, with exact=True, the sigma-point filter's, R wavefronts),
     else central differences -- ONE launch of R (2 P + 1) trials, each record read in place by its 2 P + 1 probes."""
     R, P = thetas.shape
-    exact = _exact_with_substeps(_exact_with_gaps(exact, missing), method, substeps)
+    exact = _exact_with_times(_exact_with_substeps(_exact_with_gaps(exact, missing), method, substeps), method, dts, dt)
     if exact is None:
         exact = _exact_by_default(method, build, Xi, R, build_kw)
     if exact:
@@ -570,7 +601,7 @@ def _value_and_grad_many(method, build, thetas, yss, Xi, dt, sgps, rel_step, bui
     batch[:, 1 + 2 * idx, idx] += h
     batch[:, 2 + 2 * idx, idx] -= h
     nll = batched_nll(method, build, batch.reshape(-1, P), yss, Xi, dt, sgps, record_index=record_index, missing=missing, substeps=substeps,
-                      **build_kw).reshape(R, 2 * P + 1)
+                      dts=dts, check_dts=False, **build_kw).reshape(R, 2 * P + 1)      # (fit_many has checked the intervals)
     f = nll[:, 0].copy()
     grad = (nll[:, 1::2] - nll[:, 2::2]) / (2 * h)
     f[~np.isfinite(f)] = np.inf
@@ -578,7 +609,7 @@ def _value_and_grad_many(method, build, thetas, yss, Xi, dt, sgps, rel_step, bui
 
 
 def fit_many(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=200, history=10, gtol=1e-5, ftol=2.2e-9,
-             rel_step=1e-6, exact=None, *, missing=None, substeps=1, **build_kw):
+             rel_step=1e-6, exact=None, *, missing=None, substeps=1, dts=None, **build_kw):
     """Maximum likelihood for R measurement records in lock step: limited-memory BFGS with a backtracking (Armijo) line
     search, every record with its own iterate, history and step length, and every probe of every record evaluated in
     the SAME kernel launch (R x 13 trials for the chirp model).  A launch costs T x 0.35 us whatever the batch up to
@@ -586,16 +617,22 @@ def fit_many(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=200, hi
     run one L-BFGS-B per record.  Same objective, same unconstrained parametrisation g() as :func:`fit`.
 
     yss (R, T);  init_params (P,) or (R, P) positive model parameters  ->  (opt_params (R, P), info dict).
-    ``missing='skip'``: NaN samples of the records are gaps (difference gradient only, as in :func:`make_objective`); ``substeps`` likewise."""
+    ``missing='skip'``: NaN samples of the records are gaps (difference gradient only, as in :func:`make_objective`); ``substeps`` likewise;
+    ``dts=`` (dt then None): (T,) one time grid for all records or (R, T) one per record, difference gradient only."""
     from chirpgp_amd import _engine as E
     _substeps_kw(method, substeps)                    # a count or a method that cannot take it fails here, before anything is copied
+    exact = _exact_with_times(exact, method, dts, dt)
+    if dts is not None:                               # checked once, on the host: every launch of the search passes the same grids
+        shape = E._leading_shape(yss)
+        dts = E.check_intervals(dts, shape[-1], None if len(shape) == 1 else shape[0])
+        dts = dts[0] if dts.shape[0] == 1 else dts
     yss = E.dev(yss)                                 # uploaded once; every probe of every line search reads it in place
     if yss.ndim == 1:
         yss = yss[None, :]
     R = yss.shape[0]
     x = np.array(np.broadcast_to(M.g_inv(np.asarray(init_params, dtype=np.float64)), (R, np.shape(init_params)[-1])))
     P = x.shape[1]
-    f, g = _value_and_grad_many(method, build, x, yss, Xi, dt, sgps, rel_step, build_kw, exact=exact, missing=missing, substeps=substeps)
+    f, g = _value_and_grad_many(method, build, x, yss, Xi, dt, sgps, rel_step, build_kw, exact=exact, missing=missing, substeps=substeps, dts=dts)
     S, Y = [], []                                    # lists of (R, P) pairs, newest last
     done = ~np.isfinite(f)
     nit = np.zeros(R, dtype=int)
@@ -631,7 +668,7 @@ def fit_many(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=200, hi
             idx = np.flatnonzero(searching)
             xt = x[idx] + step[idx, None] * d[idx]
             ft, gt = _value_and_grad_many(method, build, xt, yss, Xi, dt, sgps, rel_step, build_kw, record_index=idx, exact=exact, missing=missing,
-                                          substeps=substeps)
+                                          substeps=substeps, dts=dts)
             launches += 1
             ok = ft <= f[idx] + 1e-4 * step[idx] * gd[idx]
             acc = idx[ok]
@@ -652,17 +689,18 @@ def fit_many(method, build, init_params, yss, Xi, dt, sgps=None, maxiter=200, hi
     return M.g(x), dict(fun=f, grad=g, nit=nit, launches=launches, converged=done)
 
 
-def grid_search(method, build, grid, yss, Xi, dt, sgps=None, *, substeps=1, **build_kw):
+def grid_search(method, build, grid, yss, Xi, dt, sgps=None, *, substeps=1, dts=None, **build_kw):
     """Parameter-grid MLE sweep (BASELINE config C5: "batch x param-grid MLE sweep"): the final NLL of ``method`` at every
     grid point for every record, in ONE launch of R G trials -- G parameter vectors per record, each record read in place.
 
     grid (G, P) positive model parameters; yss (R, T) or (T,)  ->  (best (R, P), nll (R, G), argmin (R,)).
-    A diverged grid point (NaN / inf NLL) never wins; a record whose every grid point diverges gets NaN parameters."""
+    A diverged grid point (NaN / inf NLL) never wins; a record whose every grid point diverges gets NaN parameters.
+    ``dts=`` ('cd_ekf', 'cd_sgp_filter'; dt then None): one interval per step, (T,) or one time grid per record."""
     grid = np.atleast_2d(np.asarray(grid, dtype=np.float64))
     G = grid.shape[0]
     R = 1 if np.ndim(yss) == 1 else int(np.shape(yss)[0])
     thetas = np.tile(M.g_inv(grid), (R, 1))                     # record-major: the G rows of a record are consecutive trials
-    nll = batched_nll(method, build, thetas, yss, Xi, dt, sgps, substeps=substeps, **build_kw).reshape(R, G)
+    nll = batched_nll(method, build, thetas, yss, Xi, dt, sgps, substeps=substeps, dts=dts, **build_kw).reshape(R, G)
     masked = np.where(np.isfinite(nll), nll, np.inf)
     arg = np.argmin(masked, axis=1)
     best = M.g(M.g_inv(grid))[arg]                              # the parameters the filter actually ran with

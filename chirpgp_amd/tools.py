@@ -9,13 +9,39 @@ whatever the batch or the number of ranks."""
 import numpy as np
 import scipy.linalg
 
-__all__ = ['rmse', 'lti_sde_to_disc', 'simulate_lgssm', 'simulate_sde', 'simulate_sde_init', 'simulate_measurements', 'simulate_initial']
+__all__ = ['rmse', 'intervals', 'lti_sde_to_disc', 'simulate_lgssm', 'simulate_sde', 'simulate_sde_init', 'simulate_measurements', 'simulate_initial']
 
 
 def rmse(x1, x2, reduce_sum=True):
     """Root mean square error over axis 0 (tools.py:279-293)."""
     val = np.sqrt(np.mean((np.asarray(x1) - np.asarray(x2)) ** 2, axis=0))
     return np.sum(val) if reduce_sum else val
+
+
+def intervals(ts, t0=None):
+    """Time stamps -> the ``dts=`` of cd_ekf / cd_eks / cd_sgp_filter / cd_sgp_smoother: dts[t] = ts[t] - ts[t - 1], and dts[0] = ts[0] - t0
+    the time from the initial condition (m0, P0) to the first sample.  ``t0`` defaults to ts[0] - (ts[1] - ts[0]), one first interval
+    before the first sample -- what the plain call's prediction over dt ahead of its first update amounts to on a grid.  ``ts`` is (T,),
+    or (R, T) with one row per record (t0 then a scalar or (R,)); equal stamps are two samples at one instant (a zero interval).  A stamp
+    that is not finite or runs backwards is a ValueError that names it."""
+    ts = np.asarray(ts, dtype=np.float64)
+    if ts.ndim not in (1, 2) or ts.shape[-1] < 1:
+        raise ValueError(f'ts must be (T,) or (R, T) with T >= 1, got {ts.shape}')
+    if t0 is None:
+        if ts.shape[-1] < 2:
+            raise ValueError('one time stamp has no first interval to copy: pass t0')
+        t0 = ts[..., 0] - (ts[..., 1] - ts[..., 0])
+    t0 = np.asarray(t0, dtype=np.float64)
+    if t0.shape not in ((), ts.shape[:-1]):
+        raise ValueError(f't0 must be a scalar or one value per record, got {t0.shape}')
+    dts = np.diff(ts, axis=-1, prepend=np.broadcast_to(t0, ts.shape[:-1])[..., None])
+    bad = ~(np.isfinite(dts) & (dts >= 0.0))
+    if bad.any():
+        at = tuple(int(v) for v in np.argwhere(bad)[0])
+        where = f'ts[{at[0]}]' if ts.ndim == 1 else f'ts[{at[0]}, {at[1]}]'
+        raise ValueError(f'{where} = {float(ts[at])!r} is not finite or lies before its predecessor ({"t0" if at[-1] == 0 else "the stamp before it"}): '
+                         f'time stamps must be finite and non-decreasing')
+    return dts
 
 
 def lti_sde_to_disc(A, B, dt):
